@@ -1,7 +1,17 @@
 """Headline benchmark: encoded nodes/s on synthetic 60,000-node / 300,000-edge
 shards (BASELINE.json configs[2]), fp16 model, inputs resident in HBM.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: set-up, warm-up, the K timed steps, the
+outputs if ``--dump-outputs`` is given, and the result line.  Everything else it can measure
+(the repeated leg, ``roofline``, ``kernels_ms``, ``distance``, ``cpu_baseline``) runs only with
+``--full``; those keys are null in a plain run.
+
+``--dump-outputs DIR`` (rank 0): after the timed steps, the embeddings of the shard the last
+timed step encoded, as the caller of the hot path receives them (60,000 x 128, fp16 widened to
+float32, 30.7 MB), are written to ``DIR/embeddings.npy``.  The shards are seeded, so the same
+arguments give the same inputs on every run.
 
 ``--gpus N`` with N > 1 (or ``--spawn``) outside torch.distributed.run: this process starts
 the N ranks itself (``python -m torch.distributed.run --nnodes=1 --nproc-per-node N
@@ -20,14 +30,14 @@ Multi-GPU: shards are independent, every rank encodes its own shards, there is n
 collective ("weak" scaling); the only communication is the barrier and the MAX-reduction of
 the elapsed time.
 
-Before the W warm-up steps the script runs the same steps untimed for 0.25 s
-(GFY_BENCH_SETTLE_S): set-up, so that every pre-bound step exists and the part has
+Before the W warm-up steps the script builds every pre-bound step the K steps use (each run
+once) and runs batches untimed for 0.25 s (GFY_BENCH_SETTLE_S): set-up, so that the part has
 reached its working clocks whatever K and W are.  Then W warm-up steps, barrier +
-synchronize, EXACTLY K timed steps, synchronize, MAX over ranks.  When those K steps took less
-than 10 ms (the driver's K=20 is 1.5 ms) the same leg is repeated until 10 ms are covered and
+synchronize, EXACTLY K timed steps, synchronize, MAX over ranks.  With ``--full``, when those K
+steps took less than 10 ms (K=20 is 1.5 ms) the same leg is repeated until 10 ms are covered and
 reported beside the contract values (``timed_ms``, ``repeated``); ``value`` stays the K-step one.
 
-Rank 0 prints ONE JSON line.  Besides the contract keys it carries
+Rank 0 prints ONE JSON line.  Besides the contract keys it carries, with ``--full``
   roofline      dominant kernel (k_gine_layer_w, or k_gine_layer_f16 with --batch 1):
                 algorithmic bytes per launch ((512·N + 9·E) x the shards of one launch + layer
                 weights) ÷ its mean duration IN THE
@@ -89,9 +99,16 @@ def parse() -> argparse.Namespace:
                         help="batches in flight per GPU (HIP streams)")
     parser.add_argument("--batch", type=int, default=4,
                         help="shards per launch sequence (gfy_encode_coo_batch, 1..16)")
+    parser.add_argument("--full", action="store_true",
+                        help="also run the repeated leg, the per-kernel roofline, the distance "
+                             "leg and the CPU baseline (off: set-up, warm-up, timed steps only)")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="write the last timed step's embeddings to DIR/embeddings.npy "
+                             "(float32, rank 0)")
     parser.add_argument("--distance-rows", type=int, default=1_000_000,
-                        help="rows of the all-pairs nearest leg (0 = skip it)")
-    parser.add_argument("--no-cpu-baseline", action="store_true")
+                        help="with --full: rows of the all-pairs nearest leg (0 = skip it)")
+    parser.add_argument("--no-cpu-baseline", action="store_true",
+                        help="with --full: skip the CPU baseline")
     parser.add_argument("--cpu-seconds", type=float, default=12.0)
     parser.add_argument("--workload", choices=("encode", "cross-shard"), default="encode",
                         help="cross-shard = BASELINE configs[4] in miniature: shard-parallel "
@@ -397,6 +414,10 @@ def main() -> None:
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be >= 1")
+    if args.dump_outputs is not None and args.workload != "encode":
+        raise SystemExit("bench.py: --dump-outputs covers the encode workload only")
     if "RANK" not in os.environ and (args.gpus > 1 or args.spawn):
         launch_ranks(args)            # before anything touches the GPU; does not return
     rank = int(os.environ.get("RANK", "0"))
@@ -471,12 +492,28 @@ def main() -> None:
                 [(*inputs[(first + k) % POOL], None, outputs[lane][k]) for k in range(count)])
         step(handles[lane])
 
-    def run(steps: int) -> None:
-        """`steps` shards, batch by batch, round-robin over the lanes."""
-        done, index = 0, 0
+    def run(steps: int) -> tuple[int, int]:
+        """`steps` shards, batch by batch, round-robin over the lanes; returns the lane and the
+        output slot of the last shard."""
+        done, index, last = 0, 0, (0, 0)
         while done < steps:
             count = min(batch, steps - done)
             call(index % lanes, done, count)
+            last = (index % lanes, count - 1)
+            done += count
+            index += 1
+        return last
+
+    def prebind(steps: int) -> None:
+        """Build (and run once) every pre-bound step that `run(steps)` uses, without running
+        all `steps` shards."""
+        done, index, seen = 0, 0, set()
+        while done < steps:
+            count = min(batch, steps - done)
+            key = (index % lanes, done % POOL, count)
+            if key not in seen:
+                seen.add(key)
+                call(index % lanes, done, count)
             done += count
             index += 1
 
@@ -488,7 +525,7 @@ def main() -> None:
     # set-up, not measurement: build every pre-bound step once and let the part reach its
     # working clocks (a cold MI355X needs tens of milliseconds of load), whatever W is
     settle = time.perf_counter() + float(os.environ.get("GFY_BENCH_SETTLE_S", "0.25"))
-    run(args.steps)
+    prebind(args.steps)
     torch.cuda.synchronize(device)
     while time.perf_counter() < settle:
         run(batch * lanes)
@@ -497,7 +534,7 @@ def main() -> None:
     run(args.warmup)
     fence()
     began = time.perf_counter()
-    run(args.steps)
+    last_lane, last_slot = run(args.steps)
     torch.cuda.synchronize(device)
     elapsed = time.perf_counter() - began
     if distributed:
@@ -505,11 +542,18 @@ def main() -> None:
         dist.all_reduce(worst, op=dist.ReduceOp.MAX)
         elapsed = float(worst.item())
     fence()
-    # the K timed steps may cover very little time (the driver runs K = 20: under 2 ms): the
+    # what the last timed step computed: the embeddings of shard (K - 1) mod POOL, read before
+    # anything else writes the lane's output blocks
+    if rank == 0 and args.dump_outputs is not None:
+        folder = Path(args.dump_outputs)
+        folder.mkdir(parents=True, exist_ok=True)
+        np.save(folder / "embeddings.npy",
+                outputs[last_lane][last_slot].float().cpu().numpy())
+    # --full: the K timed steps may cover very little time (K = 20: under 2 ms): the
     # same K steps are repeated until at least MIN_TIMED_S have been timed, and both figures are
     # reported — `value` stays the contract's (exactly K steps)
     repeats, long_elapsed = 0, 0.0
-    if rank == 0 or distributed:
+    if args.full and (rank == 0 or distributed):
         repeats = max(1, int(np.ceil(MIN_TIMED_S / max(elapsed, 1e-6))))
         repeats = min(repeats, 4096)
         fence()
@@ -527,7 +571,7 @@ def main() -> None:
     # ---- per-kernel device time, rank 0 ------------------------------------------------------
     roofline = None
     kernels = None
-    if rank == 0:
+    if rank == 0 and args.full:
         full = min(batch, max(args.steps, 1))          # shards per launch in what follows
         launch_bytes, launch_flops = LAYER_BYTES * full, LAYER_FLOPS * full
 
@@ -624,11 +668,11 @@ def main() -> None:
                    "last_layer_with_head_normalise_ms": mean[-2]}
 
     distance = None
-    if rank == 0 and world == 1 and args.distance_rows > 0:
+    if args.full and rank == 0 and world == 1 and args.distance_rows > 0:
         distance = distance_leg(args.distance_rows, device)
 
     baseline = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         baseline = cpu_baseline(args.cpu_seconds)
 
     if rank == 0:

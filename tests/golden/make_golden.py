@@ -19,6 +19,11 @@ Fixture list:
                         output; fp32-model output of the first 16; per-stage
                         tensors of the first 4
   rouskin_full.npz  F4b whole shard (897,588 nodes): every 97th output row
+  rouskin64_aten_gemm.json
+                    F4c SHA-256 of the fp16 output of F4a with oneDNN off: torch's
+                        own GEMM kernels, which it uses where the CPU has no
+                        AVX512-FP16 / AMX-FP16 (F4a was recorded on a CPU with
+                        AVX512-FP16)
   synthetic.npz     F5  roofline_shard(seed 0/1): 1,024 sampled output rows each
   arbitrary.npz     F6  arbitrary_shard(seed 0): every 4th output row
   integers.json     F7  SHA-256 of the reference builder's arrays for the whole
@@ -99,6 +104,25 @@ def sha(array: np.ndarray) -> str:
     return hashlib.sha256(np.ascontiguousarray(array).tobytes()).hexdigest()
 
 
+def aten_gemm_fixture(encoder, shard) -> None:
+    """F4c: ``python -c "import make_golden as m; m.aten_gemm_fixture_main()"`` from this
+    directory records it alone."""
+    enabled = torch.backends.mkldnn.enabled
+    torch.backends.mkldnn.enabled = False
+    try:
+        out = cat(encoder.encode_graphs(shard))
+    finally:
+        torch.backends.mkldnn.enabled = enabled
+    fixture = {"out.m16": {"sha256": sha(out), "shape": list(out.shape), "dtype": str(out.dtype)}}
+    (HERE / "rouskin64_aten_gemm.json").write_text(json.dumps(fixture, indent=1) + "\n")
+
+
+def aten_gemm_fixture_main() -> None:
+    torch.manual_seed(0)
+    full = ref.GraphBuilder().build_shard(ref.read_rna_table(TSV))
+    aten_gemm_fixture(ref.Ginfinity.load(), full.slice(0, 64))
+
+
 def main() -> None:
     torch.manual_seed(0)
     enc16 = ref.Ginfinity.load()
@@ -159,6 +183,7 @@ def main() -> None:
     fixture.update({f"stage.{k}": v for k, v in
                     traced_encode(enc16, full.slice(0, 4)).items()})
     np.savez_compressed(HERE / "rouskin64.npz", **fixture)
+    aten_gemm_fixture(enc16, first64)
 
     whole = cat(enc16.encode_graphs(full))
     np.savez_compressed(HERE / "rouskin_full.npz",

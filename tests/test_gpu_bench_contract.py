@@ -1,6 +1,6 @@
 """bench.py prints ONE JSON line with the keys the driver reads (the contract in the task
-statement), plus the `roofline` and `cpu_baseline` objects.  Run as a child process, the way
-the driver runs it."""
+statement), plus, with `--full`, the `roofline` and `cpu_baseline` objects.  Run as a child
+process, the way the driver runs it."""
 from __future__ import annotations
 
 import json
@@ -9,6 +9,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,8 @@ def _run(*flags: str) -> dict:
 
 
 def test_bench_line_contract():
-    line = _run("--steps", "40", "--warmup", "8", "--cpu-seconds", "2", "--distance-rows", "65536")
+    line = _run("--full", "--steps", "40", "--warmup", "8", "--cpu-seconds", "2",
+                "--distance-rows", "65536")
     assert line["metric"] == "encoded nodes/sec on 60k-node/300k-edge shards"
     assert line["unit"] == "nodes/s" and line["higher_is_better"] is True
     assert (line["n_gpus"], line["steps"], line["warmup"]) == (1, 40, 8)
@@ -58,8 +60,30 @@ def test_bench_line_contract():
     assert cpu["cores"] >= 1 and 0 < cpu["value"] < line["value"] and cpu["sample"]
 
 
+def test_plain_run_reports_the_headline_only_and_dumps_the_last_step(tmp_path, golden):
+    """Without `--full`: the contract keys, the extra legs null; `--dump-outputs` writes what the
+    last timed step computed.  21 steps over the pool of 4 shards: the last one is shard
+    20 mod 4 = 0, the seed-0 synthetic shard whose rows the reference itself encoded."""
+    out = tmp_path / "outputs"
+    line = _run("--steps", "21", "--warmup", "4", "--dump-outputs", str(out))
+    assert line["metric"] == "encoded nodes/sec on 60k-node/300k-edge shards"
+    assert line["unit"] == "nodes/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "f16" and (line["steps"], line["warmup"]) == (21, 4)
+    assert line["value"] > 1e8
+    assert abs(line["value"] - 60000 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    for key in ("repeated", "roofline", "kernels_ms", "distance", "cpu_baseline"):
+        assert line[key] is None, key
+    assert sorted(p.name for p in out.iterdir()) == ["embeddings.npy"]
+    got = np.load(out / "embeddings.npy")
+    assert got.dtype == np.float32 and got.shape == (60000, 128) and np.isfinite(got).all()
+    assert np.abs(np.linalg.norm(got.astype(np.float64), axis=1) - 1.0).max() < 1e-2
+    g = golden("synthetic.npz")
+    want = g["seed0.out.m16"].astype(np.float64)
+    assert np.abs(got[g["seed0.rows"]].astype(np.float64) - want).max() <= 1e-3
+
+
 def test_bench_line_one_stream_without_cpu_baseline():
-    line = _run("--steps", "20", "--warmup", "4", "--streams", "1", "--no-cpu-baseline",
+    line = _run("--full", "--steps", "20", "--warmup", "4", "--streams", "1", "--no-cpu-baseline",
                 "--distance-rows", "0")
     assert line["cpu_baseline"] is None and line["steps"] == 20 and line["distance"] is None
     assert line["config"]["streams_per_gpu"] == 1
@@ -68,8 +92,8 @@ def test_bench_line_one_stream_without_cpu_baseline():
 def test_bench_through_the_rank_launcher_world_size_one():
     """`--spawn` = what `--gpus N>1` does: the parent starts torch.distributed.run, the one
     rank creates the RCCL group, rank 0's line is relayed."""
-    line = _run("--gpus", "1", "--spawn", "--steps", "20", "--warmup", "4", "--no-cpu-baseline",
-                "--distance-rows", "0")
+    line = _run("--gpus", "1", "--spawn", "--full", "--steps", "20", "--warmup", "4",
+                "--no-cpu-baseline", "--distance-rows", "0")
     assert line["n_gpus"] == 1 and line["config"]["rccl_ranks"] == 1
     assert line["value"] > 1e8 and line["cpu_baseline"] is None
 
@@ -95,7 +119,7 @@ def test_two_ranks_rehearsed_on_one_gpu_over_gloo():
     done = subprocess.run(
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
          "--standalone", "--local-addr", "127.0.0.1", str(ROOT / "bench.py"),   # (a free port)
-         "--gpus", "2", "--steps", "40", "--warmup", "8"],
+         "--gpus", "2", "--full", "--steps", "40", "--warmup", "8"],
         cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert done.returncode == 0, done.stderr[-2000:]
     lines = [line for line in done.stdout.splitlines() if line.startswith("{")]

@@ -70,13 +70,17 @@ def test_argument_errors_without_a_gpu(checkpoint):
     lib.gfy_upload_ring_destroy(None)
 
 
-def test_layer_kernel_keeps_its_register_and_scratch_budget():
+def test_layer_kernel_keeps_its_register_and_scratch_budget(tmp_path):
     """The fused layer kernel must not spill: a scratch reload is a `vmcnt` wait that drains the
     LDS-DMA look-ahead, and more than 256 VGPRs would halve the waves per SIMD (two per SIMD
-    is what one 512-thread workgroup per CU needs).  hipcc cross-compiles, no GPU needed."""
+    is what one 512-thread workgroup per CU needs).  hipcc cross-compiles, no GPU needed.
+    The script's temporary files and the assembly it leaves stay in this test's directory."""
+    import os
     import subprocess
     script = Path(__file__).resolve().parents[1] / "tools" / "kernel_resources.sh"
-    done = subprocess.run(["bash", str(script)], capture_output=True, text=True, timeout=600)
+    env = dict(os.environ, TMPDIR=str(tmp_path), GFY_ASM_OUT=str(tmp_path / "gine_f16.s"))
+    done = subprocess.run(["bash", str(script)], capture_output=True, text=True, timeout=600,
+                          env=env)
     assert done.returncode == 0, done.stderr[-2000:]
     layers = [line for line in done.stdout.splitlines() if "k_gine_layer_f16" in line]
     assert len(layers) == 4, done.stdout            # <kResidual, kHead> x 2 x 2

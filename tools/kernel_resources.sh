@@ -1,6 +1,7 @@
 #!/bin/bash
 # Registers, spills and scratch of the encode kernels as hipcc allocates them (no GPU needed):
 #   bash tools/kernel_resources.sh [extra hipcc flags]
+# The assembly is left in $GFY_ASM_OUT (default /tmp/gine_f16.s).
 set -e
 cd "$(dirname "$0")/../ginfinity_amd/csrc"
 OUT=$(mktemp -d)
@@ -17,5 +18,5 @@ for block in meta.split('  - .agpr_count:')[1:]:
           f"spilled {field('vgpr_spill_count'):>3s} sgpr {field('sgpr_count'):>3s} "
           f"scratch {field('private_segment_fixed_size')} B")
 PY
-cp "$OUT/gine_f16-hip-amdgcn-amd-amdhsa-gfx950.s" /tmp/gine_f16.s
+cp "$OUT/gine_f16-hip-amdgcn-amd-amdhsa-gfx950.s" "${GFY_ASM_OUT:-/tmp/gine_f16.s}"
 rm -rf "$OUT"

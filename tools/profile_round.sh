@@ -15,20 +15,20 @@ cd /tmp && export TMPDIR=/tmp
 if [ "$PART" != "b" ]; then
 # 1. bench lines: the default (batches of 4 shards, 2 in flight), one batch at a time, and one
 #    SHARD at a time (single-round launches: the round-2 kernel with the fused head)
-timeout -k 10 400 python3 $R/bench.py --steps 960 --warmup 96 > $OUT/bench_line.json 2> $OUT/bench_line.err || exit 1
-timeout -k 10 200 python3 $R/bench.py --steps 960 --warmup 96 --streams 1 --no-cpu-baseline --distance-rows 0 > $OUT/bench_1stream_line.json 2>> $OUT/bench_line.err || exit 1
-timeout -k 10 200 python3 $R/bench.py --steps 960 --warmup 96 --streams 1 --batch 1 --no-cpu-baseline --distance-rows 0 > $OUT/bench_single_line.json 2>> $OUT/bench_line.err || exit 1
+timeout -k 10 400 python3 $R/bench.py --full --steps 960 --warmup 96 > $OUT/bench_line.json 2> $OUT/bench_line.err || exit 1
+timeout -k 10 200 python3 $R/bench.py --full --steps 960 --warmup 96 --streams 1 --no-cpu-baseline --distance-rows 0 > $OUT/bench_1stream_line.json 2>> $OUT/bench_line.err || exit 1
+timeout -k 10 200 python3 $R/bench.py --full --steps 960 --warmup 96 --streams 1 --batch 1 --no-cpu-baseline --distance-rows 0 > $OUT/bench_single_line.json 2>> $OUT/bench_line.err || exit 1
 # ... and what the driver runs (20 steps, 5 warm-up): the repeated leg covers >= 10 ms
-timeout -k 10 200 python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --distance-rows 0 > $OUT/bench_driver_line.json 2>> $OUT/bench_line.err || exit 1
+timeout -k 10 200 python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --distance-rows 0 > $OUT/bench_driver_line.json 2>> $OUT/bench_line.err || exit 1
 
 [ "$PART" = "lines" ] && { echo done; exit 0; }   # "lines": the bench lines only (after pmc_summary.py has refreshed the counter files they quote)
 # 2. per-kernel durations of the same commands (kernel trace + stats only)
 for S in 1 2; do
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt$S -o kt --output-format csv -- \
-    python3 $R/bench.py --steps 960 --warmup 96 --streams $S --no-cpu-baseline --distance-rows 0 > $OUT/bench_${S}stream_line_profiled.json 2> $OUT/kt$S.err || exit 1
+    python3 $R/bench.py --full --steps 960 --warmup 96 --streams $S --no-cpu-baseline --distance-rows 0 > $OUT/bench_${S}stream_line_profiled.json 2> $OUT/kt$S.err || exit 1
 done
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/kt_single -o kt --output-format csv -- \
-  python3 $R/bench.py --steps 960 --warmup 96 --streams 1 --batch 1 --no-cpu-baseline --distance-rows 0 > $OUT/bench_single_line_profiled.json 2> $OUT/kt_single.err || exit 1
+  python3 $R/bench.py --full --steps 960 --warmup 96 --streams 1 --batch 1 --no-cpu-baseline --distance-rows 0 > $OUT/bench_single_line_profiled.json 2> $OUT/kt_single.err || exit 1
 
 # 3. HBM traffic counters: separate passes, kernel trace only (MI355X_MICROARCH.md, HBM section).
 #    240,000 nodes in one graph = four shards' worth: the launches a batch of 4 makes
