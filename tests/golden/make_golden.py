@@ -28,6 +28,11 @@ Fixture list:
   arbitrary.npz     F6  arbitrary_shard(seed 0): every 4th output row
   integers.json     F7  SHA-256 of the reference builder's arrays for the whole
                         rouskin shard, micro-batch boundaries at default limits
+  architectures.npz F8  the non-bundled architectures of tests/arch_models.py
+                        (seeded random weights): fp16 model / fp16 output and fp32
+                        model / fp32 output on 24 rouskin records (encode_many) and on
+                        an arbitrary_shard of the architecture's spec, strided rows;
+                        ``python make_golden.py architectures`` records it alone
 """
 from __future__ import annotations
 
@@ -53,13 +58,15 @@ ARRAYS = ("node_features", "edge_index", "edge_types", "node_ptr", "edge_ptr",
 
 
 def to_reference_shard(shard) -> "ref.GraphShard":
+    spec = shard.spec
     return ref.GraphShard(
         identifiers=shard.identifiers, sequences=shard.sequences,
         structures=shard.structures, node_features=shard.node_features,
         edge_index=shard.edge_index, edge_types=shard.edge_types,
         node_ptr=shard.node_ptr, edge_ptr=shard.edge_ptr,
-        spec=ref.GraphSpec.bundled(), residue_index=shard.residue_index,
-        node_roles=shard.node_roles)
+        spec=ref.GraphSpec(struct_feature=spec.struct_feature, positional=spec.positional,
+                           edge_dim=spec.edge_dim, extra_edges=spec.extra_edges),
+        residue_index=shard.residue_index, node_roles=shard.node_roles)
 
 
 def traced_encode(encoder, shard) -> dict[str, np.ndarray]:
@@ -252,5 +259,60 @@ def main() -> None:
     print("fixtures written to", HERE)
 
 
+def save_npz_reproducibly(path: Path, arrays: dict) -> None:
+    """``np.savez_compressed`` without the wall-clock time in the archive: the same arrays give
+    the same bytes, run after run (``np.load`` reads it as any .npz)."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", compression=zipfile.ZIP_DEFLATED) as archive:
+        for name, value in arrays.items():
+            buffer = io.BytesIO()
+            np.lib.format.write_array(buffer, np.asanyarray(value), allow_pickle=False)
+            entry = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            entry.compress_type = zipfile.ZIP_DEFLATED
+            archive.writestr(entry, buffer.getvalue())
+
+
+def architectures_fixture() -> None:
+    """F8: for each architecture of ``arch_models.VARIANTS``, its model directory (seeded
+    ``random_state`` weights) loaded by the reference itself, both model dtypes, two inputs."""
+    import dataclasses
+    import tempfile
+    sys.path.insert(0, str(ROOT / "tests"))
+    import arch_models as A
+    torch.manual_seed(0)
+    records = ref.read_rna_table(TSV)[:A.ROUSKIN_RECORDS]
+    rouskin_stride, arbitrary_stride = A.STRIDES
+    fixture = {"rouskin.records": np.int64(A.ROUSKIN_RECORDS),
+               "rouskin.stride": np.int64(rouskin_stride),
+               "arbitrary.stride": np.int64(arbitrary_stride)}
+    for name in A.VARIANTS:
+        config, seed = A.variant(name)
+        shard = A.arbitrary_input(config)
+        assert set(np.unique(shard.edge_types)) == set(range(config.edge_dim))
+        assert np.bincount(shard.edge_index[1]).max() > 8
+        with tempfile.TemporaryDirectory() as directory:
+            A.write_model_dir(directory, config, seed)
+            enc16 = ref.Ginfinity.load(model_dir=directory)
+            enc32 = ref.Ginfinity.load(model_dir=directory, full_precision=True)
+        fixture[f"{name}.seed"] = np.int64(seed)
+        fixture[f"{name}.config"] = np.array(json.dumps(
+            {**dataclasses.asdict(config), "extra_edges": list(config.extra_edges)},
+            sort_keys=True))
+        fixture[f"{name}.pack_sha256"] = np.array(A.pack_sha256(config, seed))
+        for tag, encoder, dtype in (("m16", enc16, "float16"), ("m32", enc32, "float32")):
+            rows = cat(encoder.encode_many(records, embedding_dtype=dtype))
+            fixture[f"{name}.rouskin.{tag}.{dtype}"] = rows[::rouskin_stride]
+            rows = cat(encoder.encode_graphs(to_reference_shard(shard), embedding_dtype=dtype))
+            assert rows.shape[0] == int((shard.node_roles == 0).sum())
+            fixture[f"{name}.arbitrary.{tag}.{dtype}"] = rows[::arbitrary_stride]
+    save_npz_reproducibly(HERE / "architectures.npz", fixture)
+    print("written", HERE / "architectures.npz")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["architectures"]:
+        architectures_fixture()
+    else:
+        main()
+        architectures_fixture()
