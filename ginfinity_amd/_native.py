@@ -59,6 +59,15 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_build_graphs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                  c_int64, c_int64, c_int, c_int, c_int, c_void_p,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "gfy_window_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gfy_window_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                  c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                  c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gfy_window_emit": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p,
+                                c_void_p, c_void_p, c_int64, c_int64, c_int64, c_void_p,
+                                c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
+                                c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gfy_csr_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gfy_build_csr": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -43,7 +43,7 @@ import torch
 from . import _native as native
 from .engine import DeviceEncoder, attach_records, device_output_dtype, records_pay
 from .host import HostEncoder
-from .graph import Graph, GraphBuilder, GraphShard, shard_text
+from .graph import Graph, GraphBuilder, GraphShard, shard_text, window_text
 from .records import RNA
 from .spec import (DATA_DIRECTORY, GraphCompatibilityError, GraphSpec,
                    GraphValidationError)
@@ -615,6 +615,10 @@ class Ginfinity:
         if self._host is None and not any(record.sliced for record in records):
             return self._encode_records(records, max_batch_nodes, max_batch_edges,
                                         _embedding_dtype(embedding_dtype))
+        if self._host is None:
+            return self._encode_windows(records, max_batch_nodes, max_batch_edges,
+                                        _embedding_dtype(embedding_dtype),
+                                        keep_paired_neighbours, context_hops)
         shard = GraphBuilder(
             self._graph_spec, keep_paired_neighbours=keep_paired_neighbours,
             context_hops=context_hops).build_shard(records)
@@ -704,6 +708,143 @@ class Ginfinity:
                     f"record {records[start + bad].identifier!r}: sequence or structure "
                     "text is not a balanced dot-bracket string over A, C, G, U")
         return outputs
+
+    _BAD_TEXT = ("record {!r}: sequence or structure text is not a balanced dot-bracket "
+                 "string over A, C, G, U")
+
+    def _select_windows(self, records: Sequence[RNA], keep_paired_neighbours: bool,
+                        context_hops: int, spec: GraphSpec):
+        """The first half of the device window builder: upload the distinct molecules' text,
+        ``gfy_window_select``, and bring the records' (nodes, edges) back — the ONE
+        synchronisation of the road: node_ptr / edge_ptr, the limits and the micro-batches all
+        depend on how much context every window drew in.  Returns ``(text, windows on the
+        device, positional columns on the device or None, node_ptr, edge_ptr)``."""
+        if context_hops < 1:
+            raise ValueError("context_hops must be >= 1")
+        text = window_text(records, spec)
+        if self._uploader is None:
+            self._uploader = _Uploader(self._engine.device)
+        bases, marks, mol_ptr, molecule, start, end, positional = self._uploader(
+            (text.bases, text.marks, text.mol_ptr, text.molecule, text.start, text.end,
+             text.positional()))
+        windows = self._engine.window_select(
+            bases, marks, mol_ptr, molecule, start, end,
+            keep_paired_neighbours=keep_paired_neighbours, context_hops=context_hops,
+            skip2=spec.has_skip2)
+        counts = windows.counts.cpu().numpy()
+        empty = np.flatnonzero(counts[:, 0] <= 0)      # a usable record keeps its window
+        if empty.size:
+            raise GraphValidationError(
+                self._BAD_TEXT.format(records[int(empty[0])].identifier))
+        node_ptr = np.zeros(len(records) + 1, dtype=np.int64)
+        edge_ptr = np.zeros(len(records) + 1, dtype=np.int64)
+        np.cumsum(counts[:, 0], out=node_ptr[1:])
+        np.cumsum(counts[:, 1], out=edge_ptr[1:])
+        return text, windows, positional, node_ptr, edge_ptr
+
+    def _encode_windows(self, records: Sequence[RNA], max_batch_nodes: int,
+                        max_batch_edges: int, embedding_dtype: np.dtype,
+                        keep_paired_neighbours: bool, context_hops: int) -> list[np.ndarray]:
+        """Sliced records, alone or among unsliced ones: the windows are built ON THE DEVICE
+        (``gfy_window_select`` + ``gfy_window_emit``, the arrays ``GraphBuilder`` would produce,
+        bit for bit) without building any whole molecule — each distinct molecule's text
+        crosses PCIe once, however many windows it has.  Same packing, limits and errors as
+        ``encode_graphs``, applied to the SLICED node and edge counts."""
+        if max_batch_nodes <= 0 or max_batch_edges <= 0:
+            raise ValueError("batch node and edge limits must be positive")
+        spec = self._graph_spec
+        text, windows, positional, node_ptr, edge_ptr = self._select_windows(
+            records, keep_paired_neighbours, context_hops, spec)
+        lengths, edge_counts = np.diff(node_ptr).tolist(), np.diff(edge_ptr).tolist()
+        if max(lengths) > max_batch_nodes:
+            raise ValueError("max_batch_nodes is smaller than the longest graph")
+        if max(edge_counts) > max_batch_edges:
+            raise ValueError("max_batch_edges is smaller than the largest graph")
+        torch_dtype, _code, exact = device_output_dtype(embedding_dtype)
+        engine, device = self._engine, self._engine.device
+        bounds = microbatch_bounds(lengths, edge_counts, max_batch_nodes, max_batch_edges)
+        produced = np.dtype(embedding_dtype) if exact else np.dtype(np.float64)
+        core_counts = text.core_counts
+        core_ptr = np.zeros(len(records) + 1, dtype=np.int64)
+        np.cumsum(core_counts, out=core_ptr[1:])
+        total_rows = int(core_ptr[-1])
+        host_block, fetch, _direct = self._landing(total_rows, produced, torch_dtype, exact)
+        device_rows = self._device_rows(total_rows, torch_dtype)
+        struct_states = 1 if spec.struct_feature == "A" else 3
+        pending, verdicts = [], []
+        assert MICROBATCH_GROUP <= self._uploader.slots
+        for group in _groups(len(bounds), ramp=True):
+            members = []
+            for index in group:
+                start, stop = bounds[index]
+                n0, n1 = int(node_ptr[start]), int(node_ptr[stop])
+                e0, e1 = int(edge_ptr[start]), int(edge_ptr[stop])
+                c0, c1 = int(core_ptr[start]), int(core_ptr[stop])
+                # out_rows only where a context node has to be dropped (as _pack_microbatch)
+                cores = core_ptr[start:stop + 1] if n1 - n0 != c1 - c0 else None
+                batch_nodes, batch_edges, batch_cores = self._uploader(
+                    (node_ptr[start:stop + 1], edge_ptr[start:stop + 1], cores))
+                features, edge_index, edge_types, _residue, _roles, out_rows, first_invalid = \
+                    engine.window_emit(windows, start, batch_nodes, batch_edges, batch_cores,
+                                       positional, n1 - n0, e1 - e0, c1 - c0,
+                                       struct_states=struct_states)
+                if records_pay(node_ptr[start:stop + 1], edge_ptr[start:stop + 1]):
+                    attach_records(edge_index, batch_nodes, batch_edges)
+                members.append((features, edge_index, edge_types, out_rows,
+                                device_rows[c0:c1]))
+                verdicts.append(first_invalid)
+                pending.append((c0, c1 - c0, core_counts[start:stop]))
+            engine.encode_coo_group(members)
+            ready = torch.cuda.Event()
+            ready.record(torch.cuda.current_stream(device))
+            group_row = pending[-len(members)][0]
+            last_row, last_kept, _counts = pending[-1]
+            landing = fetch(device_rows[group_row:last_row + last_kept], ready, group_row,
+                            last_row + last_kept - group_row)
+            for slot in range(len(pending) - len(members), len(pending)):
+                pending[slot] = (landing,) + pending[slot]
+        outputs: list[np.ndarray] = []
+        for job, row, kept, counts in pending:
+            job.result()
+            outputs.extend(self._splitter(counts, embedding_dtype, exact)(
+                host_block[row:row + kept]))
+        for first_invalid in verdicts:
+            bad = int(first_invalid.item())
+            if bad >= 0:
+                raise GraphValidationError(self._BAD_TEXT.format(records[bad].identifier))
+        return outputs
+
+    def build_graphs_device(self, records: Sequence[RNA], *,
+                            keep_paired_neighbours: bool = False, context_hops: int = 1,
+                            spec: GraphSpec | None = None) -> GraphShard:
+        """The shard ``GraphBuilder(spec, ...).build_shard(records)`` gives, built by the device
+        window builder and copied back to host arrays: what ``encode_many`` encodes for a list
+        with sliced records, to look at.  ``spec`` defaults to the encoder's own."""
+        if self._host is not None:
+            raise ValueError("build_graphs_device needs a 'cuda' encoder; "
+                             "GraphBuilder builds shards on the host")
+        records = list(records)
+        spec = self._graph_spec if spec is None else spec
+        text, windows, positional, node_ptr, edge_ptr = self._select_windows(
+            records, keep_paired_neighbours, context_hops, spec)
+        core_ptr = np.zeros(len(records) + 1, dtype=np.int64)
+        np.cumsum(text.core_counts, out=core_ptr[1:])
+        batch_nodes, batch_edges, batch_cores = self._uploader((node_ptr, edge_ptr, core_ptr))
+        features, edge_index, edge_types, residue, roles, _rows, first_invalid = \
+            self._engine.window_emit(
+                windows, 0, batch_nodes, batch_edges, batch_cores, positional,
+                int(node_ptr[-1]), int(edge_ptr[-1]), int(core_ptr[-1]),
+                struct_states=1 if spec.struct_feature == "A" else 3)
+        bad = int(first_invalid.item())
+        if bad >= 0:
+            raise GraphValidationError(self._BAD_TEXT.format(records[bad].identifier))
+        return GraphShard(
+            identifiers=tuple(record.identifier for record in records),
+            sequences=tuple(record.sequence for record in records),
+            structures=tuple(record.structure for record in records),
+            node_features=features.cpu().numpy(), edge_index=edge_index.cpu().numpy(),
+            edge_types=edge_types.cpu().numpy(), node_ptr=node_ptr, edge_ptr=edge_ptr,
+            spec=spec, residue_index=residue.cpu().numpy(), node_roles=roles.cpu().numpy())
 
     def encode_graph(self, graph: Graph, *,
                      embedding_dtype: np.dtype | str = np.float16) -> np.ndarray:

@@ -626,6 +626,85 @@ int gfy_build_graphs(const uint8_t* bases, const uint8_t* marks, const int64_t* 
                              edge_index, edge_types, first_invalid, (hipStream_t)stream);
 }
 
+// ---- windowed records ---------------------------------------------------------------------
+namespace {
+int check_window_text(const char* who, const uint8_t* bases, const uint8_t* marks,
+                      const int64_t* mol_ptr, int64_t molecules, int64_t molecule_nt,
+                      const int32_t* rec_mol, const int32_t* rec_start, const int32_t* rec_end,
+                      int64_t records, const void* ws, size_t ws_bytes) {
+  GFY_REQUIRE(molecules >= 1 && molecules < INT32_MAX && molecule_nt >= 1 &&
+                  molecule_nt < INT32_MAX && records >= 1 && records < INT32_MAX,
+              GFY_ERR_INVALID, "%s: molecules=%lld nt=%lld records=%lld out of range", who,
+              (long long)molecules, (long long)molecule_nt, (long long)records);
+  GFY_REQUIRE(bases && marks && mol_ptr && rec_mol && rec_start && rec_end && ws,
+              GFY_ERR_INVALID, "%s: NULL argument", who);
+  const size_t need = gfy::window_workspace_bytes(molecules, molecule_nt, records);
+  GFY_REQUIRE(ws_bytes >= need, GFY_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who,
+              ws_bytes, need);
+  return GFY_OK;
+}
+}  // namespace
+
+size_t gfy_window_workspace_bytes(int64_t n_molecules, int64_t molecule_nt, int64_t n_records) {
+  if (n_molecules < 0 || molecule_nt < 0 || n_records < 0) return 0;
+  return gfy::window_workspace_bytes(n_molecules, molecule_nt, n_records);
+}
+
+int gfy_window_select(const uint8_t* bases, const uint8_t* marks, const int64_t* mol_ptr,
+                      int64_t molecules, int64_t molecule_nt, const int32_t* rec_mol,
+                      const int32_t* rec_start, const int32_t* rec_end, int64_t records,
+                      int keep_paired_neighbours, int context_hops, int skip2, int32_t* counts,
+                      int32_t* first_invalid, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const int status = check_window_text("gfy_window_select", bases, marks, mol_ptr, molecules,
+                                       molecule_nt, rec_mol, rec_start, rec_end, records, ws,
+                                       ws_bytes);
+  if (status != GFY_OK) return status;
+  GFY_REQUIRE(context_hops >= 1, GFY_ERR_INVALID, "gfy_window_select: context_hops must be >= 1");
+  GFY_REQUIRE(counts && first_invalid, GFY_ERR_INVALID, "gfy_window_select: NULL output");
+  return launch_window_select(bases, marks, mol_ptr, molecules, molecule_nt, rec_mol, rec_start,
+                              rec_end, records, keep_paired_neighbours ? 1 : 0, context_hops,
+                              skip2 ? 1 : 0, counts, first_invalid, ws, (hipStream_t)stream);
+}
+
+int gfy_window_emit(const uint8_t* bases, const uint8_t* marks, const int64_t* mol_ptr,
+                    int64_t molecules, int64_t molecule_nt, const int32_t* rec_mol,
+                    const int32_t* rec_start, const int32_t* rec_end, int64_t records,
+                    int64_t first_record, int64_t batch_records, const int64_t* node_ptr,
+                    const int64_t* edge_ptr, const int64_t* core_ptr, int64_t n, int64_t e,
+                    int64_t n_core, int struct_states, int positional_columns, int skip2,
+                    const float* positional, float* node_features, int32_t* edge_index,
+                    uint8_t* edge_types, int32_t* residue_index, uint8_t* node_roles,
+                    int32_t* out_rows, int32_t* first_invalid, void* ws, size_t ws_bytes,
+                    void* stream) {
+  clear_error();
+  const int status = check_window_text("gfy_window_emit", bases, marks, mol_ptr, molecules,
+                                       molecule_nt, rec_mol, rec_start, rec_end, records, ws,
+                                       ws_bytes);
+  if (status != GFY_OK) return status;
+  GFY_REQUIRE(first_record >= 0 && batch_records >= 1 && first_record + batch_records <= records,
+              GFY_ERR_INVALID, "gfy_window_emit: records [%lld, +%lld) outside 0..%lld",
+              (long long)first_record, (long long)batch_records, (long long)records);
+  GFY_REQUIRE(n >= 1 && n < INT32_MAX && e >= 0 && e < INT32_MAX && n_core >= 0 && n_core <= n,
+              GFY_ERR_INVALID, "gfy_window_emit: n=%lld e=%lld core=%lld out of range",
+              (long long)n, (long long)e, (long long)n_core);
+  GFY_REQUIRE(struct_states == 1 || struct_states == 3, GFY_ERR_INVALID,
+              "gfy_window_emit: struct_states must be 1 (paired flag) or 3 (one-hot)");
+  GFY_REQUIRE(positional_columns == 0 || positional_columns == 2, GFY_ERR_INVALID,
+              "gfy_window_emit: positional_columns must be 0 or 2");
+  GFY_REQUIRE(positional_columns == 0 || positional, GFY_ERR_INVALID,
+              "gfy_window_emit: positional columns requested but positional is NULL");
+  GFY_REQUIRE(node_ptr && edge_ptr && node_features && residue_index && node_roles &&
+                  first_invalid && (e == 0 || (edge_index && edge_types)) &&
+                  (!out_rows || core_ptr),
+              GFY_ERR_INVALID, "gfy_window_emit: NULL argument");
+  return launch_window_emit(bases, marks, mol_ptr, molecules, molecule_nt, rec_mol, rec_start,
+                            rec_end, first_record, batch_records, node_ptr, edge_ptr, core_ptr, n,
+                            e, n_core, struct_states, positional_columns, skip2 ? 1 : 0,
+                            positional, node_features, edge_index, edge_types, residue_index,
+                            node_roles, out_rows, first_invalid, ws, (hipStream_t)stream);
+}
+
 size_t gfy_encode_workspace_bytes(const gfy_encoder* enc, int64_t n, int64_t e) {
   if (!enc) return 0;
   n = n < 1 ? 1 : n;

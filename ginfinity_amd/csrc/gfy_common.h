@@ -294,6 +294,23 @@ int launch_build_graphs(const uint8_t* bases, const uint8_t* marks, const int64_
                         const float* positional, float* features, int32_t* edge_index,
                         uint8_t* edge_types, int32_t* first_invalid, hipStream_t s);
 
+// windowed records (graph_windows.hip): pair tables + chosen maps + counts, then the arrays
+size_t window_workspace_bytes(int64_t molecules, int64_t molecule_nt, int64_t records);
+int launch_window_select(const uint8_t* bases, const uint8_t* marks, const int64_t* mol_ptr,
+                         int64_t molecules, int64_t molecule_nt, const int32_t* rec_mol,
+                         const int32_t* rec_start, const int32_t* rec_end, int64_t records,
+                         int keep, int hops, int skip2, int32_t* counts, int32_t* first_invalid,
+                         void* ws, hipStream_t s);
+int launch_window_emit(const uint8_t* bases, const uint8_t* marks, const int64_t* mol_ptr,
+                       int64_t molecules, int64_t molecule_nt, const int32_t* rec_mol,
+                       const int32_t* rec_start, const int32_t* rec_end, int64_t first_record,
+                       int64_t records, const int64_t* node_ptr, const int64_t* edge_ptr,
+                       const int64_t* core_ptr, int64_t n, int64_t e, int64_t n_core,
+                       int struct_states, int positional_cols, int skip2,
+                       const float* positional, float* features, int32_t* edge_index,
+                       uint8_t* edge_types, int32_t* residue_index, uint8_t* node_roles,
+                       int32_t* out_rows, int32_t* first_invalid, void* ws, hipStream_t s);
+
 // > 64 KB of dynamic LDS is an opt-in per kernel and per DEVICE: done once when an encoder is
 // created on a device, not per encode call
 int prepare_device_f16();

@@ -44,6 +44,23 @@ class DeviceCsr:
     edges: int
 
 
+@dataclass
+class DeviceWindows:
+    """What ``DeviceEncoder.window_select`` leaves on the device for ``window_emit``: the
+    molecules' text, the records' windows, the workspace with the chosen maps, and the
+    (nodes, edges) of every record."""
+    bases: torch.Tensor       # uint8 [nt]
+    marks: torch.Tensor       # uint8 [nt]
+    mol_ptr: torch.Tensor     # int64 [M+1]
+    molecule: torch.Tensor    # int32 [R]
+    start: torch.Tensor       # int32 [R]
+    end: torch.Tensor         # int32 [R]
+    workspace: torch.Tensor   # uint8
+    counts: torch.Tensor      # int32 [R, 2]
+    first_invalid: torch.Tensor   # int32 [1]: -1, or the first unusable record
+    skip2: bool
+
+
 def _ptr(tensor: torch.Tensor | None) -> int | None:
     return None if tensor is None else tensor.data_ptr()
 
@@ -191,6 +208,82 @@ class DeviceEncoder:
                 _ptr(features), _ptr(edge_index), _ptr(edge_types), _ptr(first_invalid),
                 self._stream()), "gfy_build_graphs")
         return features, edge_index, edge_types, first_invalid
+
+    # -- windowed records (csrc/graph_windows.hip) -----------------------------------------
+    def window_select(self, bases: torch.Tensor, marks: torch.Tensor, mol_ptr: torch.Tensor,
+                      molecule: torch.Tensor, start: torch.Tensor, end: torch.Tensor, *,
+                      keep_paired_neighbours: bool, context_hops: int, skip2: bool
+                      ) -> "DeviceWindows":
+        """Text of the distinct molecules (device uint8 [nt] each, int64 [M+1] offsets) and the
+        records' (molecule, start, end) int32 [R] → the chosen map of every record in a
+        workspace that stays on the device, and ``counts`` int32 [R, 2] = (nodes, edges) of
+        every record: ``GraphBuilder._slice_graph`` (graph.py:608-695) up to the point where
+        the arrays can be laid out.  ``window_emit`` writes them."""
+        if context_hops < 1:
+            raise ValueError("context_hops must be >= 1")
+        molecules, nt = int(mol_ptr.numel()) - 1, int(bases.numel())
+        records = int(molecule.numel())
+        assert bases.dtype == torch.uint8 and marks.dtype == torch.uint8
+        assert int(marks.numel()) == nt and mol_ptr.dtype == torch.int64
+        assert molecule.dtype == start.dtype == end.dtype == torch.int32
+        assert int(start.numel()) == int(end.numel()) == records
+        with torch.cuda.device(self.device):
+            need = self._lib.gfy_window_workspace_bytes(molecules, nt, records)
+            # its own allocation, not _scratch: the maps must survive the encode calls between
+            # the select and the last emit of a call
+            workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=self.device)
+            counts = torch.empty((records, 2), dtype=torch.int32, device=self.device)
+            first_invalid = torch.empty(1, dtype=torch.int32, device=self.device)
+            native.check(self._lib.gfy_window_select(
+                _ptr(bases), _ptr(marks), _ptr(mol_ptr), molecules, nt, _ptr(molecule),
+                _ptr(start), _ptr(end), records, 1 if keep_paired_neighbours else 0,
+                int(context_hops), 1 if skip2 else 0, _ptr(counts), _ptr(first_invalid),
+                _ptr(workspace), workspace.numel(), self._stream()), "gfy_window_select")
+        return DeviceWindows(bases, marks, mol_ptr, molecule, start, end, workspace, counts,
+                             first_invalid, bool(skip2))
+
+    def window_emit(self, windows: "DeviceWindows", first_record: int, node_ptr: torch.Tensor,
+                    edge_ptr: torch.Tensor, core_ptr: torch.Tensor | None,
+                    positional: torch.Tensor | None, nodes: int, edges: int, core: int, *,
+                    struct_states: int):
+        """Records [first_record, first_record + len(node_ptr) - 1) of a ``window_select`` →
+        (node_features f32 [N,F], edge_index int32 [2,E], edge_types uint8 [E], residue_index
+        int32 [N], node_roles uint8 [N], out_rows int32 [N] or None, first_invalid int32 [1])
+        on the device.  ``node_ptr`` / ``edge_ptr`` (device int64): prefix sums of the
+        records' counts; ``core_ptr``: of their window lengths, given when ``out_rows`` is
+        wanted (context nodes get -1).  ``positional``: float32 [molecule nt, 2] or None."""
+        batch = int(node_ptr.numel()) - 1
+        columns = 0 if positional is None else int(positional.shape[1])
+        molecules, nt = int(windows.mol_ptr.numel()) - 1, int(windows.bases.numel())
+        assert node_ptr.dtype == torch.int64 and edge_ptr.dtype == torch.int64
+        assert int(edge_ptr.numel()) == batch + 1
+        assert core_ptr is None or (core_ptr.dtype == torch.int64
+                                    and int(core_ptr.numel()) == batch + 1)
+        assert positional is None or (positional.dtype == torch.float32
+                                      and positional.is_contiguous()
+                                      and positional.shape[0] == nt)
+        with torch.cuda.device(self.device):
+            features = torch.empty((nodes, 4 + struct_states + columns),
+                                   dtype=torch.float32, device=self.device)
+            edge_index = torch.empty((2, edges), dtype=torch.int32, device=self.device)
+            edge_types = torch.empty(edges, dtype=torch.uint8, device=self.device)
+            residue_index = torch.empty(nodes, dtype=torch.int32, device=self.device)
+            node_roles = torch.empty(nodes, dtype=torch.uint8, device=self.device)
+            out_rows = (None if core_ptr is None
+                        else torch.empty(nodes, dtype=torch.int32, device=self.device))
+            first_invalid = torch.empty(1, dtype=torch.int32, device=self.device)
+            native.check(self._lib.gfy_window_emit(
+                _ptr(windows.bases), _ptr(windows.marks), _ptr(windows.mol_ptr), molecules, nt,
+                _ptr(windows.molecule), _ptr(windows.start), _ptr(windows.end),
+                int(windows.molecule.numel()), int(first_record), batch, _ptr(node_ptr),
+                _ptr(edge_ptr), _ptr(core_ptr), nodes, edges, core, struct_states, columns,
+                1 if windows.skip2 else 0, _ptr(positional), _ptr(features),
+                _ptr(edge_index) if edges else None, _ptr(edge_types) if edges else None,
+                _ptr(residue_index), _ptr(node_roles), _ptr(out_rows), _ptr(first_invalid),
+                _ptr(windows.workspace), windows.workspace.numel(), self._stream()),
+                "gfy_window_emit")
+        return (features, edge_index, edge_types, residue_index, node_roles, out_rows,
+                first_invalid)
 
     def encode(self, node_features: torch.Tensor, csr: DeviceCsr, *,
                out_rows: torch.Tensor | None = None,

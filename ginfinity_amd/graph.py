@@ -728,6 +728,76 @@ def shard_text(records: Sequence[RNA], spec: GraphSpec) -> ShardText:
     return ShardText(bases.copy(), marks.copy(), node_ptr, edge_ptr, spec)
 
 
+@dataclass(frozen=True)
+class WindowText:
+    """Windowed (and whole) records in the form the device window builder takes
+    (``gfy_window_select`` / ``gfy_window_emit``, include/gfy.h): the text of the DISTINCT
+    molecules — windows of one transcript share one copy — and, per record, its molecule and
+    its window [start, end); an unsliced record is the window [0, L)."""
+
+    bases: np.ndarray        # uint8 [molecule nt]
+    marks: np.ndarray        # uint8 [molecule nt]
+    mol_ptr: np.ndarray      # int64 [M+1]
+    molecule: np.ndarray     # int32 [R]
+    start: np.ndarray        # int32 [R]
+    end: np.ndarray          # int32 [R]
+    spec: GraphSpec
+
+    @property
+    def molecule_count(self) -> int:
+        return int(self.mol_ptr.shape[0]) - 1
+
+    @property
+    def record_count(self) -> int:
+        return int(self.molecule.shape[0])
+
+    @property
+    def core_counts(self) -> np.ndarray:
+        return (self.end - self.start).astype(np.int64)
+
+    def positional(self) -> np.ndarray | None:
+        """float32 [molecule nt, 2]: the sin / cos columns of the WHOLE molecules (a window
+        keeps its molecule's values, graph.py:608-695), or None."""
+        whole = ShardText(self.bases, self.marks, self.mol_ptr, self.mol_ptr, self.spec)
+        return whole.positional(0, self.molecule_count)
+
+
+def window_text(records: Sequence[RNA], spec: GraphSpec) -> WindowText:
+    """``WindowText`` of a list of records, sliced or not, in the order given.  Molecules are
+    told apart by sequence and structure, not by identifier: equal text is uploaded, and its
+    brackets are matched, once."""
+    count = len(records)
+    if count == 0:
+        raise GraphValidationError("a graph shard cannot be empty")
+    if len({record.identifier for record in records}) != count:
+        raise GraphValidationError("duplicate identifiers in graph shard")
+    index_of: dict[tuple[str, str], int] = {}
+    sequences: list[str] = []
+    structures: list[str] = []
+    molecule = np.empty(count, dtype=np.int32)
+    start = np.empty(count, dtype=np.int32)
+    end = np.empty(count, dtype=np.int32)
+    for slot, record in enumerate(records):
+        key = (record.sequence, record.structure)
+        found = index_of.get(key)
+        if found is None:
+            found = index_of[key] = len(sequences)
+            sequences.append(record.sequence)
+            structures.append(record.structure)
+        molecule[slot] = found
+        start[slot] = record.start if record.sliced else 0
+        end[slot] = record.end if record.sliced else record.length
+    lengths = np.fromiter(map(len, sequences), dtype=np.int64, count=len(sequences))
+    mol_ptr = np.zeros(len(sequences) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=mol_ptr[1:])
+    if int(mol_ptr[-1]) > _INT32_MAX:
+        raise GraphValidationError(
+            "graph shard exceeds the int32 node-index capacity; split it")
+    bases = np.frombuffer("".join(sequences).encode("ascii"), np.uint8)
+    marks = np.frombuffer("".join(structures).encode("ascii"), np.uint8)
+    return WindowText(bases.copy(), marks.copy(), mol_ptr, molecule, start, end, spec)
+
+
 def partition_records(records: Iterable[RNA], *, max_records: int,
                       max_nodes: int | None = None
                       ) -> Iterator[tuple[RNA, ...]]:
@@ -762,5 +832,5 @@ __all__ = [
     "NODE_ROLE_CORE", "Graph", "GraphBuilder", "GraphCompatibilityError",
     "GraphShard", "GraphSpec", "GraphValidationError", "ShardText",
     "graph_metadata_path", "load_graph_shard", "pair_table", "partition_records",
-    "save_graph_shard", "shard_text",
+    "save_graph_shard", "shard_text", "WindowText", "window_text",
 ]

@@ -108,6 +108,67 @@ int gfy_build_graphs(const uint8_t* bases, const uint8_t* marks,
                      int32_t* edge_index, uint8_t* edge_types,
                      int32_t* first_invalid, void* stream);
 
+/* ---- windowed (sliced) records -> graph arrays ---------------------------------------
+ * GraphBuilder._slice_graph on top of _build_full (src/ginfinity/graph.py:608-695) for every
+ * record of a list, WITHOUT building a window's whole molecule: the chosen positions of a
+ * record (the window, and with keep_paired_neighbours the partners of its paired bases plus
+ * context_hops - 1 further hops along the whole molecule's edges, stopping when a hop adds
+ * nothing) are a 4,096-bit map per record, and every array follows from the map.  The arrays
+ * are the reference's bit for bit: nodes ascending by position, the whole molecule's edges with
+ * both ends chosen, in the whole molecule's order, renumbered to the new node ranks.  An
+ * unsliced record is the window [0, L) and comes out as gfy_build_graphs writes it.
+ *   bases, marks   uint8 [molecule_nt]  text of the DISTINCT molecules, concatenated: windows
+ *                                       of one transcript share one copy and one pair table
+ *   mol_ptr        int64 [M+1]          molecule m owns mol_ptr[m]-mol_ptr[0] .. ; 1..4,096 nt
+ *   rec_mol, rec_start, rec_end  int32 [R]   record r is the window [start, end) of molecule
+ *                                       rec_mol[r], 0 <= start < end <= its length
+ * Two calls with ONE copy to the host between them, because node_ptr / edge_ptr (and so the
+ * micro-batches) depend on how much context every window drew in:
+ *   gfy_window_select   pair table of every molecule, then per record the chosen map into the
+ *                       workspace and  counts int32 [R][2] = (nodes, edges)  out
+ *   gfy_window_emit     records [first_record, first_record + batch_records) — one micro-batch —
+ *                       from the maps the select call left in the SAME workspace:
+ *     node_ptr, edge_ptr  int64 [batch_records+1]  prefix sums of the counts (any base: the
+ *                         kernels subtract the first entry), n_nodes / n_edges their totals
+ *     core_ptr       int64 [batch_records+1] prefix sums of end - start, n_core its total;
+ *                    read only when out_rows is given
+ *     struct_states, positional_columns, skip2   as for gfy_build_graphs
+ *     positional     float32 [molecule_nt][positional_columns] or NULL: the reference's host
+ *                    numpy sin/cos columns of the WHOLE molecules (a window keeps its
+ *                    molecule's values)
+ *     node_features  float32 [n_nodes][4 + struct_states + positional_columns]    out
+ *     edge_index     int32 [2][n_edges], edge_types uint8 [n_edges]                  out
+ *     residue_index  int32 [n_nodes] position in the molecule; node_roles uint8 [n_nodes]
+ *                    0 = core (inside the window), 1 = context                     out
+ *     out_rows       int32 [n_nodes] or NULL: row of the micro-batch's output for a core
+ *                    node, -1 for a context node — the out_rows argument of the encode calls
+ *   first_invalid  int32 [1] out of either call: -1, or the first record (index into the whole
+ *                  list) that names no molecule, whose window leaves its molecule, whose
+ *                  molecule is not 1..4,096 nt of balanced structure over the alphabet, or —
+ *                  emit — whose node_ptr / edge_ptr / core_ptr entries disagree with its map.
+ *                  Its counts are then 0 and its rows unspecified; every value read from the
+ *                  inputs is range-checked and nothing is written out of bounds.
+ *   workspace      gfy_window_workspace_bytes(); select writes it, emit reads it.  Returns
+ *                  GFY_ERR_WORKSPACE when it is too small, GFY_ERR_INVALID for bad arguments. */
+size_t gfy_window_workspace_bytes(int64_t n_molecules, int64_t molecule_nt, int64_t n_records);
+int gfy_window_select(const uint8_t* bases, const uint8_t* marks, const int64_t* mol_ptr,
+                      int64_t n_molecules, int64_t molecule_nt, const int32_t* rec_mol,
+                      const int32_t* rec_start, const int32_t* rec_end, int64_t n_records,
+                      int keep_paired_neighbours, int context_hops, int skip2,
+                      int32_t* counts, int32_t* first_invalid, void* workspace,
+                      size_t workspace_bytes, void* stream);
+int gfy_window_emit(const uint8_t* bases, const uint8_t* marks, const int64_t* mol_ptr,
+                    int64_t n_molecules, int64_t molecule_nt, const int32_t* rec_mol,
+                    const int32_t* rec_start, const int32_t* rec_end, int64_t n_records,
+                    int64_t first_record, int64_t batch_records, const int64_t* node_ptr,
+                    const int64_t* edge_ptr, const int64_t* core_ptr, int64_t n_nodes,
+                    int64_t n_edges, int64_t n_core, int struct_states,
+                    int positional_columns, int skip2, const float* positional,
+                    float* node_features, int32_t* edge_index, uint8_t* edge_types,
+                    int32_t* residue_index, uint8_t* node_roles, int32_t* out_rows,
+                    int32_t* first_invalid, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
 /* ---- COO -> CSR ------------------------------------------------------------
  * Destination-major CSR of a shard's edges, edges of one destination kept in
  * their COO order (a stable counting sort; integer work, bit-exact, run-to-run
