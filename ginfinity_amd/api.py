@@ -41,7 +41,8 @@ import numpy as np
 import torch
 
 from . import _native as native
-from .engine import DeviceEncoder, attach_records, device_output_dtype, records_pay
+from .engine import (DeviceEncoder, attach_records, device_output_dtype, records_closed,
+                     records_pay)
 from .host import HostEncoder
 from .graph import Graph, GraphBuilder, GraphShard, shard_text, window_text
 from .records import RNA
@@ -365,6 +366,24 @@ class _Uploader:
         self._next = (slot + 1) % len(self._staging)
         return slot
 
+    def _acquire(self, slot: int, total: int) -> torch.Tensor:
+        """The staging buffer of ``slot``, free to be written and at least ``total`` bytes long:
+        BOTH guards of the slot have been waited for — the event of its last torch copy or mapped
+        read (``send``, ``send_range``, ``hold``) and, once a ring exists, the native ring's event
+        of its last ``gfy_upload_async`` (``send_group``) — before a byte of it changes and before
+        it is replaced by a larger block (the old one returns to torch's host allocator, which
+        knows nothing of a native copy still reading it).  The one way to ``_staging[slot]`` for
+        everything that writes it."""
+        if self._copied[slot] is not None:
+            self._copied[slot].synchronize()
+        if self._ring:
+            native.check(native.library().gfy_upload_wait(self._ring, slot), "gfy_upload_wait")
+        staging = self._staging[slot]
+        if staging is None or staging.numel() < total:
+            staging = self._staging[slot] = torch.empty(
+                max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
+        return staging
+
     def pack(self, slot: int, arrays: Sequence):
         """``arrays``: numpy arrays, ``None``, or ``(array, scalar, lo, hi)`` = pack
         ``array - scalar`` after checking that every value lies in [lo, hi) (edge indices
@@ -377,13 +396,7 @@ class _Uploader:
             offsets.append(total)
             if array is not None:
                 total += -(-array.nbytes // 256) * 256
-        if self._copied[slot] is not None:
-            self._copied[slot].synchronize()          # the slot's last copy has left it
-        staging = self._staging[slot]
-        if staging is None or staging.numel() < total:
-            staging = self._staging[slot] = torch.empty(
-                max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
-        host = staging.numpy()
+        host = self._acquire(slot, total).numpy()     # the slot's last copy has left it
         for array, offset, rebase in zip(arrays, offsets, rebases):
             if array is not None and array.nbytes:
                 # ONE pass from the source (a view of the shard — for a loaded shard a view of
@@ -438,14 +451,7 @@ class _Uploader:
     def prepare_slot(self, slot: int, total: int) -> None:
         """Launching thread, before the group's packers are submitted: the slot's last copy has
         left it and its staging buffer holds ``total`` bytes."""
-        if self._copied[slot] is not None:
-            self._copied[slot].synchronize()
-        if self._ring:
-            native.check(native.library().gfy_upload_wait(self._ring, slot), "gfy_upload_wait")
-        staging = self._staging[slot]
-        if staging is None or staging.numel() < total:
-            self._staging[slot] = torch.empty(max(total, 1 << 20), dtype=torch.uint8,
-                                              pin_memory=True)
+        self._acquire(slot, total)
 
     def pack_at(self, slot: int, base: int, arrays: Sequence) -> list[int]:
         """``pack`` into a prepared slot at byte ``base`` (packer threads; the ranges of a
@@ -928,7 +934,9 @@ class Ginfinity:
         device_rows = self._device_rows(total_rows, torch_dtype)
 
         def prepare(slot: int, start: int, stop: int):
-            return self._pack_microbatch(uploader, slot, shard, start, stop)
+            # (mapped inputs never take the record-range set-up, see below: no boundaries, no check)
+            return self._pack_microbatch(uploader, slot, shard, start, stop,
+                                         with_records=not direct)
 
         assert MICROBATCH_GROUP <= uploader.slots
         jobs: list = []
@@ -985,14 +993,16 @@ class Ginfinity:
 
     @staticmethod
     def _pack_microbatch(uploader: "_Uploader", slot: int, shard: GraphShard, start: int,
-                         stop: int):
+                         stop: int, with_records: bool = True):
         """Records [start, stop) of ``shard`` → pinned staging slot ``slot`` (packer threads):
         the arrays of GraphShard.slice(start, stop) (graph.py:414-444: edge indices rebased to the
         first node of the range) without building — and re-validating — a GraphShard per
         micro-batch; the one check of GraphShard.__post_init__ that depends on the slice
         (graph.py:318-321 after the rebasing: an edge that leaves the micro-batch's node range,
         which the whole-shard range check cannot see) is made on the way into pinned memory and
-        refused exactly as the reference refuses it.  Returns ``(packed, kept core rows)``."""
+        refused exactly as the reference refuses it.  ``with_records``: the record boundaries go
+        along where they pay and no edge joins two records (``records_closed``: such an edge is
+        legal, and only the counting set-up honours it).  Returns ``(packed, kept core rows)``."""
         n0, n1 = int(shard.node_ptr[start]), int(shard.node_ptr[stop])
         e0, e1 = int(shard.edge_ptr[start]), int(shard.edge_ptr[stop])
         roles = shard.node_roles[n0:n1]
@@ -1005,7 +1015,10 @@ class Ginfinity:
         # the record boundaries go up as they are (the kernels subtract the first entry): two
         # arrays of records + 1 int64, and COO -> tile plans then needs no global atomics
         node_ptr = edge_ptr = None
-        if records_pay(shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1]):
+        if (with_records
+                and records_pay(shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1])
+                and records_closed(shard.edge_index[:, e0:e1], shard.node_ptr[start:stop + 1],
+                                   shard.edge_ptr[start:stop + 1])):
             node_ptr, edge_ptr = shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1]
         packed = uploader.pack(slot, (
             shard.node_features[n0:n1], (shard.edge_index[:, e0:e1], np.int32(n0), n0, n1),
@@ -1061,7 +1074,9 @@ class Ginfinity:
             rows = np.cumsum(core, dtype=np.int32) - np.int32(1)
             rows[~core] = -1
         node_ptr = edge_ptr = None
-        if records_pay(shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1]):
+        if (records_pay(shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1])
+                and records_closed(shard.edge_index[:, e0:e1], shard.node_ptr[start:stop + 1],
+                                   shard.edge_ptr[start:stop + 1])):
             node_ptr, edge_ptr = shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1]
         arrays = (shard.node_features[n0:n1], (shard.edge_index[:, e0:e1], np.int32(n0), n0, n1),
                   shard.edge_types[e0:e1], rows, node_ptr, edge_ptr)

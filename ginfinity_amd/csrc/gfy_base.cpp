@@ -49,10 +49,13 @@ static bool stream_stores() {   // read per call (once per ~4 MB): tests and A/B
 }
 
 // to[i] = from[i] - shift for `count` 32-bit values; returns the OR of (value | (limit - value))
-// over all of them: negative exactly when some value lies outside [0, limit]
+// over all of them: negative exactly when some value lies outside [0, limit].  `*inside` takes
+// the OR of ((value - low) | (high - value)): negative when a value inside [0, limit] lies
+// outside [low, high] — the node range of the record these edges belong to.
 static int32_t copy_rebased(int32_t* to, const int32_t* from, int64_t count, int32_t shift,
-                            int32_t limit, bool stream) {
-  int32_t seen = 0;
+                            int32_t limit, int32_t low, int32_t high, int32_t* inside,
+                            bool stream) {
+  int32_t seen = 0, kept = 0;
   int64_t i = 0;
 #if defined(__SSE2__)
   if (stream) {
@@ -60,9 +63,11 @@ static int32_t copy_rebased(int32_t* to, const int32_t* from, int64_t count, int
       const int32_t value = (int32_t)((uint32_t)from[i] - (uint32_t)shift);
       to[i] = value;
       seen |= value | (int32_t)((uint32_t)limit - (uint32_t)value);
+      kept |= (int32_t)((uint32_t)value - (uint32_t)low) | (int32_t)((uint32_t)high - (uint32_t)value);
     }
     const __m128i shifts = _mm_set1_epi32(shift), limits = _mm_set1_epi32(limit);
-    __m128i any = _mm_setzero_si128();
+    const __m128i lows = _mm_set1_epi32(low), highs = _mm_set1_epi32(high);
+    __m128i any = _mm_setzero_si128(), own = _mm_setzero_si128();
     for (; i + 16 <= count; i += 16) {
       __m128i v[4];
       for (int k = 0; k < 4; ++k)
@@ -70,19 +75,24 @@ static int32_t copy_rebased(int32_t* to, const int32_t* from, int64_t count, int
                              shifts);
       for (int k = 0; k < 4; ++k) {
         any = _mm_or_si128(any, _mm_or_si128(v[k], _mm_sub_epi32(limits, v[k])));
+        own = _mm_or_si128(own, _mm_or_si128(_mm_sub_epi32(v[k], lows), _mm_sub_epi32(highs, v[k])));
         _mm_stream_si128(reinterpret_cast<__m128i*>(to + i + 4 * k), v[k]);
       }
     }
     alignas(16) int32_t lanes[4];
     _mm_store_si128(reinterpret_cast<__m128i*>(lanes), any);
     seen |= lanes[0] | lanes[1] | lanes[2] | lanes[3];
+    _mm_store_si128(reinterpret_cast<__m128i*>(lanes), own);
+    kept |= lanes[0] | lanes[1] | lanes[2] | lanes[3];
   }
 #endif
   for (; i < count; ++i) {
     const int32_t value = (int32_t)((uint32_t)from[i] - (uint32_t)shift);
     to[i] = value;
     seen |= value | (int32_t)((uint32_t)limit - (uint32_t)value);
+    kept |= (int32_t)((uint32_t)value - (uint32_t)low) | (int32_t)((uint32_t)high - (uint32_t)value);
   }
+  *inside |= kept;
   return seen;
 }
 
@@ -144,18 +154,38 @@ int gfy_pack_microbatch(const float* node_features, int feature_dim, const int32
   offsets[0] = at;
   gfy::copy_bytes(out + at, node_features + n0 * feature_dim, (size_t)(n * feature_dim) * 4, stream);
   at += pad(n * feature_dim * 4);
-  // edge_index, rebased; an index outside [0, n) in either row is the caller's error
+  // record boundaries travel only where every record's edge list is short (engine.py,
+  // records_pay) ...
+  bool records = with_records != 0 && stop > start;
+  for (int64_t r = start; r < stop && records; ++r)
+    records = edge_ptr[r + 1] >= edge_ptr[r] && edge_ptr[r + 1] - edge_ptr[r] <= (int64_t)1 << 16;
+  // edge_index, rebased; an index outside [0, n) in either row is the caller's error.  Where
+  // boundaries would travel the copy goes record by record and also looks whether both ends of
+  // every edge lie in the record that owns it (by list position): the record-range set-up finds
+  // a row's in-edges only there (gfy.h, gfy_shard), the reference honours the edge wherever it
+  // points inside the micro-batch.
   offsets[1] = at;
-  int32_t seen = 0;
+  int32_t seen = 0, inside = 0;
   for (int row = 0; row < 2; ++row) {
     const int32_t* from = edge_index + (int64_t)row * edges_total + e0;
     int32_t* to = reinterpret_cast<int32_t*>(out + at) + (int64_t)row * e;
-    seen |= gfy::copy_rebased(to, from, e, (int32_t)n0, (int32_t)(n - 1), stream);
+    if (!records) {
+      seen |= gfy::copy_rebased(to, from, e, (int32_t)n0, (int32_t)(n - 1), 0, (int32_t)(n - 1),
+                                &inside, stream);
+      continue;
+    }
+    for (int64_t r = start; r < stop; ++r) {
+      const int64_t first = edge_ptr[r] - e0;
+      seen |= gfy::copy_rebased(to + first, from + first, edge_ptr[r + 1] - edge_ptr[r],
+                                (int32_t)n0, (int32_t)(n - 1), (int32_t)(node_ptr[r] - n0),
+                                (int32_t)(node_ptr[r + 1] - 1 - n0), &inside, stream);
+    }
   }
   if (e > 0 && seen < 0) {
     gfy::set_error("edge index outside shard node range");
     return GFY_ERR_INVALID;
   }
+  if (inside < 0) records = false;   // an edge joins two records: this micro-batch is counted
   at += pad(2 * e * 4);
   offsets[2] = at;
   if (e > 0) gfy::copy_bytes(out + at, edge_types + e0, (size_t)e, stream);
@@ -174,9 +204,6 @@ int gfy_pack_microbatch(const float* node_features, int feature_dim, const int32
     at += pad(n * 4);
   }
   // record boundaries, as they are (the set-up kernel reads them relative to their first entry)
-  bool records = with_records != 0 && stop > start;
-  for (int64_t r = start; r < stop && records; ++r)
-    records = edge_ptr[r + 1] - edge_ptr[r] <= (int64_t)1 << 16;
   offsets[4] = offsets[5] = -1;
   if (records) {
     const int64_t bytes = (stop - start + 1) * 8;

@@ -78,11 +78,42 @@ def records_pay(node_ptr: np.ndarray, edge_ptr: np.ndarray) -> bool:
     return int(np.diff(edge_ptr).max()) <= MAX_RECORD_EDGES
 
 
+def records_closed(edge_index: np.ndarray, node_ptr: np.ndarray, edge_ptr: np.ndarray) -> bool:
+    """Whether both ends of every edge lie in the node range of the record that owns the edge by
+    its position in the list: what the record-range set-up relies on (include/gfy.h, gfy_shard)
+    and no ``GraphShard`` check enforces — the reference honours an edge that joins two records
+    of a micro-batch (graph.py:318-321 looks at the shard's range only).  ``edge_index`` [2, E]
+    in the numbering of ``node_ptr`` (a slice of a shard with the shard's own entries, or
+    rebased with entries that start at zero); ``edge_ptr`` from any base.  The numpy twin of the
+    check inside ``gfy_pack_microbatch``."""
+    counts = np.diff(edge_ptr)
+    if int(counts.sum()) != edge_index.shape[1] or (counts < 0).any():
+        return False
+    # per edge: first node of its record and the record's node count (np.repeat, not reduceat —
+    # a record without edges contributes nothing instead of its neighbour's value)
+    if edge_index.dtype != np.int32:        # (not a GraphShard's array: no wrapping tricks)
+        first = np.repeat(np.asarray(node_ptr[:-1]), counts)
+        last = np.repeat(np.asarray(node_ptr[1:]), counts)
+        return bool(((edge_index >= first) & (edge_index < last)).all())
+    first = np.repeat(np.asarray(node_ptr[:-1]).astype(np.int32), counts)
+    sizes = np.repeat(np.diff(node_ptr).astype(np.uint32), counts)
+    # as unsigned, an index below its record's first node wraps above every size
+    return bool(((edge_index - first).view(np.uint32) < sizes).all())
+
+
 def attach_records(edge_index: torch.Tensor, node_ptr: torch.Tensor,
                    edge_ptr: torch.Tensor) -> torch.Tensor:
     """Record boundaries (device int64 tensors of records + 1 entries) ride on the micro-batch's
     edge_index tensor, so the (features, edge_index, edge_types, out_rows, out) tuples every
-    caller passes around stay what they are."""
+    caller passes around stay what they are.
+
+    Precondition (include/gfy.h, gfy_shard): no edge leaves its record.  The kernels do not
+    check it, and neither does this function — the CALLER does, on the host, before the arrays
+    go up: ``records_closed`` in ``upload_arrays`` and the numpy packers of ``api.py``, the same
+    test inside ``gfy_pack_microbatch``; a micro-batch that fails it travels without boundaries
+    and its group takes the counting set-up.  Graphs built on the device (``build_graphs``,
+    ``window_emit``: ``encode_many``'s text path and ``_encode_windows``) need no check: every
+    edge is emitted from ONE record's text with both ends inside that record's node range."""
     assert node_ptr.dtype == torch.int64 and edge_ptr.dtype == torch.int64
     assert node_ptr.numel() == edge_ptr.numel() >= 2
     edge_index.gfy_records = (node_ptr, edge_ptr)
@@ -127,6 +158,19 @@ class DeviceEncoder:
         # a call on another stream first waits for that call (event), see encode_coo
         self._coo_done: "torch.cuda.Event | None" = None
         self._coo_stream: int | None = None
+        #: batch calls of this encoder (``encode_coo_group``, ``encode_coo_group_pointers``, the
+        #: steps made by ``prepare_batch_step``, counted when made) in which EVERY shard carried record boundaries —
+        #: the record-range set-up (csrc/csr_records.inc) — and those in which one did not — the
+        #: counting set-up (include/gfy.h, gfy_shard; the fp32 model always counts, whatever it is
+        #: given).  Diagnostics: the tests read them.
+        self.ranged_batch_calls = 0
+        self.counting_batch_calls = 0
+
+    def _note_batch(self, array) -> None:
+        if all(slot.n_records > 0 and slot.node_ptr and slot.edge_ptr for slot in array):
+            self.ranged_batch_calls += 1
+        else:
+            self.counting_batch_calls += 1
 
     # -- lifetime ---------------------------------------------------------------
     def close(self) -> None:
@@ -456,6 +500,7 @@ class DeviceEncoder:
             status = encode(handle, array, count, out_code, flag, p_ws, ws_bytes, stream_handle)
             if status != 0:
                 native.check(status, "gfy_encode_coo_batch")
+        self._note_batch(array)      # (once, here: the step itself is the benchmark's hot loop)
         return step
 
     def encode_coo_batch(self, shards, *, out_dtype: torch.dtype = torch.float16,
@@ -496,6 +541,7 @@ class DeviceEncoder:
                 self._handle, array, count, out_code, 1 if normalise else 0, _ptr(scratch),
                 scratch.numel(), stream.cuda_stream), "gfy_encode_coo_batch")
             self._coo_enqueued(rows, stream)
+            self._note_batch(array)
 
     # -- the same from device ADDRESSES (no tensor per array: encode_shards_device) -------------
     @staticmethod
@@ -538,6 +584,7 @@ class DeviceEncoder:
                 self._handle, array, count, out_code, 1 if normalise else 0, _ptr(scratch),
                 scratch.numel(), stream.cuda_stream), "gfy_encode_coo_batch")
             self._coo_enqueued(rows, stream)
+            self._note_batch(array)
 
     def hidden(self, node_features: torch.Tensor, csr: DeviceCsr,
                stage: int) -> torch.Tensor:
@@ -637,7 +684,9 @@ class DeviceEncoder:
         ``node_ptr`` / ``edge_ptr``: the micro-batch's record boundaries (graph.py:268-271);
         where they pay (``records_pay``) they go up too and ride on the edge_index tensor
         (``attach_records``): the batch call then builds its tile plans without global atomics
-        (include/gfy.h, gfy_shard.node_ptr)."""
+        (include/gfy.h, gfy_shard.node_ptr).  Not when an edge joins two records
+        (``records_closed``): the micro-batch then goes up without boundaries and the edge is
+        honoured by the counting set-up, as the reference honours it."""
         nodes = int(node_features.shape[0])
         out_rows, kept = None, nodes
         if node_roles is not None:
@@ -648,7 +697,8 @@ class DeviceEncoder:
                 rows[~core] = -1
                 out_rows = torch.from_numpy(rows).to(self.device)
         x, ei, et = (self._upload(a) for a in (node_features, edge_index, edge_types))
-        if node_ptr is not None and edge_ptr is not None and records_pay(node_ptr, edge_ptr):
+        if (node_ptr is not None and edge_ptr is not None and records_pay(node_ptr, edge_ptr)
+                and records_closed(edge_index, node_ptr, edge_ptr)):
             attach_records(ei, self._upload(np.asarray(node_ptr, dtype=np.int64)),
                            self._upload(np.asarray(edge_ptr, dtype=np.int64)))
         return x, ei, et, out_rows, kept

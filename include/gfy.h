@@ -267,12 +267,22 @@ typedef struct gfy_shard {
   /* Optional (ABI 4): the shard's record boundaries as GraphShard keeps them (graph.py:268-271),
    * DEVICE arrays of n_records + 1 ascending int64 — record r owns the nodes
    * [node_ptr[r] - node_ptr[0], node_ptr[r + 1] - node_ptr[0]) and the edges
-   * [edge_ptr[r] - edge_ptr[0], ...) of this shard, and no edge leaves its record
-   * (graph.py:392-395).  When EVERY shard of a call has them, COO -> tile plans runs without
-   * global atomics (csrc/csr_records.inc: one launch instead of two; a workgroup scans only the
-   * edges of the records that overlap its rows).  NULL / 0: the counting kernel, as before.
-   * Results are identical either way.  Pass them only where a record's edge list is short
-   * against the shard (every workgroup of a record reads the record's whole edge list).      */
+   * [edge_ptr[r] - edge_ptr[0], ...) of this shard.  When EVERY shard of a call has them,
+   * COO -> tile plans runs without global atomics (csrc/csr_records.inc: one launch instead of
+   * two; a workgroup scans only the edges of the records that overlap its rows).  NULL / 0: the
+   * counting kernel, as before.
+   * PRECONDITION, the CALLER's to check: no edge leaves its record — both ends of every edge
+   * lie in the node range of the record whose edge range holds it (what GraphShard.from_graphs
+   * builds, graph.py:392-395; the kernel needs it of the destination).  The library does not
+   * look: an edge whose destination lies in another record is not found by that record's
+   * workgroups and is DROPPED without an error, unless both records happen to overlap one range
+   * of rows.  Such an edge is legal input (the reference validates edges against the shard's
+   * node range only, graph.py:318-321, and honours them): pass a shard that has one WITHOUT
+   * boundaries.  gfy_pack_microbatch makes this check while it copies the edges and leaves the
+   * boundaries out (counts[2] = 0); ginfinity_amd does the same wherever it attaches them
+   * (engine.py, records_closed).  With the precondition met, results are identical either way.
+   * Pass them only where a record's edge list is short against the shard (every workgroup of
+   * a record reads the record's whole edge list).                                            */
   const int64_t* node_ptr;
   const int64_t* edge_ptr;
   int64_t n_records;
@@ -376,9 +386,11 @@ int gfy_host_encode(const gfy_host_encoder* encoder, const float* node_features,
  *   slot + base      where the block starts (page-locked staging memory; base % 256 == 0)
  *   offsets[6]       out: byte offsets FROM `slot` of node_features, edge_index (2 x edges),
  *                    edge_types, out_rows (int32, -1 = dropped row; absent when every node is a
- *                    core node), node_ptr, edge_ptr (absent unless with_records and every
- *                    record has <= 65,536 edges); -1 = absent; every array starts at a multiple
- *                    of 256
+ *                    core node), node_ptr, edge_ptr (absent unless with_records, every
+ *                    record has <= 65,536 edges and both ends of every edge lie in the node
+ *                    range of the record whose edge range holds it: the precondition of
+ *                    gfy_shard.node_ptr, checked here - an edge that joins two records of the
+ *                    range is no error); -1 = absent; every array starts at a multiple of 256
  *   counts[4]        out: nodes, edges, records (0 = boundaries absent), kept rows
  * Returns GFY_ERR_INVALID (gfy_last_error: which) for an edge that leaves the records' node range
  * — the check of GraphShard.slice (graph.py:318-321).                                          */

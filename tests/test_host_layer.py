@@ -524,3 +524,204 @@ def test_native_packer_writes_the_bytes_of_the_numpy_packer(stream, monkeypatch)
                 api.Ginfinity._pack_microbatch_at(slots, 0, 0, broken, 1, 2)   # ... and record 1's below it
         finally:
             api.NATIVE_PACKER = True
+    # The same two edges are LEGAL in a range that holds both of their ends (the reference checks
+    # the slice's node range only, graph.py:318-321, and honours them): no error, the edges go
+    # up as they are, and the record boundaries stay behind (records = 0, offsets -1) — the
+    # record-range set-up would look for a row's in-edges in its own record only (gfy.h,
+    # gfy_shard).  Ranges of the same shard that hold neither edge keep their boundaries.  One
+    # crossing end at a time (destination / source), in the first, a middle and the last record,
+    # next to one-node records without edges, and in the streamed body as well as in the scalar
+    # head and tail of the native copy (list positions 0, 5, 33, last).
+    def crossed(shard, changes):
+        edges = shard.edge_index.copy()
+        for (row, position), value in changes.items():
+            edges[row, position] = value
+        object.__setattr__(shard, "edge_index", edges)
+        return shard
+
+    ep = synthetic.roofline_shard(1, records=3, length=100).edge_ptr
+    crossing = [
+        (crossed(synthetic.roofline_shard(1, records=3, length=100),
+                 {(0, 5): 250, (1, int(ep[1]) + 7): 3}),
+         {(0, 3): 0, (0, 2): -1, (1, 3): -1, (0, 1): -1, (1, 2): -1, (2, 3): 1}),
+        (crossed(synthetic.roofline_shard(2, records=3, length=100), {(1, 0): 299}),      # destination
+         {(0, 3): 0, (0, 2): -1, (1, 3): 2}),
+        (crossed(synthetic.roofline_shard(2, records=3, length=100), {(0, int(ep[3]) - 1): 0}),   # source
+         {(0, 3): 0, (1, 3): -1, (0, 2): 2, (1, 2): 1}),
+        (crossed(synthetic.roofline_shard(4, records=4, length=64), {(1, int(ep[0]) + 33): 200}),
+         {(0, 4): 0, (0, 3): -1, (1, 4): 3}),
+        # one-node records (arbitrary_shard cuts at random: 40 nodes in 12 records has some) and
+        # records without edges around the crossing one
+        (crossed(synthetic.arbitrary_shard(7, nodes=40, edges=90, records=12, hub_degree=3),
+                 {(1, 0): 39}), {(0, 12): 0}),
+    ]
+    lone = crossing[-1][0]
+    assert int(np.diff(lone.node_ptr).min()) == 1
+    for shard, ranges in crossing:
+        assert api._packable(shard)
+        for (start, stop), records in ranges.items():
+            got, want = [], []
+            for native_packer, slot, sink in ((True, 0, got), (False, 1, want)):
+                api.NATIVE_PACKER = native_packer
+                slots._staging[slot].zero_()
+                try:
+                    if records < 0:       # the edge leaves the RANGE: the error, unchanged
+                        with pytest.raises(GraphValidationError, match="edge index outside"):
+                            api.Ginfinity._pack_microbatch_at(slots, slot, 0, shard, start, stop)
+                        continue
+                    sink.append(api.Ginfinity._pack_microbatch_at(slots, slot, 256, shard, start, stop))
+                finally:
+                    api.NATIVE_PACKER = True
+            if records < 0:
+                continue
+            (offsets_a, *counts_a), (offsets_b, *counts_b) = got[0], want[0]
+            assert list(offsets_a) == list(offsets_b) and counts_a == counts_b, (start, stop)
+            assert counts_a[2] == records, (start, stop, counts_a)
+            assert (offsets_a[4] == offsets_a[5] == -1) == (records == 0)
+            assert slots._staging[0].numpy().tobytes() == slots._staging[1].numpy().tobytes()
+            # the edges themselves went up untouched but for the rebasing
+            e0, e1 = int(shard.edge_ptr[start]), int(shard.edge_ptr[stop])
+            packed = slots._staging[0].numpy()[offsets_a[1]:offsets_a[1] + 8 * (e1 - e0)]
+            np.testing.assert_array_equal(
+                packed.view(np.int32).reshape(2, e1 - e0),
+                shard.edge_index[:, e0:e1] - np.int32(shard.node_ptr[start]))
+
+
+def test_records_closed_is_the_per_record_range_check():
+    """``engine.records_closed`` (the numpy twin of the check in ``gfy_pack_microbatch``) against
+    the definition, edge by edge: both ends inside the node range of the record that owns the
+    edge by list position — with records that have no edges (``np.minimum.reduceat`` would
+    answer for them with their neighbour's edge), absolute and rebased numbering, a non-zero
+    edge_ptr base, and every single crossing end of a small shard."""
+    from ginfinity_amd import synthetic
+    from ginfinity_amd.engine import records_closed
+
+    def slow(edge_index, node_ptr, edge_ptr):
+        for r in range(len(node_ptr) - 1):
+            part = edge_index[:, edge_ptr[r] - edge_ptr[0]:edge_ptr[r + 1] - edge_ptr[0]]
+            if part.size and (part.min() < node_ptr[r] or part.max() >= node_ptr[r + 1]):
+                return False
+        return True
+
+    node_ptr = np.array([0, 1, 5, 6, 7, 12], dtype=np.int64)       # records 0, 2, 3: one node
+    edge_ptr = np.array([0, 0, 4, 4, 4, 9], dtype=np.int64)        # ... and no edge
+    edges = np.array([[1, 2, 3, 4, 7, 8, 9, 10, 11], [4, 3, 2, 1, 11, 10, 9, 8, 7]], dtype=np.int32)
+    assert records_closed(edges, node_ptr, edge_ptr) and slow(edges, node_ptr, edge_ptr)
+    assert records_closed(edges + np.int32(100), node_ptr + 100, edge_ptr + 7)
+    assert records_closed(edges[:, :0], node_ptr[:1 + 1], edge_ptr[:1 + 1])
+    assert not records_closed(edges, node_ptr, edge_ptr[:-1])
+    for row in range(2):
+        for position in range(edges.shape[1]):
+            for value in range(12):
+                changed = edges.copy()
+                changed[row, position] = value
+                assert records_closed(changed, node_ptr, edge_ptr) == slow(changed, node_ptr, edge_ptr), \
+                    (row, position, value)
+    assert not records_closed(edges.astype(np.int64) + 1, node_ptr, edge_ptr)    # (another dtype)
+    assert records_closed(edges.astype(np.int64), node_ptr, edge_ptr)
+    shard = synthetic.arbitrary_shard(2, nodes=5000, edges=20000, records=6)
+    assert records_closed(shard.edge_index, shard.node_ptr, shard.edge_ptr)
+    n0, e0, e1 = int(shard.node_ptr[2]), int(shard.edge_ptr[2]), int(shard.edge_ptr[5])
+    assert records_closed(shard.edge_index[:, e0:e1], shard.node_ptr[2:6], shard.edge_ptr[2:6])
+    assert records_closed(shard.edge_index[:, e0:e1] - np.int32(n0), shard.node_ptr[2:6] - n0,
+                          shard.edge_ptr[2:6] - e0)
+    moved = shard.edge_index.copy()
+    moved[1, e0] = n0 - 1
+    assert not records_closed(moved[:, e0:e1], shard.node_ptr[2:6], shard.edge_ptr[2:6])
+
+
+def test_a_staging_slot_is_acquired_before_it_is_written_or_replaced(monkeypatch):
+    """A staging slot has TWO guards: the torch event of its last copy or mapped read
+    (``_copied[slot]``: ``send``, ``send_range``, ``hold``) and the native ring's event of its last
+    ``gfy_upload_async`` (``send_group``, which sets no ``_copied``).  Everything that writes
+    ``_staging[slot]`` or replaces it by a larger block — ``pack`` (and ``__call__`` through it),
+    ``prepare_slot`` — must have waited for BOTH before the first byte changes and before the old
+    block goes back to torch's host allocator: ``encode_graphs`` / ``encode_many`` /
+    ``build_graphs_device`` share the uploader with ``encode_shards_device``, whose uploads may
+    still be reading the slot.  No timing, no device: the waits are fakes that note the identity
+    and a checksum of the slot's buffer at the moment they are called, and the allocation of the
+    larger block is a fake that notes when it happens."""
+    import torch
+    import zlib
+    from ginfinity_amd import api
+
+    log = []
+
+    def state(uploader, slot):
+        buffer = uploader._staging[slot]
+        return id(buffer), zlib.crc32(buffer.numpy().tobytes())
+
+    class Event:
+        def __init__(self, uploader, slot):
+            self.uploader, self.slot = uploader, slot
+
+        def synchronize(self):
+            log.append(("event", self.slot, *state(self.uploader, self.slot)))
+
+    class Library:                       # the one native call a slot's acquisition may make
+        def __init__(self, uploader):
+            self.uploader = uploader
+
+        def gfy_upload_wait(self, ring, slot):
+            assert ring == 0x5151
+            log.append(("ring", slot, *state(self.uploader, slot)))
+            return 0
+
+        def gfy_upload_ring_destroy(self, ring):
+            pass
+
+        def __getattr__(self, name):
+            raise AssertionError(f"unexpected native call {name}")
+
+    class Slots(api._Uploader):
+        def __init__(self, ring):
+            self._device, self.slots, self._next, self._ring = None, 3, 0, ring
+            self._staging = [torch.full((4096,), 0xAB, dtype=torch.uint8) for _ in range(3)]
+            self._copied = [Event(self, slot) for slot in range(3)]
+
+    real_empty = torch.empty
+
+    def empty(*size, pin_memory=False, **options):     # page-locked memory needs a device
+        if pin_memory:
+            log.append(("grow", int(size[0])))
+        return real_empty(*size, **options)
+
+    monkeypatch.setattr(torch, "empty", empty)
+    small = [np.arange(300, dtype=np.int32), None, np.ones(7, dtype=np.uint8)]
+    large = [np.arange(3000, dtype=np.float32)]                       # 12,000 bytes > 4,096
+    writers = {
+        "pack": lambda up, slot, arrays: up.pack(slot, arrays),
+        "prepare_slot": lambda up, slot, arrays: up.prepare_slot(
+            slot, sum(up.padded(a.nbytes) for a in arrays if a is not None)),
+    }
+    for ring in (0x5151, None):
+        for name, write in writers.items():
+            for slot, arrays in ((1, small), (2, large)):
+                uploader = Slots(ring)
+                library = Library(uploader)
+                monkeypatch.setattr(api.native, "library", lambda library=library: library)
+                try:
+                    del log[:]
+                    before = state(uploader, slot)
+                    write(uploader, slot, arrays)
+                    waits = [entry for entry in log if entry[0] in ("event", "ring")]
+                    # both guards, this slot's, each with the buffer still there and untouched
+                    assert [entry[0] for entry in waits] == (["event", "ring"] if ring else ["event"]), \
+                        (name, ring, log)
+                    for kind, waited, identity, checksum in waits:
+                        assert waited == slot and (identity, checksum) == before, (name, kind, log)
+                    grown = [entry for entry in log if entry[0] == "grow"]
+                    if arrays is large:          # ... and replaced only behind them
+                        assert len(grown) == 1 and log.index(grown[0]) > max(map(log.index, waits))
+                        assert id(uploader._staging[slot]) != before[0]
+                        assert uploader._staging[slot].numel() >= 12_000
+                    else:
+                        assert not grown and id(uploader._staging[slot]) == before[0]
+                    if name == "pack":           # the write did happen, behind the waits
+                        got = uploader._staging[slot].numpy()[:arrays[0].nbytes]
+                        assert got.tobytes() == arrays[0].tobytes()
+                    # the other slots were neither waited for nor touched
+                    for other in set(range(3)) - {slot}:
+                        assert uploader._staging[other].numpy().tobytes() == b"\xab" * 4096
+                finally:
+                    uploader._ring = None        # (nothing for __del__ to hand to the real library)
