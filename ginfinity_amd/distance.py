@@ -89,7 +89,8 @@ def nearest(a, b=None, *, metric: str = "l2", exclude_self: bool = False,
     ``a``) skips the pair (i, i); ``exclude_offset=k`` skips (i, i+k) — ``a`` is a
     row block of ``b`` starting at row k; ``window_first=k`` is the opposite case:
     ``b`` is rows [k, k + m) of ``a`` and every row skips itself (the cross-shard
-    search of a rank's own piece, one call).  With ``workspace`` the returned
+    search of a rank's own piece, one call).  A row with every candidate excluded
+    gets index -1 and value ``+inf`` (l2) / ``-inf`` (cosine).  With ``workspace`` the returned
     tensors are views of its buffers, valid until its next use."""
     a = _prepare(a, None)
     b = a if b is None else _prepare(b, a.device)

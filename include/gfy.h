@@ -438,7 +438,10 @@ int gfy_pairwise_dense(const void* a, int64_t n, const void* b, int64_t m,
  *   best_val float32 [n], best_idx int32 [n]: nearest b-row of each a-row
  *   (smallest distance for GFY_L2, largest similarity for GFY_COSINE; ties ->
  *   lowest index).  exclude_offset >= 0 skips the pair (i, i + exclude_offset)
- *   — "self" when b is a with a row offset; -1 excludes nothing.               */
+ *   — "self" when b is a with a row offset; -1 excludes nothing.
+ *   An a-row whose every candidate is excluded (m = 1 and that row skipped; in
+ *   gfy_pairwise_nearest_window a row whose only candidate is itself) gets
+ *   best_idx = -1 and best_val = +inf (GFY_L2) / -inf (GFY_COSINE).            */
 int gfy_pairwise_nearest(const void* a, int64_t n, const void* b, int64_t m,
                          int metric, int64_t exclude_offset, float* best_val,
                          int32_t* best_idx, void* workspace,

@@ -149,9 +149,12 @@ def test_nearest_at_workgroup_and_tile_seams(n, m):
 
 
 def test_nearest_duplicates_across_tiles_and_sweep_chunks():
-    """Ties go to the lowest index also when the equal rows sit in different b-tiles, in
-    different ring buffers and — few a-rows, many b-rows — in different sweep chunks whose
-    partial results are merged by k_nearest_finish."""
+    """Ties go to the lowest index also when the equal rows sit in different b-tiles and —
+    few a-rows, many b-rows — in different sweep chunks whose partial results are merged by
+    k_nearest_finish.  With 90 a-rows every workgroup sweeps ONE tile (one chunk per b-tile),
+    so the copies are 2,290 and 3,480 rows apart in different chunks, never in two buffers of
+    one workgroup's ring: ties inside a sweep of several tiles are
+    tests/test_gpu_distance_sweeps.py's."""
     from ginfinity_amd import distance
     base = _rows(11, 90)
     filler = _rows(12, 4000) * np.float16(0.5)           # never closer than an exact copy
