@@ -1019,4 +1019,40 @@ int gfy_pairwise_nearest_window(const void* a, int64_t n, const void* b, int64_t
                                  ws_bytes, (hipStream_t)stream);
 }
 
+size_t gfy_pairwise_topk_workspace_bytes(int64_t n, int64_t m, int k) {
+  k = k < 1 ? 1 : k > GFY_PAIRWISE_TOPK_MAX ? GFY_PAIRWISE_TOPK_MAX : k;
+  return pairwise_topk_workspace_bytes(n < 1 ? 1 : n, m < 1 ? 1 : m, k);
+}
+
+int gfy_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
+                      int64_t exclude_offset, float* top_val, int32_t* top_idx, void* ws,
+                      size_t ws_bytes, void* stream) {
+  clear_error();
+  GFY_REQUIRE(a && b && top_val && top_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
+              GFY_ERR_INVALID, "gfy_pairwise_topk: bad arguments");
+  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
+              "gfy_pairwise_topk: unknown metric %d", metric);
+  GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_MAX, GFY_ERR_INVALID,
+              "gfy_pairwise_topk: k = %d outside 1..%d", k, GFY_PAIRWISE_TOPK_MAX);
+  return launch_pairwise_topk(a, n, b, m, metric, k, exclude_offset, exclude_offset >= 0 ? 1 : 0,
+                              top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_pairwise_topk_window(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                             int k, int64_t window_first, float* top_val, int32_t* top_idx,
+                             void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  GFY_REQUIRE(a && b && top_val && top_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
+              GFY_ERR_INVALID, "gfy_pairwise_topk_window: bad arguments");
+  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
+              "gfy_pairwise_topk_window: unknown metric %d", metric);
+  GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_MAX, GFY_ERR_INVALID,
+              "gfy_pairwise_topk_window: k = %d outside 1..%d", k, GFY_PAIRWISE_TOPK_MAX);
+  GFY_REQUIRE(window_first >= 0 && window_first + m <= n, GFY_ERR_INVALID,
+              "gfy_pairwise_topk_window: b must be rows [%lld, %lld) of the %lld rows of a",
+              (long long)window_first, (long long)(window_first + m), (long long)n);
+  return launch_pairwise_topk(a, n, b, m, metric, k, -window_first, 1, top_val, top_idx, ws,
+                              ws_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

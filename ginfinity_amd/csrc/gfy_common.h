@@ -353,6 +353,16 @@ int launch_pairwise_nearest(const void* a, int64_t n, const void* b, int64_t m,
                             int32_t* best_idx, void* ws, size_t ws_bytes,
                             hipStream_t s);
 size_t pairwise_workspace_bytes(int64_t n, int64_t m);
+// per-row terms of the keys (k_row_terms, pairwise.hip): (s, t) of `count` b-rows padded to
+// `padded`, or the a-side term; the arrays not wanted are nullptr
+int launch_pairwise_row_terms(const void* rows, int64_t count, int64_t padded, int metric,
+                              int fold, float* s_out, float* t_out, float* a_term,
+                              hipStream_t s);
+// pairwise_topk.hip
+int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
+                         int64_t exclude_offset, int exclude_on, float* top_val,
+                         int32_t* top_idx, void* ws, size_t ws_bytes, hipStream_t s);
+size_t pairwise_topk_workspace_bytes(int64_t n, int64_t m, int k);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS

@@ -40,6 +40,9 @@ constexpr int kBuffers = 4;   // b-tile ring: tile i is consumed while i+1 .. i+
 #define GFY_PAIRWISE_TILES_PER_BARRIER 2   // nearest: 2 = a barrier per pair of tiles, 1 = per tile
 #endif
 
+// pairwise_topk.hip carries its own copies of uniform_pointer, off256, the ring constants and the
+// `request` lambda (so that this file's machine code does not move with it): a fix to the DMA
+// addressing or the swizzle goes into both files.
 template <class T>
 __device__ __forceinline__ const T* uniform_pointer(const T* pointer) {
   const uint64_t bits = (uint64_t)(uintptr_t)pointer;
@@ -570,6 +573,16 @@ constexpr int kPairLds = kBuffers * kRowBytes + kTermSlots * kTermBytes;   // ro
 }  // namespace
 
 size_t pairwise_workspace_bytes(int64_t n, int64_t m) { return carve(nullptr, n, m).bytes; }
+
+// k_row_terms for the top-k sweep (pairwise_topk.hip): one kernel, so its keys are these keys
+int launch_pairwise_row_terms(const void* rows, int64_t count, int64_t padded, int metric,
+                              int fold, float* s_out, float* t_out, float* a_term,
+                              hipStream_t s) {
+  k_row_terms<<<(int)((padded * 16 + 255) / 256), 256, 0, s>>>((const f16*)rows, count, padded,
+                                                               metric, fold, s_out, t_out, a_term);
+  GFY_CHECK_HIP(hipGetLastError());
+  return GFY_OK;
+}
 
 // > 64 KB of dynamic LDS: opt in once per device, thread-safe (gfy_common.h)
 static PerDeviceOnce g_pairwise_lds_opt_in;

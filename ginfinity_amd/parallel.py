@@ -7,7 +7,8 @@ MI355X node the same decomposition maps to ranks:
 * **encode is shard-parallel and needs no collective** — graphs never share
   edges across records (graph.py:392-395), weights (0.6 MB) are replicated,
   rank r encodes shards r, r+W, r+2W, …;
-* **the one exchange step** is the cross-shard nearest-neighbour search: the fp16
+* **the one exchange step** is the cross-shard nearest-neighbour search (one neighbour:
+  ``cross_shard_nearest``, the k nearest: ``cross_shard_topk``): the fp16
   embedding blocks are all-gathered in chunks (``all_gather_into_tensor`` per chunk into
   one of two staging buffers — RCCL over xGMI on GPUs, gloo on CPU tensors in the tests)
   and every chunk is searched against the rank's own rows while the next one is in
@@ -187,5 +188,113 @@ def cross_shard_nearest(block: torch.Tensor, *, metric: str = "l2", group=None,
     return best_value, best_index, offsets
 
 
+_NO_ROW = torch.iinfo(torch.int64).max   # an empty slot while lists are merged: behind every row
+
+
+def _merge_topk(best_value, best_index, values, indices, k: int, metric: str):
+    """The k best of two [rows][k] lists by (value, global row): smallest value first for l2,
+    largest for cosine, ties to the lowest global row; empty slots (row _NO_ROW) go last.
+    Two stable sorts: by row, then by value."""
+    value = torch.cat([best_value, values], dim=1)
+    index = torch.cat([best_index, indices], dim=1)
+    by_row = torch.argsort(index, dim=1, stable=True)
+    value, index = value.gather(1, by_row), index.gather(1, by_row)
+    by_value = torch.argsort(value if metric == "l2" else -value, dim=1, stable=True)[:, :k]
+    return value.gather(1, by_value), index.gather(1, by_value)
+
+
+def cross_shard_topk(block: torch.Tensor, k: int, *, metric: str = "l2", group=None,
+                     chunk_rows: int = 1 << 20, search=None
+                     ) -> tuple[torch.Tensor, torch.Tensor, list[int]]:
+    """The ``k`` nearest other embeddings, over ALL ranks' rows, of every local row.
+
+    The exchange is that of ``cross_shard_nearest``: chunks of ``chunk_rows`` rows per rank,
+    one equal-count ``all_gather_into_tensor`` per chunk into one of two staging buffers, chunk
+    c searched while chunk c+1 is in flight.  Per piece one ``distance.topk`` call (the rank's
+    own piece with ``window_first``), whose ``[rows][k]`` lists are merged into the running
+    ones on the device by (value, global row), keeping ``k``; ties go to the lowest global
+    row.  A row with fewer than ``k`` other rows in the whole world fills its trailing columns
+    with row -1 and value ``+inf`` (l2) / ``-inf`` (cosine).  A rank without rows takes part
+    in the collectives and returns empty results.
+
+    The merged order is that of the VALUES, not of the kernel's keys.  ``distance.topk`` orders
+    a row by (fp32 key, row), and two pairs with different keys can round to the same fp32 value
+    (the l2 value is ``sqrt(max(|a|² + key, 0))``; keys within about 3e-7 of each other for unit
+    rows).  Two such neighbours stand here in row order, in a plain ``distance.topk`` call over
+    the same rows in key order: the same rows and the same values, two adjacent columns
+    exchanged — for random unit rows about one row in 10^4 at k = 8.  So this function equals
+    ``distance.topk`` bit for bit only on data without such a pair; what it guarantees on any
+    data is the order (value, global row) stated above.
+
+    Returns (values float32 [rows_r][k], global rows int64 [rows_r][k], rank offsets W+1).
+    ``search`` (tests) replaces ``distance.topk``."""
+    from . import distance
+    workspace = None
+    if search is None:
+        search = distance.topk
+        workspace = distance.TopKWorkspace()     # one set of buffers for every piece
+    if metric not in ("l2", "cosine"):
+        raise ValueError("metric must be 'l2' or 'cosine'")
+    k = distance.checked_k(k)                    # the check of distance.topk
+    rank, size = world(group)
+    rows = int(block.shape[0])
+    device = block.device
+    if size > 1:
+        mine = torch.tensor([rows], dtype=torch.int64, device=device)
+        everyone = torch.empty(size, dtype=torch.int64, device=device)
+        dist.all_gather_into_tensor(everyone, mine, group=group)
+        sizes = [int(v) for v in everyone.tolist()]
+    else:
+        sizes = [rows]
+    offsets = [0]
+    for value in sizes:
+        offsets.append(offsets[-1] + value)
+    widest = max(sizes)
+    chunk_rows = max(1, min(int(chunk_rows), max(widest, 1)))
+    chunks = (widest + chunk_rows - 1) // chunk_rows
+    worse = float("inf") if metric == "l2" else float("-inf")
+    best_value = torch.full((rows, k), worse, dtype=torch.float32, device=device)
+    best_index = torch.full((rows, k), _NO_ROW, dtype=torch.int64, device=device)
+    if size > 1:
+        staging = [torch.empty((size, chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
+                   for _ in range(min(2, max(chunks, 1)))]
+        outgoing = [torch.zeros((chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
+                    for _ in range(len(staging))]
+
+    def start(chunk: int):
+        first = chunk * chunk_rows
+        have = max(0, min(rows - first, chunk_rows))
+        buffer = outgoing[chunk % len(outgoing)]
+        if have:
+            buffer[:have] = block[first:first + have]
+        return dist.all_gather_into_tensor(
+            staging[chunk % len(staging)].view(size * chunk_rows, block.shape[1]), buffer,
+            group=group, async_op=True)
+
+    pending = start(0) if size > 1 and chunks else None
+    for chunk in range(chunks):
+        first = chunk * chunk_rows
+        if size > 1:
+            arriving = pending
+            pending = start(chunk + 1) if chunk + 1 < chunks else None   # in flight under the search
+            arriving.wait()
+        for other in range(size):
+            valid = max(0, min(sizes[other] - first, chunk_rows))
+            if valid == 0 or rows == 0:
+                continue
+            piece = (staging[chunk % len(staging)][other, :valid] if size > 1
+                     else block[first:first + valid])
+            extra = {} if workspace is None else {"workspace": workspace}
+            if other == rank:
+                extra["window_first"] = first
+            values, indices = search(block, piece, k=k, metric=metric, **extra)
+            indices = indices.to(torch.int64)
+            indices = torch.where(indices < 0, _NO_ROW, indices + (offsets[other] + first))
+            best_value, best_index = _merge_topk(best_value, best_index, values, indices, k,
+                                                 metric)
+    best_index = torch.where(best_index == _NO_ROW, -1, best_index)
+    return best_value, best_index, offsets
+
+
 __all__ = ["world", "shard_assignment", "encode_owned_shards",
-           "all_gather_rows", "cross_shard_nearest"]
+           "all_gather_rows", "cross_shard_nearest", "cross_shard_topk"]

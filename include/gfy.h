@@ -455,6 +455,29 @@ int gfy_pairwise_nearest_window(const void* a, int64_t n, const void* b, int64_t
                                 int32_t* best_idx, void* workspace, size_t workspace_bytes,
                                 void* stream);
 
+/* Exact top-k, the N x M matrix is never materialised.  For every a-row the k best b-rows,
+ * smallest distance first (GFY_L2) / largest similarity first (GFY_COSINE):
+ *   top_val float32 [n][k], top_idx int32 [n][k], row-major.
+ *   Order: by (the kernel's fp32 key of the pair, b-row index) — among equal keys the lowest
+ *   index comes first; no index appears twice in a row.  The key is the one
+ *   gfy_pairwise_nearest minimises, computed the same way, so column 0 is its answer bit for
+ *   bit, the first j columns of a call with k >= j are the call with k = j bit for bit, and a
+ *   row's result does not depend on which other rows the call holds.
+ *   1 <= k <= GFY_PAIRWISE_TOPK_MAX; anything else is GFY_ERR_INVALID before any launch.
+ *   exclude_offset as in gfy_pairwise_nearest, window_first as in gfy_pairwise_nearest_window:
+ *   an excluded pair appears in no column.
+ *   A row with fewer than k candidates (m < k, or one fewer after an exclusion) fills its
+ *   trailing columns with top_idx = -1 and top_val = +inf (GFY_L2) / -inf (GFY_COSINE).
+ *   The workspace has its own size, which grows with k.                                   */
+#define GFY_PAIRWISE_TOPK_MAX 16
+size_t gfy_pairwise_topk_workspace_bytes(int64_t n, int64_t m, int k);
+int gfy_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
+                      int64_t exclude_offset, float* top_val, int32_t* top_idx,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int gfy_pairwise_topk_window(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                             int k, int64_t window_first, float* top_val, int32_t* top_idx,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,12 +1,16 @@
 #!/bin/bash
-# Registers / spills of the pairwise kernels as hipcc allocates them (no GPU needed); the
-# assembly is left in /tmp/pairwise.s
+# Registers / spills of the pairwise kernels as hipcc allocates them (no GPU needed):
+#   bash tools/pairwise_resources.sh [extra hipcc flags]
+#   GFY_SOURCE=pairwise_topk.hip bash tools/pairwise_resources.sh     # the top-k kernels
+# The assembly is left in $GFY_ASM_OUT (default /tmp/<source stem>.s, i.e. /tmp/pairwise.s).
 set -e
 cd "$(dirname "$0")/../ginfinity_amd/csrc"
+SOURCE="${GFY_SOURCE:-pairwise.hip}"
+STEM="${SOURCE%.hip}"
 OUT=$(mktemp -d)
 /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math \
-  -Wall -Wno-unused-function "$@" --save-temps=obj -c pairwise.hip -o "$OUT/p.o"
-python3 - "$OUT/pairwise-hip-amdgcn-amd-amdhsa-gfx950.s" <<'PY'
+  -Wall -Wno-unused-function "$@" --save-temps=obj -c "$SOURCE" -o "$OUT/p.o"
+python3 - "$OUT/$STEM-hip-amdgcn-amd-amdhsa-gfx950.s" <<'PY'
 import re, sys
 text = open(sys.argv[1]).read()
 meta = text[text.index('amdhsa.kernels:'):]
@@ -16,5 +20,5 @@ for block in meta.split('  - .agpr_count:')[1:]:
     print(f"{name[:60]:60s} agpr {block.split()[0]:>3s} vgpr {field('vgpr_count'):>3s} "
           f"spilled {field('vgpr_spill_count'):>3s} scratch {field('private_segment_fixed_size')} B")
 PY
-cp "$OUT/pairwise-hip-amdgcn-amd-amdhsa-gfx950.s" /tmp/pairwise.s
+cp "$OUT/$STEM-hip-amdgcn-amd-amdhsa-gfx950.s" "${GFY_ASM_OUT:-/tmp/$STEM.s}"
 rm -rf "$OUT"
