@@ -28,10 +28,13 @@ from __future__ import annotations
 
 from concurrent.futures import ThreadPoolExecutor
 import collections
+import contextlib
 import ctypes
+import functools
 import os
 import queue
 import threading
+import weakref
 
 import json
 from pathlib import Path
@@ -106,7 +109,6 @@ def _advise_huge_pages(block: np.ndarray) -> None:
     faults, 11 ms on one thread, for the 230 MB of config 2.  Best effort: not Linux, THP off
     or a small block → nothing happens."""
     try:
-        import ctypes
         libc = ctypes.CDLL(None, use_errno=True)
         huge = 2 << 20
         begin = block.ctypes.data
@@ -188,7 +190,6 @@ _pinned_lock = threading.Lock()         # (finalizers run on whatever thread dro
 def _pinned_block(shape, dtype: torch.dtype) -> torch.Tensor:
     """A page-locked host tensor whose bytes count against PINNED_RESULT_LIMIT while it lives
     (the numpy views handed to the caller keep it alive)."""
-    import weakref
     block = torch.empty(shape, dtype=dtype, pin_memory=True)
     size = block.numel() * block.element_size()
     with _pinned_lock:
@@ -384,36 +385,44 @@ class _Uploader:
                 max(total, 1 << 20), dtype=torch.uint8, pin_memory=True)
         return staging
 
+    @staticmethod
+    def _write(host: np.ndarray, at: int, item) -> int:
+        """One entry of ``pack`` / ``pack_at`` → ``host[at:]``; returns its bytes.  ONE pass
+        from the source (a view of the shard — for a loaded shard a view of the file mapping)
+        into pinned memory, rebasing on the way where asked."""
+        array, rebase = (item[0], item[1:]) if isinstance(item, tuple) else (item, None)
+        if array.nbytes:
+            target = host[at:at + array.nbytes].view(array.dtype).reshape(array.shape)
+            if rebase is None:
+                np.copyto(target, array)
+            else:
+                base, low, high = rebase
+                if base:
+                    np.subtract(array, base, out=target)
+                else:                      # a shard's first micro-batch: nothing to rebase
+                    np.copyto(target, array)
+                # one pass: as unsigned, a value below `low` wraps to ≥ 2^31 > high - low
+                if target.size and int(target.view(np.uint32).max()) >= high - low:
+                    raise GraphValidationError("edge index outside shard node range")
+        return array.nbytes
+
     def pack(self, slot: int, arrays: Sequence):
         """``arrays``: numpy arrays, ``None``, or ``(array, scalar, lo, hi)`` = pack
         ``array - scalar`` after checking that every value lies in [lo, hi) (edge indices
         rebased to the micro-batch's first node, graph.py:414-444, with the range check of
-        graph.py:318-321 on the slice).  Thread-safe per slot."""
-        rebases = [item[1:] if isinstance(item, tuple) else None for item in arrays]
-        arrays = [item[0] if isinstance(item, tuple) else item for item in arrays]
+        graph.py:318-321 on the slice).  Every array starts on a multiple of 256 bytes; ``None``
+        takes none.  Thread-safe per slot."""
+        plain = [item[0] if isinstance(item, tuple) else item for item in arrays]
         offsets, total = [], 0
-        for array in arrays:
+        for array in plain:
             offsets.append(total)
             if array is not None:
-                total += -(-array.nbytes // 256) * 256
+                total += self.padded(array.nbytes)
         host = self._acquire(slot, total).numpy()     # the slot's last copy has left it
-        for array, offset, rebase in zip(arrays, offsets, rebases):
-            if array is not None and array.nbytes:
-                # ONE pass from the source (a view of the shard — for a loaded shard a view of
-                # the file mapping) into pinned memory, rebasing on the way where asked
-                target = host[offset:offset + array.nbytes].view(array.dtype).reshape(array.shape)
-                if rebase is None:
-                    np.copyto(target, array)
-                else:
-                    base, low, high = rebase
-                    if base:
-                        np.subtract(array, base, out=target)
-                    else:                      # a shard's first micro-batch: nothing to rebase
-                        np.copyto(target, array)
-                    # one pass: as unsigned, a value below `low` wraps to ≥ 2^31 > high - low
-                    if target.size and int(target.view(np.uint32).max()) >= high - low:
-                        raise GraphValidationError("edge index outside shard node range")
-        return slot, arrays, offsets, total
+        for item, offset in zip(arrays, offsets):
+            if item is not None:
+                self._write(host, offset, item)
+        return slot, plain, offsets, total
 
     def send(self, packed, *, mapped: bool = False) -> list[torch.Tensor | None]:
         """The packed slot → device tensors (views of one allocation), on the current stream.
@@ -455,28 +464,14 @@ class _Uploader:
 
     def pack_at(self, slot: int, base: int, arrays: Sequence) -> list[int]:
         """``pack`` into a prepared slot at byte ``base`` (packer threads; the ranges of a
-        group's micro-batches are disjoint): the offsets of the arrays inside the slot."""
-        rebases = [item[1:] if isinstance(item, tuple) else None for item in arrays]
-        arrays = [item[0] if isinstance(item, tuple) else item for item in arrays]
+        group's micro-batches are disjoint): the offsets of the arrays inside the slot, for
+        ``None`` the offset the next array gets."""
         host = self._staging[slot].numpy()
         offsets, at = [], base
-        for array, rebase in zip(arrays, rebases):
+        for item in arrays:
             offsets.append(at)
-            if array is None:
-                continue
-            if array.nbytes:
-                target = host[at:at + array.nbytes].view(array.dtype).reshape(array.shape)
-                if rebase is None:
-                    np.copyto(target, array)
-                else:
-                    shift, low, high = rebase
-                    if shift:
-                        np.subtract(array, shift, out=target)
-                    else:
-                        np.copyto(target, array)
-                    if target.size and int(target.view(np.uint32).max()) >= high - low:
-                        raise GraphValidationError("edge index outside shard node range")
-            at += self.padded(array.nbytes)
+            if item is not None:
+                at += self.padded(self._write(host, at, item))
         return offsets
 
     def send_range(self, slot: int, total: int) -> torch.Tensor:
@@ -530,9 +525,6 @@ class Ginfinity:
         self._copier: _Downloader | None = None
         self._direct: _DirectDownloader | None = None
         self._device_block: torch.Tensor | None = None
-        self._preparer: ThreadPoolExecutor | None = None
-        self._uploader: _Uploader | None = None
-        self._copy_stream: "torch.cuda.Stream | None" = None
         self._lanes: "list[tuple[DeviceEncoder, torch.cuda.Stream]] | None" = None
         self._metadata = checkpoint.metadata
         self._state = checkpoint.state
@@ -576,6 +568,19 @@ class Ginfinity:
         loaded = cls(engine, checkpoint, device, full_precision=full_precision)
         loaded.pinned_outputs = None if pinned_outputs is None else bool(pinned_outputs)
         return loaded
+
+    # -- helpers of a GPU encoder, made when a call first needs them ----------------
+    @functools.cached_property
+    def _uploader(self) -> _Uploader:
+        return _Uploader(self._engine.device)
+
+    @functools.cached_property
+    def _preparer(self) -> ThreadPoolExecutor:
+        return ThreadPoolExecutor(max_workers=_PACKERS, thread_name_prefix="ginfinity-prep")
+
+    @functools.cached_property
+    def _copy_stream(self) -> "torch.cuda.Stream":
+        return torch.cuda.Stream(device=self._engine.device)
 
     # -- metadata -----------------------------------------------------------------
     @property
@@ -632,6 +637,89 @@ class Ginfinity:
             shard, max_batch_nodes=max_batch_nodes,
             max_batch_edges=max_batch_edges, embedding_dtype=embedding_dtype)
 
+    @staticmethod
+    def _check_limits(max_batch_nodes: int, max_batch_edges: int,
+                      node_ptr: np.ndarray | None = None,
+                      edge_ptr: np.ndarray | None = None) -> None:
+        """The reference's refusals of a call's limits (api.py:196-210) against the records'
+        offsets; without offsets the first of them only (the window road knows its counts once
+        the windows are selected)."""
+        if max_batch_nodes <= 0 or max_batch_edges <= 0:
+            raise ValueError("batch node and edge limits must be positive")
+        if node_ptr is None:
+            return
+        # (records that fit a micro-batch as a whole have none that does not: the per-record
+        # maxima are looked at only above that — 7 us per shard of a 128-shard call's prologue)
+        if (int(node_ptr[-1]) > max_batch_nodes
+                and int(np.diff(node_ptr).max()) > max_batch_nodes):
+            raise ValueError("max_batch_nodes is smaller than the longest graph")
+        if (int(edge_ptr[-1]) > max_batch_edges
+                and int(np.diff(edge_ptr).max()) > max_batch_edges):
+            raise ValueError("max_batch_edges is smaller than the largest graph")
+
+    def _encode_grouped(self, bounds: Sequence[tuple[int, int]], counts: np.ndarray,
+                        embedding_dtype: np.dtype, member, *, jobs: Sequence = (),
+                        before_group=None) -> list[np.ndarray]:
+        """Several micro-batches → the per-record host arrays of one call: the host pipeline of
+        ``encode_graphs`` and of both ``encode_many`` roads.  ``bounds``: the records of every
+        micro-batch; ``counts``: the output rows of every record.  ``member(index, out,
+        direct)`` puts micro-batch ``index`` on the device and returns ``(packed, (features,
+        edge_index, edge_types, out_rows, out))`` — ``out`` is where its rows go, ``direct``
+        says that inputs may be sent ``mapped``, ``packed`` is the staging slot it did send that
+        way (``None``: it copied).  ``before_group(first, direct)`` runs on this thread before
+        the group that starts with micro-batch ``first``; ``jobs``: what the caller has on
+        helper threads, settled if the call leaves through an exception.
+
+        Three kinds of thread: helpers prepare inputs ahead (the caller's business); THIS thread
+        uploads, launches and records events (~0.1 ms per micro-batch); the copy engine — or,
+        for pageable results, COPIERS through their pinned ring — brings the embeddings back
+        into one host block.  PCIe is full duplex and the host copies run in parallel, so the
+        call is bound by the 230 MB of D2H (config 2), not by a thread.  Compute stays on ONE
+        stream in micro-batch order (one encoder, one workspace)."""
+        uploader, device = self._uploader, self._engine.device
+        try:
+            torch_dtype, _code, exact = device_output_dtype(embedding_dtype)
+            produced = embedding_dtype if exact else np.dtype(np.float64)
+            row_ptr = np.zeros(len(counts) + 1, dtype=np.int64)
+            np.cumsum(counts, out=row_ptr[1:])
+            # the first output row of every micro-batch, then the end of the last
+            rows = row_ptr[[start for start, _stop in bounds] + [len(counts)]].tolist()
+            host_block, fetch, direct = self._landing(rows[-1], produced, torch_dtype, exact)
+            device_rows = self._device_rows(rows[-1], torch_dtype)
+            assert MICROBATCH_GROUP <= uploader.slots   # a group's inputs live in the ring
+            landings = []
+            for group in _groups(len(bounds), ramp=True):
+                # the micro-batches of a group share every launch (gfy_encode_coo_batch): a
+                # 60,000-node micro-batch by itself gives a CU less than one round of tiles
+                if before_group is not None:
+                    before_group(group.start, direct)
+                members = [member(index, device_rows[rows[index]:rows[index + 1]], direct)
+                           for index in group]
+                self._engine.encode_coo_group([tensors for _packed, tensors in members])
+                ready = torch.cuda.Event()
+                ready.record(torch.cuda.current_stream(device))
+                if direct:                  # mapped inputs are read until the group has run
+                    for packed, _tensors in members:
+                        if packed is not None:
+                            uploader.hold(packed, ready)
+                # (the workers run no interpreter-level loops: a worker cutting 400 views holds
+                # the GIL for 0.3 ms at a time and this thread, which needs it between every two
+                # enqueues, took 0.6 ms per micro-batch instead of 0.1)
+                first, end = rows[group.start], rows[group.stop]
+                landings.append((fetch(device_rows[first:end], ready, first, end - first), group))
+        except BaseException:
+            _settle(jobs)      # no helper may still be writing a staging slot after we leave
+            raise
+        # the per-record views are cut here, group by group as the copies land
+        outputs: list[np.ndarray] = []
+        for landing, group in landings:
+            landing.result()
+            for index in group:
+                start, stop = bounds[index]
+                outputs.extend(self._splitter(counts[start:stop], embedding_dtype, exact)(
+                    host_block[rows[index]:rows[index + 1]]))
+        return outputs
+
     def _encode_records(self, records: Sequence[RNA], max_batch_nodes: int,
                         max_batch_edges: int, embedding_dtype: np.dtype
                         ) -> list[np.ndarray]:
@@ -640,79 +728,36 @@ class Ginfinity:
         record offsets and the positional columns cross PCIe, 2 + 8 bytes per nucleotide
         instead of 46.  Same packing, limits and errors as ``encode_graphs``."""
         text = shard_text(records, self._graph_spec)
-        if max_batch_nodes <= 0 or max_batch_edges <= 0:
-            raise ValueError("batch node and edge limits must be positive")
-        lengths, edge_counts = text.lengths.tolist(), text.edge_counts.tolist()
-        if max(lengths) > max_batch_nodes:
-            raise ValueError("max_batch_nodes is smaller than the longest graph")
-        if max(edge_counts) > max_batch_edges:
-            raise ValueError("max_batch_edges is smaller than the largest graph")
-        torch_dtype, _code, exact = device_output_dtype(embedding_dtype)
-        engine, device = self._engine, self._engine.device
-        spec = self._graph_spec
-        if self._uploader is None:
-            self._uploader = _Uploader(device)
-        pending, verdicts = [], []
-        bounds = microbatch_bounds(lengths, edge_counts, max_batch_nodes, max_batch_edges)
-        produced = np.dtype(embedding_dtype) if exact else np.dtype(np.float64)
-        total_rows = int(text.node_ptr[-1] - text.node_ptr[0])
-        host_block, fetch, direct = self._landing(total_rows, produced, torch_dtype, exact)
-        device_rows = self._device_rows(total_rows, torch_dtype)
+        self._check_limits(max_batch_nodes, max_batch_edges, text.node_ptr, text.edge_ptr)
+        engine, uploader, spec = self._engine, self._uploader, self._graph_spec
+        lengths = text.lengths
+        bounds = microbatch_bounds(lengths, text.edge_counts, max_batch_nodes, max_batch_edges)
+        struct_states = 1 if spec.struct_feature == "A" else 3
         # the positional columns (numpy sin / cos, GIL released) of later micro-batches are
-        # computed on a second helper thread while this one uploads and launches
-        if self._preparer is None:
-            self._preparer = ThreadPoolExecutor(max_workers=_PACKERS,
-                                                thread_name_prefix="ginfinity-prep")
+        # computed on helper threads while this one uploads and launches
         columns_of = [self._preparer.submit(text.positional, a, b) for a, b in bounds]
-        assert MICROBATCH_GROUP <= self._uploader.slots   # a group's inputs live in the ring
-        try:
-            for group in _groups(len(bounds), ramp=True):
-                members, group_row = [], None
-                for index in group:
-                    start, stop = bounds[index]
-                    n0, n1 = int(text.node_ptr[start]), int(text.node_ptr[stop])
-                    e0, e1 = int(text.edge_ptr[start]), int(text.edge_ptr[stop])
-                    columns = columns_of[index].result()
-                    packed = self._uploader.pack(self._uploader.reserve(), (
-                        text.bases[n0:n1], text.marks[n0:n1], text.node_ptr[start:stop + 1],
-                        text.edge_ptr[start:stop + 1], columns))
-                    bases, marks, node_ptr, edge_ptr, positional = self._uploader.send(
-                        packed, mapped=direct)
-                    features, edge_index, edge_types, first_invalid = engine.build_graphs(
-                        bases, marks, node_ptr, edge_ptr, positional, n1 - n0, e1 - e0,
-                        struct_states=1 if spec.struct_feature == "A" else 3,
-                        skip2=spec.has_skip2)
-                    row = n0 - int(text.node_ptr[0])
-                    group_row = row if group_row is None else group_row
-                    members.append((packed, (features, edge_index, edge_types, None,
-                                             device_rows[row:row + n1 - n0])))
-                    verdicts.append((start, first_invalid))
-                    pending.append((row, n1 - n0, lengths[start:stop]))
-                engine.encode_coo_group([tensors for _packed, tensors in members])
-                ready = torch.cuda.Event()
-                ready.record(torch.cuda.current_stream(device))
-                if direct:
-                    for packed, _tensors in members:
-                        self._uploader.hold(packed, ready)
-                last_row, last_kept, _counts = pending[-1]
-                landing = fetch(device_rows[group_row:last_row + last_kept], ready, group_row,
-                                last_row + last_kept - group_row)
-                for slot in range(len(pending) - len(members), len(pending)):
-                    pending[slot] = (landing,) + pending[slot]
-        except BaseException:
-            _settle(columns_of)
-            raise
-        outputs: list[np.ndarray] = []
-        for job, row, kept, counts in pending:     # views cut here, as the copies land
-            job.result()
-            outputs.extend(self._splitter(counts, embedding_dtype, exact)(
-                host_block[row:row + kept]))
-        for start, first_invalid in verdicts:
+        verdicts = []
+
+        def member(index: int, out: torch.Tensor, direct: bool):
+            start, stop = bounds[index]
+            n0, n1 = int(text.node_ptr[start]), int(text.node_ptr[stop])
+            e0, e1 = int(text.edge_ptr[start]), int(text.edge_ptr[stop])
+            columns = columns_of[index].result()
+            packed = uploader.pack(uploader.reserve(), (
+                text.bases[n0:n1], text.marks[n0:n1], text.node_ptr[start:stop + 1],
+                text.edge_ptr[start:stop + 1], columns))
+            bases, marks, node_ptr, edge_ptr, positional = uploader.send(packed, mapped=direct)
+            features, edge_index, edge_types, first_invalid = engine.build_graphs(
+                bases, marks, node_ptr, edge_ptr, positional, n1 - n0, e1 - e0,
+                struct_states=struct_states, skip2=spec.has_skip2)
+            verdicts.append((start, first_invalid))
+            return packed, (features, edge_index, edge_types, None, out)
+
+        outputs = self._encode_grouped(bounds, lengths, embedding_dtype, member, jobs=columns_of)
+        for start, first_invalid in verdicts:      # (read only now: every copy has landed)
             bad = int(first_invalid.item())
             if bad >= 0:
-                raise GraphValidationError(
-                    f"record {records[start + bad].identifier!r}: sequence or structure "
-                    "text is not a balanced dot-bracket string over A, C, G, U")
+                raise GraphValidationError(self._BAD_TEXT.format(records[start + bad].identifier))
         return outputs
 
     _BAD_TEXT = ("record {!r}: sequence or structure text is not a balanced dot-bracket "
@@ -728,8 +773,6 @@ class Ginfinity:
         if context_hops < 1:
             raise ValueError("context_hops must be >= 1")
         text = window_text(records, spec)
-        if self._uploader is None:
-            self._uploader = _Uploader(self._engine.device)
         bases, marks, mol_ptr, molecule, start, end, positional = self._uploader(
             (text.bases, text.marks, text.mol_ptr, text.molecule, text.start, text.end,
              text.positional()))
@@ -756,64 +799,40 @@ class Ginfinity:
         bit for bit) without building any whole molecule — each distinct molecule's text
         crosses PCIe once, however many windows it has.  Same packing, limits and errors as
         ``encode_graphs``, applied to the SLICED node and edge counts."""
-        if max_batch_nodes <= 0 or max_batch_edges <= 0:
-            raise ValueError("batch node and edge limits must be positive")
+        self._check_limits(max_batch_nodes, max_batch_edges)
         spec = self._graph_spec
         text, windows, positional, node_ptr, edge_ptr = self._select_windows(
             records, keep_paired_neighbours, context_hops, spec)
-        lengths, edge_counts = np.diff(node_ptr).tolist(), np.diff(edge_ptr).tolist()
-        if max(lengths) > max_batch_nodes:
-            raise ValueError("max_batch_nodes is smaller than the longest graph")
-        if max(edge_counts) > max_batch_edges:
-            raise ValueError("max_batch_edges is smaller than the largest graph")
-        torch_dtype, _code, exact = device_output_dtype(embedding_dtype)
-        engine, device = self._engine, self._engine.device
-        bounds = microbatch_bounds(lengths, edge_counts, max_batch_nodes, max_batch_edges)
-        produced = np.dtype(embedding_dtype) if exact else np.dtype(np.float64)
+        self._check_limits(max_batch_nodes, max_batch_edges, node_ptr, edge_ptr)
+        engine, uploader = self._engine, self._uploader
+        bounds = microbatch_bounds(np.diff(node_ptr), np.diff(edge_ptr), max_batch_nodes,
+                                   max_batch_edges)
         core_counts = text.core_counts
         core_ptr = np.zeros(len(records) + 1, dtype=np.int64)
         np.cumsum(core_counts, out=core_ptr[1:])
-        total_rows = int(core_ptr[-1])
-        host_block, fetch, _direct = self._landing(total_rows, produced, torch_dtype, exact)
-        device_rows = self._device_rows(total_rows, torch_dtype)
         struct_states = 1 if spec.struct_feature == "A" else 3
-        pending, verdicts = [], []
-        assert MICROBATCH_GROUP <= self._uploader.slots
-        for group in _groups(len(bounds), ramp=True):
-            members = []
-            for index in group:
-                start, stop = bounds[index]
-                n0, n1 = int(node_ptr[start]), int(node_ptr[stop])
-                e0, e1 = int(edge_ptr[start]), int(edge_ptr[stop])
-                c0, c1 = int(core_ptr[start]), int(core_ptr[stop])
-                # out_rows only where a context node has to be dropped (as _pack_microbatch)
-                cores = core_ptr[start:stop + 1] if n1 - n0 != c1 - c0 else None
-                batch_nodes, batch_edges, batch_cores = self._uploader(
-                    (node_ptr[start:stop + 1], edge_ptr[start:stop + 1], cores))
-                features, edge_index, edge_types, _residue, _roles, out_rows, first_invalid = \
-                    engine.window_emit(windows, start, batch_nodes, batch_edges, batch_cores,
-                                       positional, n1 - n0, e1 - e0, c1 - c0,
-                                       struct_states=struct_states)
-                if records_pay(node_ptr[start:stop + 1], edge_ptr[start:stop + 1]):
-                    attach_records(edge_index, batch_nodes, batch_edges)
-                members.append((features, edge_index, edge_types, out_rows,
-                                device_rows[c0:c1]))
-                verdicts.append(first_invalid)
-                pending.append((c0, c1 - c0, core_counts[start:stop]))
-            engine.encode_coo_group(members)
-            ready = torch.cuda.Event()
-            ready.record(torch.cuda.current_stream(device))
-            group_row = pending[-len(members)][0]
-            last_row, last_kept, _counts = pending[-1]
-            landing = fetch(device_rows[group_row:last_row + last_kept], ready, group_row,
-                            last_row + last_kept - group_row)
-            for slot in range(len(pending) - len(members), len(pending)):
-                pending[slot] = (landing,) + pending[slot]
-        outputs: list[np.ndarray] = []
-        for job, row, kept, counts in pending:
-            job.result()
-            outputs.extend(self._splitter(counts, embedding_dtype, exact)(
-                host_block[row:row + kept]))
+        verdicts = []
+
+        def member(index: int, out: torch.Tensor, _direct: bool):
+            start, stop = bounds[index]
+            n0, n1 = int(node_ptr[start]), int(node_ptr[stop])
+            e0, e1 = int(edge_ptr[start]), int(edge_ptr[stop])
+            c0, c1 = int(core_ptr[start]), int(core_ptr[stop])
+            # out_rows only where a context node has to be dropped
+            cores = core_ptr[start:stop + 1] if n1 - n0 != c1 - c0 else None
+            # (three small offset arrays: through the copying send, whatever the results land in)
+            batch_nodes, batch_edges, batch_cores = uploader(
+                (node_ptr[start:stop + 1], edge_ptr[start:stop + 1], cores))
+            features, edge_index, edge_types, _residue, _roles, out_rows, first_invalid = \
+                engine.window_emit(windows, start, batch_nodes, batch_edges, batch_cores,
+                                   positional, n1 - n0, e1 - e0, c1 - c0,
+                                   struct_states=struct_states)
+            if records_pay(node_ptr[start:stop + 1], edge_ptr[start:stop + 1]):
+                attach_records(edge_index, batch_nodes, batch_edges)
+            verdicts.append(first_invalid)
+            return None, (features, edge_index, edge_types, out_rows, out)
+
+        outputs = self._encode_grouped(bounds, core_counts, embedding_dtype, member)
         for first_invalid in verdicts:
             bad = int(first_invalid.item())
             if bad >= 0:
@@ -870,16 +889,7 @@ class Ginfinity:
             raise GraphCompatibilityError(
                 "graphs were built with a specification incompatible with "
                 "this encoder")
-        if max_batch_nodes <= 0 or max_batch_edges <= 0:
-            raise ValueError("batch node and edge limits must be positive")
-        # (a shard that fits a micro-batch as a whole has no record that does not: the per-record
-        # maxima are looked at only above that — 7 us per shard of a 128-shard call's prologue)
-        if (int(shard.node_ptr[-1]) > max_batch_nodes
-                and int(np.diff(shard.node_ptr).max()) > max_batch_nodes):
-            raise ValueError("max_batch_nodes is smaller than the longest graph")
-        if (int(shard.edge_ptr[-1]) > max_batch_edges
-                and int(np.diff(shard.edge_ptr).max()) > max_batch_edges):
-            raise ValueError("max_batch_edges is smaller than the largest graph")
+        self._check_limits(max_batch_nodes, max_batch_edges, shard.node_ptr, shard.edge_ptr)
         return shard
 
     @staticmethod
@@ -913,96 +923,50 @@ class Ginfinity:
             for start, stop in bounds:
                 outputs.extend(self._run_graph_shard(shard.slice(start, stop), embedding_dtype))
             return outputs
-        # Several micro-batches, three kinds of thread: PACKERS slice the shard, rebase and
-        # range-check the edges and copy the micro-batch's arrays into pinned staging (up to
-        # `slots - 1` micro-batches ahead); THIS thread uploads, launches and records events
-        # (~0.1 ms per micro-batch); COPIERS bring the embeddings back through their pinned ring
-        # into one host block.  PCIe is full duplex and the host copies run in parallel, so the
-        # call is bound by the 230 MB of D2H (config 2), not by a thread.  Compute stays on ONE
-        # stream in micro-batch order (one encoder, one workspace).
-        torch_dtype, _code, exact = device_output_dtype(embedding_dtype)
-        if self._uploader is None:
-            self._uploader = _Uploader(self._engine.device)
-        if self._preparer is None:
-            self._preparer = ThreadPoolExecutor(max_workers=_PACKERS,
-                                                thread_name_prefix="ginfinity-prep")
-        uploader = self._uploader
-        core_counts = shard.core_count_array()
-        produced = np.dtype(embedding_dtype) if exact else np.dtype(np.float64)
-        total_rows = int(core_counts.sum())
-        host_block, fetch, direct = self._landing(total_rows, produced, torch_dtype, exact)
-        device_rows = self._device_rows(total_rows, torch_dtype)
-
-        def prepare(slot: int, start: int, stop: int):
-            # (mapped inputs never take the record-range set-up, see below: no boundaries, no check)
-            return self._pack_microbatch(uploader, slot, shard, start, stop,
-                                         with_records=not direct)
-
-        assert MICROBATCH_GROUP <= uploader.slots
+        # PACKERS slice the shard, rebase and range-check the edges and copy the micro-batch's
+        # arrays into pinned staging, up to `slots - 1` micro-batches ahead of the launches
+        uploader, preparer = self._uploader, self._preparer
         jobs: list = []
-        pending = []
-        first_row = 0
-        try:
-            for group in _groups(len(bounds), ramp=True):
-                # the micro-batches of a group share every launch (gfy_encode_coo_batch): a
-                # 60,000-node micro-batch by itself gives a CU less than one round of tiles
-                members, group_row = [], first_row
-                # packers run ahead of this thread, but never into a staging slot whose last
-                # user has not been launched: a slot is guarded by the event of the GROUP that
-                # read it (`hold`, below), so micro-batch j may be packed once micro-batch
-                # j - slots belongs to a group in front of this one
-                while len(jobs) < len(bounds) and len(jobs) < group.start + uploader.slots:
-                    a, b = bounds[len(jobs)]
-                    jobs.append(self._preparer.submit(prepare, uploader.reserve(), a, b))
-                for index in group:
-                    packed, kept = jobs[index].result()
-                    features, edge_index, edge_types, out_rows, node_ptr, edge_ptr = \
-                        uploader.send(packed, mapped=direct)
-                    # mapped inputs are read over PCIe: the record-range set-up reads a record's
-                    # destinations once per 256 of its rows, the counting kernel every array once
-                    if node_ptr is not None and not direct:
-                        attach_records(edge_index, node_ptr, edge_ptr)
-                    members.append((packed, (features, edge_index, edge_types, out_rows,
-                                             device_rows[first_row:first_row + kept])))
-                    start, stop = bounds[index]
-                    pending.append((first_row, kept, core_counts[start:stop]))
-                    first_row += kept
-                self._engine.encode_coo_group([tensors for _packed, tensors in members])
-                ready = torch.cuda.Event()
-                ready.record(torch.cuda.current_stream(self._engine.device))
-                if direct:
-                    for packed, _tensors in members:
-                        uploader.hold(packed, ready)
-                # (the workers run no interpreter-level loops: a worker cutting 400 views holds
-                # the GIL for 0.3 ms at a time and this thread, which needs it between every two
-                # enqueues, took 0.6 ms per micro-batch instead of 0.1)
-                landing = fetch(device_rows[group_row:first_row], ready, group_row,
-                                first_row - group_row)
-                for slot in range(len(pending) - len(members), len(pending)):
-                    pending[slot] = (landing,) + pending[slot]
-        except BaseException:
-            _settle(jobs)      # no packer may still be writing a staging slot after we leave
-            raise
-        # the per-record views are cut here, group by group as the copies land
-        outputs: list[np.ndarray] = []
-        for job, row, kept, counts in pending:
-            job.result()
-            outputs.extend(self._splitter(counts, embedding_dtype, exact)(
-                host_block[row:row + kept]))
-        return outputs
+
+        def pack_ahead(first: int, direct: bool) -> None:
+            # packers run ahead of the launching thread, but never into a staging slot whose
+            # last user has not been launched: a slot is guarded by the event of the GROUP that
+            # read it (`hold`), so micro-batch j may be packed once micro-batch j - slots
+            # belongs to a group in front of this one
+            while len(jobs) < len(bounds) and len(jobs) < first + uploader.slots:
+                a, b = bounds[len(jobs)]
+                # (mapped inputs never take the record-range set-up, see `member`: no
+                # boundaries, no check)
+                jobs.append(preparer.submit(self._pack_microbatch, uploader, uploader.reserve(),
+                                            shard, a, b, not direct))
+
+        def member(index: int, out: torch.Tensor, direct: bool):
+            packed, kept = jobs[index].result()
+            assert kept == out.shape[0]
+            features, edge_index, edge_types, out_rows, node_ptr, edge_ptr = \
+                uploader.send(packed, mapped=direct)
+            # mapped inputs are read over PCIe: the record-range set-up reads a record's
+            # destinations once per 256 of its rows, the counting kernel every array once
+            if node_ptr is not None and not direct:
+                attach_records(edge_index, node_ptr, edge_ptr)
+            return packed, (features, edge_index, edge_types, out_rows, out)
+
+        return self._encode_grouped(bounds, shard.core_count_array(), embedding_dtype, member,
+                                    jobs=jobs, before_group=pack_ahead)
 
     @staticmethod
-    def _pack_microbatch(uploader: "_Uploader", slot: int, shard: GraphShard, start: int,
-                         stop: int, with_records: bool = True):
-        """Records [start, stop) of ``shard`` → pinned staging slot ``slot`` (packer threads):
-        the arrays of GraphShard.slice(start, stop) (graph.py:414-444: edge indices rebased to the
-        first node of the range) without building — and re-validating — a GraphShard per
-        micro-batch; the one check of GraphShard.__post_init__ that depends on the slice
-        (graph.py:318-321 after the rebasing: an edge that leaves the micro-batch's node range,
-        which the whole-shard range check cannot see) is made on the way into pinned memory and
-        refused exactly as the reference refuses it.  ``with_records``: the record boundaries go
-        along where they pay and no edge joins two records (``records_closed``: such an edge is
-        legal, and only the counting set-up honours it).  Returns ``(packed, kept core rows)``."""
+    def _microbatch_arrays(shard: GraphShard, start: int, stop: int, with_records: bool):
+        """Records [start, stop) of ``shard`` as the six entries ``_Uploader.pack`` / ``pack_at``
+        take, and the core rows they keep: the arrays of GraphShard.slice(start, stop)
+        (graph.py:414-444: edge indices rebased to the first node of the range) without building
+        — and re-validating — a GraphShard per micro-batch; the one check of
+        GraphShard.__post_init__ that depends on the slice (graph.py:318-321 after the rebasing:
+        an edge that leaves the micro-batch's node range, which the whole-shard range check
+        cannot see) is made on the way into pinned memory and refused exactly as the reference
+        refuses it.  ``out_rows`` only where a context node has to be dropped.
+        ``with_records``: the record boundaries go along where they pay and no edge joins two
+        records (``records_closed``: such an edge is legal, and only the counting set-up honours
+        it)."""
         n0, n1 = int(shard.node_ptr[start]), int(shard.node_ptr[stop])
         e0, e1 = int(shard.edge_ptr[start]), int(shard.edge_ptr[stop])
         roles = shard.node_roles[n0:n1]
@@ -1020,10 +984,16 @@ class Ginfinity:
                 and records_closed(shard.edge_index[:, e0:e1], shard.node_ptr[start:stop + 1],
                                    shard.edge_ptr[start:stop + 1])):
             node_ptr, edge_ptr = shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1]
-        packed = uploader.pack(slot, (
-            shard.node_features[n0:n1], (shard.edge_index[:, e0:e1], np.int32(n0), n0, n1),
-            shard.edge_types[e0:e1], rows, node_ptr, edge_ptr))
-        return packed, kept
+        return (shard.node_features[n0:n1], (shard.edge_index[:, e0:e1], np.int32(n0), n0, n1),
+                shard.edge_types[e0:e1], rows, node_ptr, edge_ptr), kept
+
+    @staticmethod
+    def _pack_microbatch(uploader: "_Uploader", slot: int, shard: GraphShard, start: int,
+                         stop: int, with_records: bool = True):
+        """Records [start, stop) of ``shard`` → pinned staging slot ``slot`` (packer threads):
+        ``(packed, kept core rows)``."""
+        arrays, kept = Ginfinity._microbatch_arrays(shard, start, stop, with_records)
+        return uploader.pack(slot, arrays), kept
 
     @staticmethod
     def _microbatch_bytes(shard: GraphShard, start: int, stop: int) -> int:
@@ -1046,7 +1016,7 @@ class Ginfinity:
     def _pack_microbatch_at(uploader: "_Uploader", slot: int, base: int, shard: GraphShard,
                             start: int, stop: int):
         """``_pack_microbatch`` into a prepared group slot at byte ``base``: ``(offsets of the six
-        arrays in the slot — 0 where an array is absent —, nodes, edges, records or 0, kept)``."""
+        arrays in the slot — -1 where an array is absent —, nodes, edges, records or 0, kept)``."""
         if NATIVE_PACKER and _packable(shard):
             # one call without the interpreter lock (csrc/gfy_base.cpp): the numpy form below
             # kept a pool of packers behind one lock — 128 micro-batches, 561 MB: 19-24 ms
@@ -1064,26 +1034,11 @@ class Ginfinity:
                     raise GraphValidationError(message)
                 native.check(status, "gfy_pack_microbatch")
             return list(offsets), int(counts[0]), int(counts[1]), int(counts[2]), int(counts[3])
-        n0, n1 = int(shard.node_ptr[start]), int(shard.node_ptr[stop])
-        e0, e1 = int(shard.edge_ptr[start]), int(shard.edge_ptr[stop])
-        roles = shard.node_roles[n0:n1]
-        rows, kept = None, n1 - n0
-        if roles.any():
-            core = roles == 0
-            kept = int(np.count_nonzero(core))
-            rows = np.cumsum(core, dtype=np.int32) - np.int32(1)
-            rows[~core] = -1
-        node_ptr = edge_ptr = None
-        if (records_pay(shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1])
-                and records_closed(shard.edge_index[:, e0:e1], shard.node_ptr[start:stop + 1],
-                                   shard.edge_ptr[start:stop + 1])):
-            node_ptr, edge_ptr = shard.node_ptr[start:stop + 1], shard.edge_ptr[start:stop + 1]
-        arrays = (shard.node_features[n0:n1], (shard.edge_index[:, e0:e1], np.int32(n0), n0, n1),
-                  shard.edge_types[e0:e1], rows, node_ptr, edge_ptr)
+        arrays, kept = Ginfinity._microbatch_arrays(shard, start, stop, True)
         offsets = uploader.pack_at(slot, base, arrays)
-        present = (True, True, True, rows is not None, node_ptr is not None, edge_ptr is not None)
-        return ([offset if here else -1 for offset, here in zip(offsets, present)],
-                n1 - n0, e1 - e0, stop - start if node_ptr is not None else 0, kept)
+        features, (edges, *_rebase), _types, _rows, node_ptr, _edge_ptr = arrays
+        return ([-1 if array is None else offset for offset, array in zip(offsets, arrays)],
+                len(features), edges.shape[1], stop - start if node_ptr is not None else 0, kept)
 
     def _device_rows(self, rows: int, torch_dtype: torch.dtype) -> torch.Tensor:
         """[rows, 128] of ``torch_dtype`` on the device, a view of ONE block the encoder keeps
@@ -1193,47 +1148,62 @@ class Ginfinity:
         a tensor of that shape to write into (steady-state loops: no allocation per call)."""
         if self._engine is None:
             raise ValueError("device-resident encoding needs a GPU encoder (device='cuda')")
-        rows = sum(kept for *_arrays, kept in staged)
-        block = out
-        if block is None:
-            block = torch.empty((rows, self.embedding_dimension), dtype=torch.float16,
-                                device=self._engine.device)
-        if (tuple(block.shape) != (rows, self.embedding_dimension)
-                or block.dtype != torch.float16 or not block.is_contiguous()):
-            raise ValueError("out must be a contiguous float16 [total core rows, 128] tensor")
+        block = self._device_out(sum(kept for *_arrays, kept in staged), out)
         groups = _groups(len(staged))
         # Two groups in flight (fp16 model): the tail of one group's layer launches — the last,
-        # partial round of tiles — runs under the next group's workgroups.  Each lane is an
-        # encoder of its own (hidden-state buffers, workspace) on a stream of its own; the
-        # caller's stream waits for both.  ``STAGED_LANES = 1``: one group after the other.
-        lanes = self._two_lanes() if (STAGED_LANES > 1 and len(groups) > 1
-                                      and not self.full_precision) else None
+        # partial round of tiles — runs under the next group's workgroups.
+        # ``STAGED_LANES = 1``: one group after the other.
+        with self._lanes_joined(STAGED_LANES > 1 and len(groups) > 1) as lanes:
+            first = 0
+            for number, group in enumerate(groups):
+                members = []
+                for index in group:
+                    features, edge_index, edge_types, out_rows, kept = staged[index]
+                    members.append((features, edge_index, edge_types, out_rows,
+                                    block[first:first + kept]))
+                    first += kept
+                if lanes:
+                    engine, stream = lanes[number % len(lanes)]
+                    with torch.cuda.stream(stream):
+                        engine.encode_coo_group(members)
+                else:
+                    self._engine.encode_coo_group(members)
+        return block
+
+    def _device_out(self, rows: int, out: torch.Tensor | None) -> torch.Tensor:
+        """The fp16 block a device-resident call writes: ``out`` if it is one of ``rows`` rows,
+        a new one without it."""
+        width = self.embedding_dimension
+        if out is None:
+            return torch.empty((rows, width), dtype=torch.float16, device=self._engine.device)
+        if (tuple(out.shape) != (rows, width) or out.dtype != torch.float16
+                or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous float16 [total core rows, 128] tensor")
+        return out
+
+    @contextlib.contextmanager
+    def _lanes_joined(self, wanted: bool):
+        """``with ... as lanes``: two lanes for the groups of a device-resident call (fp16 model;
+        ``None`` if not ``wanted``).  A lane is an encoder of its own (hidden-state buffers,
+        workspace) on a stream of its own; both start behind what the caller's stream has
+        queued — the inputs, ``out``'s previous readers — and the caller's stream waits for both
+        at the end, also when the call leaves through an exception."""
+        if not wanted or self.full_precision:
+            yield None
+            return
+        lanes = self._two_lanes()
         current = torch.cuda.current_stream(self._engine.device)
-        if lanes:
-            ready = torch.cuda.Event()
-            ready.record(current)                 # the staged arrays, `out`'s previous readers
-            for _engine, stream in lanes:
-                stream.wait_event(ready)
-        first = 0
-        for number, group in enumerate(groups):
-            members = []
-            for index in group:
-                features, edge_index, edge_types, out_rows, kept = staged[index]
-                members.append((features, edge_index, edge_types, out_rows,
-                                block[first:first + kept]))
-                first += kept
-            if lanes:
-                engine, stream = lanes[number % len(lanes)]
-                with torch.cuda.stream(stream):
-                    engine.encode_coo_group(members)
-            else:
-                self._engine.encode_coo_group(members)
-        if lanes:
+        ready = torch.cuda.Event()
+        ready.record(current)
+        for _engine, stream in lanes:
+            stream.wait_event(ready)
+        try:
+            yield lanes
+        finally:
             for _engine, stream in lanes:
                 done = torch.cuda.Event()
                 done.record(stream)
                 current.wait_event(done)
-        return block
 
     def _two_lanes(self) -> "list[tuple[DeviceEncoder, torch.cuda.Stream]]":
         if self._lanes is None:
@@ -1267,22 +1237,8 @@ class Ginfinity:
             counts.append(shard.core_counts)
             plan += [(shard, a, b) for a, b in self._shard_bounds(
                 shard, max_batch_nodes, max_batch_edges)]
-        rows = sum(sum(per_record) for per_record in counts)
-        block = out
-        if block is None:
-            block = torch.empty((rows, self.embedding_dimension), dtype=torch.float16,
-                                device=device)
-        if (tuple(block.shape) != (rows, self.embedding_dimension)
-                or block.dtype != torch.float16 or not block.is_contiguous()):
-            raise ValueError("out must be a contiguous float16 [total core rows, 128] tensor")
-        if self._uploader is None:
-            self._uploader = _Uploader(device)
-        if self._preparer is None:
-            self._preparer = ThreadPoolExecutor(max_workers=_PACKERS,
-                                                thread_name_prefix="ginfinity-prep")
-        if self._copy_stream is None:
-            self._copy_stream = torch.cuda.Stream(device=device)
-        uploader, copies = self._uploader, self._copy_stream
+        block = self._device_out(sum(sum(per_record) for per_record in counts), out)
+        uploader, preparer, copies = self._uploader, self._preparer, self._copy_stream
         compute = torch.cuda.current_stream(device)
         # A GROUP of micro-batches shares one staging slot, one H2D copy and one event: per
         # micro-batch the launching thread then only hands four packers their byte ranges and
@@ -1305,49 +1261,38 @@ class Ginfinity:
             # handed to the pool is 11 us of this thread
             pieces = [[item] for item in items] if len(submitted) < 2 else [items]
             for piece in pieces:
-                jobs_of.append(self._preparer.submit(self._pack_items, uploader, slot, piece))
+                jobs_of.append(preparer.submit(self._pack_items, uploader, slot, piece))
             submitted.append((slot, at, jobs_of))
 
         # ``HOST_FEED_LANES = 2``: two groups in flight as in ``encode_staged`` — a lane = an
         # encoder and a stream of its own; group g runs on lane g mod 2 behind ITS upload only,
         # the caller's stream waits for both at the end.  Not the default: see HOST_FEED_LANES.
-        lanes = self._two_lanes() if (HOST_FEED_LANES > 1 and len(groups) > 1
-                                      and not self.full_precision) else None
-        if lanes:
-            ready = torch.cuda.Event()
-            ready.record(compute)                 # `out`'s previous readers
-            for _engine, stream in lanes:
-                stream.wait_event(ready)
         first = 0
         ahead = max(1, uploader.slots - 1)   # groups packed ahead of the one being launched
-        try:
-            for number, group in enumerate(groups):
-                while len(submitted) < len(groups) and len(submitted) <= number + ahead - 1:
-                    submit(groups[len(submitted)])
-                slot, total, jobs_of = submitted[number]
-                packed = [result for job in jobs_of for result in job.result()]
-                lane_engine, lane_stream = lanes[number % len(lanes)] if lanes else (engine, compute)
-                # one native call: H2D copy on the copy stream, the lane waits for it
-                inputs = uploader.send_group(slot, total, copies, lane_stream)
-                address = inputs.data_ptr()
-                members = []
-                for offsets, nodes, edges, records, kept in packed:
-                    members.append(engine.pointer_shard(
-                        [address + offset if offset >= 0 else 0 for offset in offsets],
-                        nodes=nodes, edges=edges, records=records,
-                        out=block[first:first + kept], keep=inputs))
-                    first += kept
-                with torch.cuda.stream(lane_stream):
-                    lane_engine.encode_coo_group_pointers(members)
-        except BaseException:
-            _settle([job for _slot, _total, jobs_of in submitted for job in jobs_of])
-            raise
-        finally:
-            if lanes:
-                for _engine, stream in lanes:
-                    done = torch.cuda.Event()
-                    done.record(stream)
-                    compute.wait_event(done)
+        with self._lanes_joined(HOST_FEED_LANES > 1 and len(groups) > 1) as lanes:
+            try:
+                for number, group in enumerate(groups):
+                    while len(submitted) < len(groups) and len(submitted) <= number + ahead - 1:
+                        submit(groups[len(submitted)])
+                    slot, total, jobs_of = submitted[number]
+                    packed = [result for job in jobs_of for result in job.result()]
+                    lane_engine, lane_stream = (lanes[number % len(lanes)] if lanes
+                                                else (engine, compute))
+                    # one native call: H2D copy on the copy stream, the lane waits for it
+                    inputs = uploader.send_group(slot, total, copies, lane_stream)
+                    address = inputs.data_ptr()
+                    members = []
+                    for offsets, nodes, edges, records, kept in packed:
+                        members.append(engine.pointer_shard(
+                            [address + offset if offset >= 0 else 0 for offset in offsets],
+                            nodes=nodes, edges=edges, records=records,
+                            out=block[first:first + kept], keep=inputs))
+                        first += kept
+                    with torch.cuda.stream(lane_stream):
+                        lane_engine.encode_coo_group_pointers(members)
+            except BaseException:
+                _settle([job for _slot, _total, jobs_of in submitted for job in jobs_of])
+                raise
         return block, counts
 
     def encode_graphs_device(self, shard: GraphShard, *,

@@ -725,3 +725,67 @@ def test_a_staging_slot_is_acquired_before_it_is_written_or_replaced(monkeypatch
                         assert uploader._staging[other].numpy().tobytes() == b"\xab" * 4096
                 finally:
                     uploader._ring = None        # (nothing for __del__ to hand to the real library)
+
+
+@pytest.mark.parametrize("shift", [0, 1000])
+def test_pack_and_pack_at_lay_a_slot_out_as_documented(shift, monkeypatch):
+    """The staging layout of ``_Uploader.pack`` and ``pack_at``, each against offsets and bytes
+    worked out here: every array starts on a multiple of 256 bytes (at ``base`` + that for
+    ``pack_at``), ``None`` takes no bytes — ``pack_at`` still records the running offset for it
+    —, ``(array, base, lo, hi)`` goes up as ``array - base``, and nothing else of the slot
+    changes.  Both refuse a value below ``lo`` and one at ``hi`` as the reference refuses an
+    edge that leaves its slice (graph.py:318-321)."""
+    import torch
+    from ginfinity_amd import api
+    from ginfinity_amd.spec import GraphValidationError
+
+    class Slots(api._Uploader):              # (as in the test above, without guards to wait for)
+        def __init__(self):
+            self._device, self.slots, self._next, self._ring = None, 2, 0, None
+            self._staging = [torch.full((8192,), 0xAB, dtype=torch.uint8) for _ in range(2)]
+            self._copied = [None, None]
+
+    real_empty = torch.empty
+    monkeypatch.setattr(torch, "empty",       # (page-locked memory needs a device)
+                        lambda *size, pin_memory=False, **options: real_empty(*size, **options))
+    rng = np.random.default_rng(5)
+    low, high = shift, shift + 700
+    edges = rng.integers(low, high, size=(2, 50)).astype(np.int32)
+    edges[0, 0], edges[1, -1] = low, high - 1                   # both ends of the range
+    arrays = [np.arange(300, dtype=np.int32), None, np.arange(7, dtype=np.uint8) + 1,
+              (edges, np.int32(shift), low, high)]
+    payloads = [arrays[0].tobytes(), None, arrays[2].tobytes(),
+                (edges.astype(np.int64) - shift).astype(np.int32).tobytes()]
+    assert [len(p) for p in payloads if p is not None] == [1200, 7, 400]
+    layout = [0, 1280, 1280, 1536]          # 1200 -> 1280; None: nothing; 7 -> 256; 400 -> 512
+    total, base = 2048, 512
+
+    def expected(first):
+        image = bytearray(b"\xab" * 8192)
+        for payload, offset in zip(payloads, layout):
+            if payload is not None:
+                image[first + offset:first + offset + len(payload)] = payload
+        return bytes(image)
+
+    uploader = Slots()
+    slot, plain, offsets, size = uploader.pack(0, arrays)
+    assert (slot, offsets, size) == (0, layout, total)
+    assert plain[1] is None and [a.nbytes for a in plain if a is not None] == [1200, 7, 400]
+    assert uploader._staging[0].numpy().tobytes() == expected(0)
+    uploader.prepare_slot(1, base + total)
+    assert uploader.pack_at(1, base, arrays) == [base + offset for offset in layout]
+    assert uploader._staging[1].numpy().tobytes() == expected(base)
+    # the same payload bytes from both packers, entry by entry
+    first, second = uploader._staging[0].numpy(), uploader._staging[1].numpy()
+    for payload, offset in zip(payloads, layout):
+        if payload is not None:
+            assert (first[offset:offset + len(payload)].tobytes()
+                    == second[base + offset:base + offset + len(payload)].tobytes() == payload)
+    for row, column, value in ((0, 3, low - 1), (1, 7, high)):
+        broken = edges.copy()
+        broken[row, column] = value
+        refused = arrays[:3] + [(broken, np.int32(shift), low, high)]
+        with pytest.raises(GraphValidationError, match="edge index outside"):
+            uploader.pack(0, refused)
+        with pytest.raises(GraphValidationError, match="edge index outside"):
+            uploader.pack_at(1, base, refused)
