@@ -115,6 +115,9 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_pairwise_topk_window": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
                                          c_int64, c_void_p, c_void_p, c_void_p, c_size_t,
                                          c_void_p]),
+    "gfy_pairwise_topk_ranges": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_size_t, c_void_p]),
 }
 
 

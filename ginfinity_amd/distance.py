@@ -9,7 +9,9 @@ parameters), so the semantics are defined here and in include/gfy.h:
 
 Inputs are fp16 device tensors as produced by ``Ginfinity.encode_graphs_device``;
 products are exact, accumulation is fp32 (MFMA).  ``nearest`` and ``topk`` never
-materialise the N×M matrix.
+materialise the N×M matrix.  ``topk`` and ``nearest`` can leave out a range of rows per row
+(``exclude_ranges``) — in a search over a library of records, each row's own record
+(``exclude_records``, ``record_ranges``).
 """
 from __future__ import annotations
 
@@ -85,8 +87,70 @@ class NearestWorkspace:
         return self.scratch, self.values[:rows], self.indices[:rows]
 
 
+def record_ranges(counts, device=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The rows of every row's own record, for rows grouped in records of ``counts`` rows each
+    (what ``Ginfinity.encode_graphs_device`` returns next to the embeddings): ``(lo, hi)``, int32
+    tensors of length ``sum(counts)`` on ``device`` (default: the host), where row r of record q
+    gets ``[ptr[q], ptr[q + 1])`` and ``ptr`` is the running sum of ``counts``.  Zero counts are
+    allowed; a negative or non-integer count is a ``ValueError``.  The pair is what
+    ``topk(..., exclude_ranges=...)`` takes."""
+    if isinstance(counts, torch.Tensor):
+        counts = counts.detach().cpu().numpy()
+    counts = np.asarray(counts)
+    if counts.size == 0:
+        counts = np.zeros(0, dtype=np.int64)
+    if counts.ndim != 1 or counts.dtype.kind not in "iu":
+        raise ValueError("record counts must be a sequence of integers")
+    counts = counts.astype(np.int64)
+    if np.any(counts < 0):
+        raise ValueError("record counts must not be negative")
+    ptr = np.concatenate(([0], np.cumsum(counts)))
+    if ptr[-1] >= 2 ** 31 - 1:
+        raise ValueError("record counts must sum to fewer than 2^31 - 1 rows")
+    lo = torch.from_numpy(np.repeat(ptr[:-1], counts).astype(np.int32))
+    hi = torch.from_numpy(np.repeat(ptr[1:], counts).astype(np.int32))
+    if device is not None:
+        lo, hi = lo.to(device), hi.to(device)
+    return lo, hi
+
+
+def _checked_ranges(n: int, b_rows: int | None, exclude_ranges, exclude_records, others: bool):
+    """``(lo, hi)`` int32 tensors of length n, wherever they live, from ``exclude_ranges`` or
+    ``exclude_records``; None when neither is given.  ``others``: one of the single-pair
+    exclusions was given too.  No device is touched."""
+    if exclude_ranges is None and exclude_records is None:
+        return None
+    if others or (exclude_ranges is not None and exclude_records is not None):
+        raise ValueError("exclude_ranges, exclude_records, exclude_self, exclude_offset and "
+                         "window_first exclude each other")
+    if exclude_records is not None:
+        if b_rows is not None and b_rows != n:
+            raise ValueError("exclude_records is for self-search: b omitted, or as many rows as a")
+        lo, hi = record_ranges(exclude_records)
+        if lo.numel() != n:
+            raise ValueError(f"exclude_records sums to {lo.numel()} rows, a has {n}")
+        return lo, hi
+    try:
+        lo, hi = exclude_ranges
+    except (TypeError, ValueError):
+        raise ValueError("exclude_ranges must be a pair (lo, hi) of int32 arrays") from None
+    bounds = []
+    for bound in (lo, hi):
+        if isinstance(bound, np.ndarray):
+            if bound.dtype != np.int32:
+                raise ValueError("exclude_ranges must be int32")
+            bound = torch.from_numpy(np.ascontiguousarray(bound))
+        if not isinstance(bound, torch.Tensor) or bound.dtype != torch.int32:
+            raise ValueError("exclude_ranges must be a pair (lo, hi) of int32 arrays")
+        if bound.dim() != 1 or bound.shape[0] != n:
+            raise ValueError(f"exclude_ranges must have shape ({n},): one range per row of a")
+        bounds.append(bound)
+    return tuple(bounds)
+
+
 def nearest(a, b=None, *, metric: str = "l2", exclude_self: bool = False,
             exclude_offset: int | None = None, window_first: int | None = None,
+            exclude_ranges=None, exclude_records=None,
             workspace: NearestWorkspace | None = None
             ) -> tuple[torch.Tensor, torch.Tensor]:
     """For every row of ``a`` the closest row of ``b`` (smallest L2 distance /
@@ -97,7 +161,19 @@ def nearest(a, b=None, *, metric: str = "l2", exclude_self: bool = False,
     ``b`` is rows [k, k + m) of ``a`` and every row skips itself (the cross-shard
     search of a rank's own piece, one call).  A row with every candidate excluded
     gets index -1 and value ``+inf`` (l2) / ``-inf`` (cosine).  With ``workspace`` the returned
-    tensors are views of its buffers, valid until its next use."""
+    tensors are views of its buffers, valid until its next use.
+
+    ``exclude_ranges`` / ``exclude_records`` (see ``topk``) skip a range of rows per row, each
+    row's own record: that search is ``topk`` at k = 1, whose column 0 is returned as ``[n]``
+    views; it takes no ``NearestWorkspace`` (``ValueError``)."""
+    if exclude_ranges is not None or exclude_records is not None:
+        if workspace is not None:
+            raise ValueError("exclude_ranges / exclude_records are served by topk: "
+                             "no NearestWorkspace")
+        values, indices = topk(a, b, k=1, metric=metric, exclude_self=exclude_self,
+                               exclude_offset=exclude_offset, window_first=window_first,
+                               exclude_ranges=exclude_ranges, exclude_records=exclude_records)
+        return values[:, 0], indices[:, 0]
     a = _prepare(a, None)
     b = a if b is None else _prepare(b, a.device)
     if window_first is not None and (exclude_self or exclude_offset is not None):
@@ -160,6 +236,7 @@ def checked_k(k) -> int:
 
 def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
          exclude_offset: int | None = None, window_first: int | None = None,
+         exclude_ranges=None, exclude_records=None,
          workspace: TopKWorkspace | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """For every row of ``a`` the ``k`` best rows of ``b``, smallest L2 distance / largest
     cosine first: ``(values float32 [n, k], indices int32 [n, k])``, exact, the N×M matrix
@@ -173,15 +250,31 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
     ``exclude_offset`` and ``window_first`` are those of ``nearest``; an excluded pair appears
     in no column.  A row with fewer than ``k`` candidates fills its trailing columns with index
     -1 and value ``+inf`` (l2) / ``-inf`` (cosine).  With ``workspace`` the returned tensors
-    are views of its buffers, valid until its next use."""
+    are views of its buffers, valid until its next use.
+
+    ``exclude_ranges=(lo, hi)``, two int32 arrays of length n (numpy or torch, on any device):
+    row i skips the rows ``lo[i] <= j < hi[i]`` of ``b``.  The bounds may hold any value
+    (``lo >= hi`` skips nothing, the comparison clips them to ``b``), rows are independent of each
+    other, and everything above holds unchanged.  ``exclude_records=counts`` is the self-search
+    form (``b`` omitted, or with n rows): the rows are grouped in records of ``counts`` rows, as
+    ``Ginfinity.encode_graphs_device`` returns them, ``sum(counts) == n``, and every row skips its
+    own record, itself included — ``exclude_ranges=record_ranges(counts)``.  The two exclude
+    each other and the three single-pair arguments.  A search whose rows are sorted by record
+    pays for the ranges only under each block's own records; arbitrary ranges are correct and
+    not meant to be fast (include/gfy.h)."""
     k = checked_k(k)
     if window_first is not None and (exclude_self or exclude_offset is not None):
         raise ValueError("window_first excludes the other exclusion arguments")
     code = _metric(metric)
     a = _checked(a)
     b = None if b is None else _checked(b)   # every argument error before a device is touched
+    ranges = _checked_ranges(a.shape[0], None if b is None else b.shape[0], exclude_ranges,
+                             exclude_records,
+                             exclude_self or exclude_offset is not None or window_first is not None)
     a = _prepare(a, None)
     b = a if b is None else _prepare(b, a.device)
+    if ranges is not None:
+        ranges = tuple(bound.to(a.device).contiguous() for bound in ranges)
     if exclude_offset is None:
         exclude_offset = 0 if exclude_self else -1
     lib = native.library()
@@ -197,7 +290,12 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
         stream = torch.cuda.current_stream(a.device).cuda_stream
         if n == 0:
             return values, indices
-        if window_first is None:
+        if ranges is not None:
+            native.check(lib.gfy_pairwise_topk_ranges(
+                a.data_ptr(), n, b.data_ptr(), m, code, k, ranges[0].data_ptr(),
+                ranges[1].data_ptr(), values.data_ptr(), indices.data_ptr(), scratch.data_ptr(),
+                scratch.numel(), stream), "gfy_pairwise_topk_ranges")
+        elif window_first is None:
             native.check(lib.gfy_pairwise_topk(
                 a.data_ptr(), n, b.data_ptr(), m, code, k, int(exclude_offset),
                 values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
@@ -210,4 +308,4 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
     return values, indices
 
 
-__all__ = ["pairwise", "nearest", "NearestWorkspace", "topk", "TopKWorkspace"]
+__all__ = ["pairwise", "nearest", "NearestWorkspace", "topk", "TopKWorkspace", "record_ranges"]

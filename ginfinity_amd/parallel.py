@@ -204,7 +204,7 @@ def _merge_topk(best_value, best_index, values, indices, k: int, metric: str):
 
 
 def cross_shard_topk(block: torch.Tensor, k: int, *, metric: str = "l2", group=None,
-                     chunk_rows: int = 1 << 20, search=None
+                     chunk_rows: int = 1 << 20, search=None, record_counts=None
                      ) -> tuple[torch.Tensor, torch.Tensor, list[int]]:
     """The ``k`` nearest other embeddings, over ALL ranks' rows, of every local row.
 
@@ -216,6 +216,13 @@ def cross_shard_topk(block: torch.Tensor, k: int, *, metric: str = "l2", group=N
     row.  A row with fewer than ``k`` other rows in the whole world fills its trailing columns
     with row -1 and value ``+inf`` (l2) / ``-inf`` (cosine).  A rank without rows takes part
     in the collectives and returns empty results.
+
+    ``record_counts``: the rank's own rows are grouped in records of that many rows each (the
+    counts ``encode_owned_shards`` returns, flattened; they sum to the rank's rows, and a record
+    never spans ranks since shards are whole), and every row skips its whole own record, itself
+    included, instead of itself alone: the rank's own pieces are searched with
+    ``exclude_ranges`` (``distance.record_ranges``, built once per call and shifted to the piece)
+    instead of ``window_first``; the other ranks' pieces as before.
 
     The merged order is that of the VALUES, not of the kernel's keys.  ``distance.topk`` orders
     a row by (fp32 key, row), and two pairs with different keys can round to the same fp32 value
@@ -239,6 +246,11 @@ def cross_shard_topk(block: torch.Tensor, k: int, *, metric: str = "l2", group=N
     rank, size = world(group)
     rows = int(block.shape[0])
     device = block.device
+    own = None
+    if record_counts is not None:
+        own = distance.record_ranges(record_counts, device)    # once: every own piece shifts it
+        if own[0].numel() != rows:
+            raise ValueError(f"record_counts sums to {own[0].numel()} rows, the block has {rows}")
     if size > 1:
         mine = torch.tensor([rows], dtype=torch.int64, device=device)
         everyone = torch.empty(size, dtype=torch.int64, device=device)
@@ -285,8 +297,10 @@ def cross_shard_topk(block: torch.Tensor, k: int, *, metric: str = "l2", group=N
             piece = (staging[chunk % len(staging)][other, :valid] if size > 1
                      else block[first:first + valid])
             extra = {} if workspace is None else {"workspace": workspace}
-            if other == rank:
+            if other == rank and own is None:
                 extra["window_first"] = first
+            elif other == rank:      # in the piece's row numbers; subsumes the self-exclusion
+                extra["exclude_ranges"] = (own[0] - first, own[1] - first)
             values, indices = search(block, piece, k=k, metric=metric, **extra)
             indices = indices.to(torch.int64)
             indices = torch.where(indices < 0, _NO_ROW, indices + (offsets[other] + first))

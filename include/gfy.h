@@ -478,6 +478,27 @@ int gfy_pairwise_topk_window(const void* a, int64_t n, const void* b, int64_t m,
                              int k, int64_t window_first, float* top_val, int32_t* top_idx,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same with a half-open range of b-rows excluded per a-row — in a self-search over rows
+ * grouped in records, each row's own record: the pair (i, j) is excluded iff
+ * skip_lo[i] <= j < skip_hi[i].
+ *   skip_lo, skip_hi int32 [n], device memory; NULL is GFY_ERR_INVALID before any launch.
+ *   They may hold any value: lo >= hi excludes nothing, and bounds below 0 or above m are
+ *   clipped by the comparison itself.  The ranges of different rows are independent: they need
+ *   not be sorted, nested or disjoint, and a row's result depends neither on the other rows of
+ *   the call nor on their ranges.
+ *   Everything else — keys, order by (key, b-row index), no index twice, -1 and +inf / -inf
+ *   behind the last candidate, the prefix property, the argument checks, the workspace and its
+ *   size (gfy_pairwise_topk_workspace_bytes) — is that of gfy_pairwise_topk.  skip_lo[i] = i + c,
+ *   skip_hi[i] = i + c + 1 is exclude_offset = c (window_first = -c) bit for bit.
+ *   Cost: a workgroup (128 a-rows) takes the unchanged path in every b-tile that does not meet
+ *   the union [min lo, max hi) of its rows' non-empty ranges, and masks in the tiles that do.
+ *   Rows sorted by record in a self-search mask in the few tiles under their own records;
+ *   arbitrary ranges may mask in every tile, which is correct and not meant to be fast.       */
+int gfy_pairwise_topk_ranges(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
+                             const int32_t* skip_lo, const int32_t* skip_hi,
+                             float* top_val, int32_t* top_idx,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

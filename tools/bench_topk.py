@@ -13,7 +13,13 @@ device.  The document names the run: host, UTC time, device, ROCm / torch versio
 kernel sources that were measured.  Writes one JSON document (default
 profiles/topk_bench.json) and prints it.
 
+``--records MEAN`` adds a leg per metric and k: the same rows cut into records of about MEAN
+rows (sizes uniform in 1 .. 2 MEAN - 1, seed 0), searched with ``exclude_records`` and, next
+to it in the same run, with ``exclude_self``; both times and their ratio are written, no ratio
+is expected in advance.
+
     python tools/bench_topk.py --rows 1000000
+    python tools/bench_topk.py --rows 1000000 --records 300
 """
 from __future__ import annotations
 
@@ -27,6 +33,7 @@ import subprocess
 import sys
 from pathlib import Path
 
+import numpy as np
 import torch
 
 ROOT = Path(__file__).resolve().parents[1]
@@ -34,7 +41,8 @@ sys.path.insert(0, str(ROOT))
 from ginfinity_amd import distance, synthetic  # noqa: E402
 
 DENSE_ROWS = 4_096
-KERNEL_SOURCES = ("pairwise.hip", "pairwise_topk.hip", "gfy_common.h", "gfy_api.hip")
+KERNEL_SOURCES = ("pairwise.hip", "pairwise_topk.hip", "pairwise_topk.inc",
+                  "pairwise_topk_ranges.hip", "gfy_common.h", "gfy_api.hip")
 
 
 def _commit() -> str | None:
@@ -73,6 +81,17 @@ def _span(seconds: list[float]) -> dict:
             "runs": seconds}
 
 
+def _record_counts(rows: int, mean: int) -> list[int]:
+    """Record sizes uniform in 1 .. 2 mean - 1 that sum to ``rows`` (the last one cut short)."""
+    sizes = np.random.default_rng(0).integers(1, 2 * mean, size=2 * rows // mean + 16)
+    ends = np.cumsum(sizes)
+    keep = int(np.searchsorted(ends, rows))
+    counts = sizes[:keep + 1].copy()
+    counts[keep] -= ends[keep] - rows
+    assert counts.sum() == rows and counts.min() >= 0
+    return [int(c) for c in counts]
+
+
 def main() -> None:
     parser = argparse.ArgumentParser()
     parser.add_argument("--rows", type=int, default=1_000_000)
@@ -81,10 +100,14 @@ def main() -> None:
     parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
     parser.add_argument("--dense-blocks", type=int, default=8)
     parser.add_argument("--ks", default="1,4,8,16")
+    parser.add_argument("--records", type=int, default=0, metavar="MEAN",
+                        help="also time exclude_records over records of about MEAN rows")
     parser.add_argument("--out", default=str(ROOT / "profiles" / "topk_bench.json"))
     args = parser.parse_args()
     if args.dense_blocks < 8:
         parser.error("--dense-blocks: at least 8")
+    if args.records < 0:
+        parser.error("--records: a positive mean")
     ks = [int(k) for k in args.ks.split(",")]
     rows = torch.from_numpy(synthetic.unit_rows(0, args.rows)).cuda()
     n = args.rows
@@ -99,6 +122,11 @@ def main() -> None:
               "repeats": args.repeats, "warmup": args.warmup, "ratios_use": "median",
               "dense_rows_per_block": DENSE_ROWS, "dense_blocks_timed": args.dense_blocks,
               "distances": {}}
+    counts = _record_counts(n, args.records) if args.records else None
+    if counts is not None:
+        result["records"] = {"mean_rows_asked": args.records, "records": len(counts),
+                             "largest": max(counts), "sizes": "uniform in 1 .. 2 mean - 1, seed 0"}
+        ranges = distance.record_ranges(counts, rows.device)     # on the device: not in the times
     for metric in ("l2", "cosine"):
         nearest = _timed(lambda: distance.nearest(rows, metric=metric, exclude_self=True),
                          args.repeats, args.warmup)
@@ -131,6 +159,20 @@ def main() -> None:
             print(f"{metric} k={k}: topk {mid:.4f} s, {mid / mid_nearest:.2f} x nearest, dense "
                   f"route {mid_dense:.2f} s = {mid_dense / mid:.1f} x topk", file=sys.stderr,
                   flush=True)
+            if counts is not None:   # the same rows, the same k, one after the other in this run
+                beside = _timed(lambda: distance.topk(rows, k=k, metric=metric, exclude_self=True,
+                                                      workspace=workspace),
+                                args.repeats, args.warmup)
+                records = _timed(lambda: distance.topk(rows, k=k, metric=metric,
+                                                       exclude_ranges=ranges, workspace=workspace),
+                                 args.repeats, args.warmup)
+                ratio = statistics.median(records) / statistics.median(beside)
+                entry["topk"][str(k)]["records"] = {
+                    "exclude_records_seconds": _span(records),
+                    "exclude_self_seconds": _span(beside),
+                    "exclude_records_over_exclude_self": ratio}
+                print(f"{metric} k={k}: exclude_records {statistics.median(records):.4f} s = "
+                      f"{ratio:.3f} x exclude_self", file=sys.stderr, flush=True)
         result["distances"][metric] = entry
     text = json.dumps(result, indent=1)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)

@@ -2,6 +2,7 @@
 # Registers / spills of the pairwise kernels as hipcc allocates them (no GPU needed):
 #   bash tools/pairwise_resources.sh [extra hipcc flags]
 #   GFY_SOURCE=pairwise_topk.hip bash tools/pairwise_resources.sh     # the top-k kernels
+#   GFY_SOURCE=pairwise_topk_ranges.hip bash tools/pairwise_resources.sh   # ... with per-row ranges
 # The assembly is left in $GFY_ASM_OUT (default /tmp/<source stem>.s, i.e. /tmp/pairwise.s).
 set -e
 cd "$(dirname "$0")/../ginfinity_amd/csrc"
