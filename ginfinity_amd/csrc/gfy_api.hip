@@ -1035,7 +1035,7 @@ int gfy_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int me
   GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_MAX, GFY_ERR_INVALID,
               "gfy_pairwise_topk: k = %d outside 1..%d", k, GFY_PAIRWISE_TOPK_MAX);
   return launch_pairwise_topk(a, n, b, m, metric, k, exclude_offset, exclude_offset >= 0 ? 1 : 0,
-                              nullptr, nullptr, top_val, top_idx, ws, ws_bytes,
+                              nullptr, nullptr, nullptr, nullptr, top_val, top_idx, ws, ws_bytes,
                               (hipStream_t)stream);
 }
 
@@ -1052,8 +1052,8 @@ int gfy_pairwise_topk_window(const void* a, int64_t n, const void* b, int64_t m,
   GFY_REQUIRE(window_first >= 0 && window_first + m <= n, GFY_ERR_INVALID,
               "gfy_pairwise_topk_window: b must be rows [%lld, %lld) of the %lld rows of a",
               (long long)window_first, (long long)(window_first + m), (long long)n);
-  return launch_pairwise_topk(a, n, b, m, metric, k, -window_first, 1, nullptr, nullptr, top_val,
-                              top_idx, ws, ws_bytes, (hipStream_t)stream);
+  return launch_pairwise_topk(a, n, b, m, metric, k, -window_first, 1, nullptr, nullptr, nullptr,
+                              nullptr, top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int gfy_pairwise_topk_ranges(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
@@ -1068,8 +1068,28 @@ int gfy_pairwise_topk_ranges(const void* a, int64_t n, const void* b, int64_t m,
               "gfy_pairwise_topk_ranges: k = %d outside 1..%d", k, GFY_PAIRWISE_TOPK_MAX);
   GFY_REQUIRE(skip_lo && skip_hi, GFY_ERR_INVALID,
               "gfy_pairwise_topk_ranges: skip_lo or skip_hi is NULL");
-  return launch_pairwise_topk(a, n, b, m, metric, k, 0, 0, skip_lo, skip_hi, top_val, top_idx, ws,
-                              ws_bytes, (hipStream_t)stream);
+  return launch_pairwise_topk(a, n, b, m, metric, k, 0, 0, skip_lo, skip_hi, nullptr, nullptr,
+                              top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_pairwise_topk_distinct(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
+                               const int32_t* skip_lo, const int32_t* skip_hi,
+                               const int32_t* group_lo, const int32_t* group_hi, float* top_val,
+                               int32_t* top_idx, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  GFY_REQUIRE(a && b && top_val && top_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
+              GFY_ERR_INVALID, "gfy_pairwise_topk_distinct: bad arguments");
+  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
+              "gfy_pairwise_topk_distinct: unknown metric %d", metric);
+  GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_DISTINCT_MAX, GFY_ERR_INVALID,
+              "gfy_pairwise_topk_distinct: k = %d outside 1..%d", k,
+              GFY_PAIRWISE_TOPK_DISTINCT_MAX);
+  GFY_REQUIRE(skip_lo && skip_hi, GFY_ERR_INVALID,
+              "gfy_pairwise_topk_distinct: skip_lo or skip_hi is NULL");
+  GFY_REQUIRE(group_lo && group_hi, GFY_ERR_INVALID,
+              "gfy_pairwise_topk_distinct: group_lo or group_hi is NULL");
+  return launch_pairwise_topk(a, n, b, m, metric, k, 0, 0, skip_lo, skip_hi, group_lo, group_hi,
+                              top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -359,11 +359,13 @@ int launch_pairwise_row_terms(const void* rows, int64_t count, int64_t padded, i
                               int fold, float* s_out, float* t_out, float* a_term,
                               hipStream_t s);
 // pairwise_topk.hip; skip_lo / skip_hi (both or neither, [n] each): per-row ranges instead of
-// the excluded pair (the sweep of pairwise_topk_ranges.hip)
+// the excluded pair (the sweep of pairwise_topk_ranges.hip); group_lo / group_hi (both or
+// neither, [m] each, with the ranges): one hit per record of b (pairwise_topk_distinct.hip)
 int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
                          int64_t exclude_offset, int exclude_on, const int32_t* skip_lo,
-                         const int32_t* skip_hi, float* top_val, int32_t* top_idx, void* ws,
-                         size_t ws_bytes, hipStream_t s);
+                         const int32_t* skip_hi, const int32_t* group_lo, const int32_t* group_hi,
+                         float* top_val, int32_t* top_idx, void* ws, size_t ws_bytes,
+                         hipStream_t s);
 size_t pairwise_topk_workspace_bytes(int64_t n, int64_t m, int k);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------

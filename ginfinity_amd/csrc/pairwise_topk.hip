@@ -32,6 +32,9 @@
 // max16 — two LDS words, 16 x (subtract, compare, select).  For record-sorted self-search that
 // is the few tiles under the block's own records; for arbitrary ranges it may be every tile,
 // which is correct and is not meant to be fast.
+//
+// One hit per record of b (gfy_pairwise_topk_distinct): the kDistinct instantiations and their
+// finish kernel, told at the head of pairwise_topk_distinct.hip.
 #include "gfy_common.h"
 #include "pairwise_topk.inc"
 
@@ -137,8 +140,9 @@ size_t pairwise_topk_workspace_bytes(int64_t n, int64_t m, int k) {
 
 int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
                          int64_t exclude_offset, int exclude_on, const int32_t* skip_lo,
-                         const int32_t* skip_hi, float* top_val, int32_t* top_idx, void* ws,
-                         size_t ws_bytes, hipStream_t s) {
+                         const int32_t* skip_hi, const int32_t* group_lo, const int32_t* group_hi,
+                         float* top_val, int32_t* top_idx, void* ws, size_t ws_bytes,
+                         hipStream_t s) {
   const TopkWorkspace w = carve_topk(ws, n, m, k);
   GFY_REQUIRE(ws_bytes >= w.bytes, GFY_ERR_WORKSPACE,
               "gfy_pairwise_topk: workspace %zu < required %zu", ws_bytes, w.bytes);
@@ -165,6 +169,12 @@ int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int
   p.part_idx = w.part_idx;
   p.skip_lo = skip_lo;
   p.skip_hi = skip_hi;
+  p.group_lo = group_lo;
+  p.group_hi = group_hi;
+  if (group_lo) {   // one hit per record of b: sweep and finish of pairwise_topk_distinct.hip
+    if (const int rc = launch_topk_sweep_distinct(p, fold, s)) return rc;
+    return launch_topk_finish_distinct(p, w.a_term, metric, top_val, top_idx, s);
+  }
   int rc;
   if (skip_lo) rc = launch_topk_sweep_ranges(p, fold, s);   // per-row ranges: pairwise_topk_ranges.hip
   else if (k <= 4) rc = fold ? launch_sweep<4, true, false>(p, s) : launch_sweep<4, false, false>(p, s);

@@ -1,8 +1,10 @@
-// The sweep of the exact top-k search: k_pairwise_topk<D, kFold, kRanges> and its launcher
-// (the design is told at the head of pairwise_topk.hip).  Included by the two translation units
-// that instantiate it: pairwise_topk.hip (kRanges = false: one excluded pair per a-row at most)
-// and pairwise_topk_ranges.hip (kRanges = true: an excluded range of b-rows per a-row), so that
-// the device code of the one does not move with the other.
+// The sweep of the exact top-k search: k_pairwise_topk<D, kFold, kRanges, kDistinct> and its
+// launcher (the design is told at the head of pairwise_topk.hip).
+// Included by the three translation units that instantiate it: pairwise_topk.hip (kRanges =
+// false: one excluded pair per a-row at most), pairwise_topk_ranges.hip (kRanges = true: an
+// excluded range of b-rows per a-row) and pairwise_topk_distinct.hip (kDistinct = true: at most
+// one hit per record of b, told at its head), so that the device code of the one does not move
+// with the others.
 
 namespace gfy {
 
@@ -21,10 +23,17 @@ struct TopkArgs {
   int32_t* part_idx;
   const int32_t* skip_lo;   // kRanges: a-row i skips the b-rows [skip_lo[i], skip_hi[i]), [n] each
   const int32_t* skip_hi;
+  const int32_t* group_lo;  // kDistinct: b-row j lies in the record [group_lo[j], group_hi[j]), [m] each
+  const int32_t* group_hi;
 };
 
 // pairwise_topk_ranges.hip: the sweep with per-row ranges, list depth from p.k
 int launch_topk_sweep_ranges(const TopkArgs& p, bool fold, hipStream_t s);
+// pairwise_topk_distinct.hip: the sweep that keeps one entry per record of b (p.group_lo,
+// p.group_hi; exclusions as ranges), and the merge of the chunks' lists that does the same
+int launch_topk_sweep_distinct(const TopkArgs& p, bool fold, hipStream_t s);
+int launch_topk_finish_distinct(const TopkArgs& p, const float* a_term, int metric, float* top_val,
+                                int32_t* top_idx, hipStream_t s);
 
 namespace {
 
@@ -37,6 +46,8 @@ constexpr int kTermBytes = 2 * kTileB * 4;     // its (s, t)
 constexpr int kTermSlots = 4;                  // (s, t) ring, like the rows
 constexpr int kTopkLds = kBuffers * kRowBytes + kTermSlots * kTermBytes;
 constexpr int kRangeBytes = kBlockA * 8;       // kRanges: (first, count) of every a-row, behind the rings
+constexpr int kGroupBytes = 2 * kTileB * 4;    // kDistinct: (group_lo, group_hi) of a b-tile, a
+constexpr int kGroupSlots = 4;                 // ring like that of the terms, behind the ranges
 constexpr int kHolders = 8;                    // lists per a-row at the end of a sweep
 constexpr int kNoIndex = 0x7fffffff;
 static_assert(kHolders * GFY_PAIRWISE_TOPK_MAX * kBlockA * 8 <= kBuffers * kRowBytes,
@@ -78,6 +89,43 @@ __device__ __forceinline__ void list_insert(float (&lk)[D], int (&li)[D], float 
   }
 }
 
+// The same for a list that holds at most one entry per record, (ck, ci) being a row of the
+// record [first, first + count): an entry of that record in front of the place (ck, ci) would
+// take is at least as good and was met earlier (lower index), so the candidate is dropped; one
+// behind it is worse and is what leaves the list — the entries between the two move one place
+// down, everything behind stays.  An empty entry (kNoIndex) lies in no record: first + count <=
+// m <= kNoIndex.
+template <int D>
+__device__ __forceinline__ void list_insert_distinct(float (&lk)[D], int (&li)[D], float ck, int ci,
+                                                     int first, int count) {
+  bool ahead = false, live = true;
+#pragma unroll
+  for (int p = 0; p < D; ++p) {
+    const bool same = (uint32_t)(li[p] - first) < (uint32_t)count;
+    ahead = ahead || ck > lk[p];
+    const bool write = ahead && live;
+    const float nk = write ? lk[p] : ck;
+    const int ni = write ? li[p] : ci;
+    lk[p] = write ? ck : lk[p];
+    li[p] = write ? ci : li[p];
+    ck = nk;
+    ci = ni;
+    live = live && !same;
+  }
+}
+
+// LDS-DMA of one dword per lane (global_load_lds_dword): lane L copies 4 bytes from gbase + goff
+// to LDS address lds + 4 L; otherwise dma16 of gfy_common.h
+__device__ __forceinline__ void dma4(const void* gbase /* uniform */, uint32_t goff, uint32_t lds) {
+  asm volatile(
+      "s_mov_b32 m0, %0\n\t"
+      "s_nop 0\n\t"
+      "global_load_lds_dword %1, %2"
+      :
+      : "s"(__builtin_amdgcn_readfirstlane(lds)), "v"(goff), "s"(gbase)
+      : "memory");
+}
+
 __device__ __forceinline__ float max16(const f32x16& g) {
   float high = __builtin_fmaxf(g[0], g[1]);
 #pragma unroll
@@ -86,8 +134,9 @@ __device__ __forceinline__ float max16(const f32x16& g) {
   return high;
 }
 
-template <int D, bool kFold, bool kRanges>
+template <int D, bool kFold, bool kRanges, bool kDistinct>
 __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p) {
+  static_assert(kRanges || !kDistinct, "the distinct sweep takes its exclusions as ranges");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
@@ -133,6 +182,20 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
       dma16(uniform_pointer((wave == 0 && !kFold ? p.s : p.t) + j0), (me & 31u) * 16u,
             lds0 + kBuffers * kRowBytes + (uint32_t)(k & (kTermSlots - 1)) * kTermBytes
                 + (uint32_t)(kFold ? 1 : wave) * (kTileB * 4));
+    if constexpr (kDistinct) {
+      // the records of the tile's rows, behind the ranges: waves 4 .. 7 bring group_lo[0, 64),
+      // group_lo[64, 128), group_hi[0, 64) and group_hi[64, 128), a dword per lane.  The arrays
+      // end at m: the rows of a ragged tile past it re-read the last row's (their t never wins).
+      if (wave >= 4) {
+        const int part = wave - 4;
+        const int last = (int)(p.m - 1 - j0);
+        const int row = 64 * (part & 1) + (int)(me & 63u);
+        dma4(uniform_pointer((part < 2 ? p.group_lo : p.group_hi) + j0),
+             (uint32_t)(row < last ? row : last) * 4u,
+             lds0 + kTopkLds + kRangeBytes + (uint32_t)(k & (kGroupSlots - 1)) * kGroupBytes
+                 + (uint32_t)part * 256u);
+      }
+    }
   };
 
   // stage the a-block through LDS once (coalesced), then keep all its fragments in registers
@@ -292,6 +355,15 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
         int first = 15;                     // lowest position holding the maximum
 #pragma unroll
         for (int q = 14; q >= 0; --q) first = g[q] == high ? q : first;
+        if constexpr (kDistinct) {
+          // only now the candidate's record is looked at: two words of the tile's ring
+          const int* lo_l = reinterpret_cast<const int*>(
+              smem + kTopkLds + kRangeBytes + (k & (kGroupSlots - 1)) * kGroupBytes);
+          const int in_tile = jw + 8 * (first >> 2) + (first & 3);
+          const int from = lo_l[in_tile];
+          list_insert_distinct<D>(lk[at], li[at], better ? high : -__builtin_inff(),
+                                  (int)j0 + in_tile, from, lo_l[kTileB + in_tile] - from);
+        } else
         list_insert<D>(lk[at], li[at], better ? high : -__builtin_inff(),
                        jb + 8 * (first >> 2) + (first & 3));
         const int taken = better ? first : -1;
@@ -339,6 +411,49 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
     uint64_t heads = 0;   // 8 bits per holder: entries taken from its list
     float* out_key = p.part_key + ((int64_t)chunk * p.n + a0 + t) * p.k;
     int32_t* out_idx = p.part_idx + ((int64_t)chunk * p.n + a0 + t) * p.k;
+    if constexpr (kDistinct) {
+      // the best head is taken unless a column already holds a row of its record (looked up
+      // where the caller keeps it: a record may lie in several holders' lists, its best row
+      // comes first); `taken` is indexed by unrolled positions only, so it stays in registers
+      int taken[D];
+#pragma unroll
+      for (int q = 0; q < D; ++q) taken[q] = kNoIndex;
+      int c = 0;
+      for (int step = 0; step < kHolders * D && c < p.k; ++step) {
+        float bk = -__builtin_inff();
+        int bi = kNoIndex, bh = 0;
+#pragma unroll
+        for (int h = 0; h < kHolders; ++h) {
+          const int pos = (int)((heads >> (8 * h)) & 0xffu);
+          if (pos < D) {
+            const float hk = m_key[(h * D + pos) * kBlockA + t];
+            const int hi = m_idx[(h * D + pos) * kBlockA + t];
+            if (hk > bk || (hk == bk && hi < bi)) {
+              bk = hk;
+              bi = hi;
+              bh = h;
+            }
+          }
+        }
+        if (bi == kNoIndex) break;   // every list is at its end or at its empty entries
+        heads += 1ull << (8 * bh);
+        const int from = p.group_lo[bi], count = p.group_hi[bi] - from;
+        bool seen = false;
+#pragma unroll
+        for (int q = 0; q < D; ++q) seen = seen || (uint32_t)(taken[q] - from) < (uint32_t)count;
+        if (!seen) {
+          out_key[c] = kFold ? -2.0f * bk : -bk;
+          out_idx[c] = bi;
+#pragma unroll
+          for (int q = 0; q < D; ++q) taken[q] = q == c ? bi : taken[q];
+          ++c;
+        }
+      }
+      for (; c < p.k; ++c) {
+        out_key[c] = __builtin_inff();
+        out_idx[c] = kNoIndex;
+      }
+    } else
     for (int c = 0; c < p.k; ++c) {
       float bk = -__builtin_inff();
       int bi = kNoIndex, bh = 0;
@@ -362,18 +477,20 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
   }
 }
 
-template <int D, bool kFold, bool kRanges>
+template <int D, bool kFold, bool kRanges, bool kDistinct = false>
 int launch_sweep(const TopkArgs& p, hipStream_t s) {
-  constexpr int kLds = kTopkLds + (kRanges ? kRangeBytes : 0);
+  constexpr int kLds = kTopkLds + (kRanges ? kRangeBytes : 0)
+                       + (kDistinct ? kGroupSlots * kGroupBytes : 0);
+  static_assert(kLds <= 160 * 1024, "the LDS of a compute unit");
   static PerDeviceOnce opt_in;   // > 64 KB of dynamic LDS: once per device (gfy_common.h)
   if (const int rc = opt_in.run([]() -> int {
         GFY_CHECK_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&k_pairwise_topk<D, kFold, kRanges>),
+            reinterpret_cast<const void*>(&k_pairwise_topk<D, kFold, kRanges, kDistinct>),
             hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
         return GFY_OK;
       }))
     return rc;
-  k_pairwise_topk<D, kFold, kRanges><<<p.blocks_a * p.chunks, kThreads, kLds, s>>>(p);
+  k_pairwise_topk<D, kFold, kRanges, kDistinct><<<p.blocks_a * p.chunks, kThreads, kLds, s>>>(p);
   return GFY_OK;
 }
 

@@ -11,7 +11,8 @@ Inputs are fp16 device tensors as produced by ``Ginfinity.encode_graphs_device``
 products are exact, accumulation is fp32 (MFMA).  ``nearest`` and ``topk`` never
 materialise the N×M matrix.  ``topk`` and ``nearest`` can leave out a range of rows per row
 (``exclude_ranges``) — in a search over a library of records, each row's own record
-(``exclude_records``, ``record_ranges``).
+(``exclude_records``, ``record_ranges``) — and can return at most one row per record
+(``distinct_records``, ``record_of``).
 """
 from __future__ import annotations
 
@@ -87,13 +88,8 @@ class NearestWorkspace:
         return self.scratch, self.values[:rows], self.indices[:rows]
 
 
-def record_ranges(counts, device=None) -> tuple[torch.Tensor, torch.Tensor]:
-    """The rows of every row's own record, for rows grouped in records of ``counts`` rows each
-    (what ``Ginfinity.encode_graphs_device`` returns next to the embeddings): ``(lo, hi)``, int32
-    tensors of length ``sum(counts)`` on ``device`` (default: the host), where row r of record q
-    gets ``[ptr[q], ptr[q + 1])`` and ``ptr`` is the running sum of ``counts``.  Zero counts are
-    allowed; a negative or non-integer count is a ``ValueError``.  The pair is what
-    ``topk(..., exclude_ranges=...)`` takes."""
+def _checked_counts(counts) -> np.ndarray:
+    """Record sizes as a non-negative int64 array; ``ValueError`` ("record counts ...") else."""
     if isinstance(counts, torch.Tensor):
         counts = counts.detach().cpu().numpy()
     counts = np.asarray(counts)
@@ -104,6 +100,17 @@ def record_ranges(counts, device=None) -> tuple[torch.Tensor, torch.Tensor]:
     counts = counts.astype(np.int64)
     if np.any(counts < 0):
         raise ValueError("record counts must not be negative")
+    return counts
+
+
+def record_ranges(counts, device=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The rows of every row's own record, for rows grouped in records of ``counts`` rows each
+    (what ``Ginfinity.encode_graphs_device`` returns next to the embeddings): ``(lo, hi)``, int32
+    tensors of length ``sum(counts)`` on ``device`` (default: the host), where row r of record q
+    gets ``[ptr[q], ptr[q + 1])`` and ``ptr`` is the running sum of ``counts``.  Zero counts are
+    allowed; a negative or non-integer count is a ``ValueError``.  The pair is what
+    ``topk(..., exclude_ranges=...)`` takes."""
+    counts = _checked_counts(counts)
     ptr = np.concatenate(([0], np.cumsum(counts)))
     if ptr[-1] >= 2 ** 31 - 1:
         raise ValueError("record counts must sum to fewer than 2^31 - 1 rows")
@@ -112,6 +119,22 @@ def record_ranges(counts, device=None) -> tuple[torch.Tensor, torch.Tensor]:
     if device is not None:
         lo, hi = lo.to(device), hi.to(device)
     return lo, hi
+
+
+def record_of(indices, counts) -> torch.Tensor:
+    """The record number of every index that ``topk`` / ``nearest`` returned, for rows grouped in
+    records of ``counts`` rows each: an int32 tensor of the shape of ``indices`` on its device
+    (a numpy array gives a host tensor), -1 where the index is -1.  A row at a boundary belongs
+    to the record that starts there; a record of zero rows owns nothing.  ``counts`` is checked
+    as ``record_ranges`` checks it."""
+    counts = _checked_counts(counts)
+    if not isinstance(indices, torch.Tensor):
+        indices = torch.from_numpy(np.ascontiguousarray(indices))
+    ends = torch.from_numpy(np.cumsum(counts)).to(indices.device)
+    # the first record whose end lies behind the row: empty records end where they start
+    found = torch.searchsorted(ends, indices.to(torch.int64), right=True)
+    outside = (indices < 0) | (found >= ends.numel())
+    return torch.where(outside, torch.full_like(found, -1), found).to(torch.int32)
 
 
 def _checked_ranges(n: int, b_rows: int | None, exclude_ranges, exclude_records, others: bool):
@@ -236,7 +259,7 @@ def checked_k(k) -> int:
 
 def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
          exclude_offset: int | None = None, window_first: int | None = None,
-         exclude_ranges=None, exclude_records=None,
+         exclude_ranges=None, exclude_records=None, distinct_records=None,
          workspace: TopKWorkspace | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """For every row of ``a`` the ``k`` best rows of ``b``, smallest L2 distance / largest
     cosine first: ``(values float32 [n, k], indices int32 [n, k])``, exact, the N×M matrix
@@ -261,8 +284,24 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
     own record, itself included — ``exclude_ranges=record_ranges(counts)``.  The two exclude
     each other and the three single-pair arguments.  A search whose rows are sorted by record
     pays for the ranges only under each block's own records; arbitrary ranges are correct and
-    not meant to be fast (include/gfy.h)."""
+    not meant to be fast (include/gfy.h).
+
+    ``distinct_records=counts_b``: the rows of ``b`` are grouped in contiguous records of
+    ``counts_b`` rows (integers, ``sum(counts_b) == m``), and at most one row per record is
+    returned: the ``k`` best rows that lie in ``k`` different records.  A record's representative
+    for row i is its non-excluded row that is first in the order (key, b-row index); the result
+    is the ``k`` best representatives in that order; a record with every row excluded has none.
+    Keys, values, the -1 / ``inf`` columns behind the last record that has a representative, the
+    prefix property and the independence of rows are as above, and with records of one row each
+    the result is the one without the argument bit for bit.  It combines with every exclusion
+    (the single-pair ones become ranges on the host); the search for the molecules that resemble
+    each position is ``topk(rows, k=8, exclude_records=counts, distinct_records=counts)``, and
+    ``record_of(indices, counts)`` names the records found.  ``k`` is at most
+    ``GFY_PAIRWISE_TOPK_DISTINCT_MAX`` (16)."""
     k = checked_k(k)
+    if distinct_records is not None and k > native.GFY_PAIRWISE_TOPK_DISTINCT_MAX:
+        raise ValueError("k must be an integer in 1.."
+                         f"{native.GFY_PAIRWISE_TOPK_DISTINCT_MAX} with distinct_records")
     if window_first is not None and (exclude_self or exclude_offset is not None):
         raise ValueError("window_first excludes the other exclusion arguments")
     code = _metric(metric)
@@ -271,10 +310,27 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
     ranges = _checked_ranges(a.shape[0], None if b is None else b.shape[0], exclude_ranges,
                              exclude_records,
                              exclude_self or exclude_offset is not None or window_first is not None)
+    groups = None
+    if distinct_records is not None:
+        n, m = a.shape[0], a.shape[0] if b is None else b.shape[0]
+        groups = record_ranges(distinct_records)
+        if groups[0].numel() != m:
+            raise ValueError(f"distinct_records sums to {groups[0].numel()} rows, b has {m}")
+        if ranges is None:   # the single-pair exclusions (or none) as ranges of one row (or none)
+            if window_first is not None:
+                skip = -int(window_first)
+            else:
+                skip = 0 if exclude_self and exclude_offset is None else exclude_offset
+            lo = torch.arange(n, dtype=torch.int64) + (0 if skip is None else int(skip))
+            hi = lo + (0 if skip is None or (window_first is None and skip < 0) else 1)
+            # a pair outside b excludes nothing; clamped so that the bounds fit int32
+            ranges = tuple(bound.clamp(-1, 2 ** 31 - 1).to(torch.int32) for bound in (lo, hi))
     a = _prepare(a, None)
     b = a if b is None else _prepare(b, a.device)
     if ranges is not None:
         ranges = tuple(bound.to(a.device).contiguous() for bound in ranges)
+    if groups is not None:
+        groups = tuple(bound.to(a.device) for bound in groups)
     if exclude_offset is None:
         exclude_offset = 0 if exclude_self else -1
     lib = native.library()
@@ -290,7 +346,13 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
         stream = torch.cuda.current_stream(a.device).cuda_stream
         if n == 0:
             return values, indices
-        if ranges is not None:
+        if groups is not None:
+            native.check(lib.gfy_pairwise_topk_distinct(
+                a.data_ptr(), n, b.data_ptr(), m, code, k, ranges[0].data_ptr(),
+                ranges[1].data_ptr(), groups[0].data_ptr(), groups[1].data_ptr(),
+                values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                stream), "gfy_pairwise_topk_distinct")
+        elif ranges is not None:
             native.check(lib.gfy_pairwise_topk_ranges(
                 a.data_ptr(), n, b.data_ptr(), m, code, k, ranges[0].data_ptr(),
                 ranges[1].data_ptr(), values.data_ptr(), indices.data_ptr(), scratch.data_ptr(),
@@ -308,4 +370,5 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
     return values, indices
 
 
-__all__ = ["pairwise", "nearest", "NearestWorkspace", "topk", "TopKWorkspace", "record_ranges"]
+__all__ = ["pairwise", "nearest", "NearestWorkspace", "topk", "TopKWorkspace", "record_ranges",
+           "record_of"]

@@ -499,6 +499,35 @@ int gfy_pairwise_topk_ranges(const void* a, int64_t n, const void* b, int64_t m,
                              float* top_val, int32_t* top_idx,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* The same with at most one hit per record of b: the k best rows that lie in k DIFFERENT
+ * records — in a library of records, the records that resemble a row instead of k neighbouring
+ * rows of one of them.  b's rows are grouped in contiguous records; the record of b-row j is the
+ * half-open range [group_lo[j], group_hi[j]).
+ *   For every record R, its representative for a-row i is the non-excluded row of R that is
+ *   first in the order (the kernel's fp32 key, then b-row index).  The result for a-row i is
+ *   the k best representatives, ordered by (key, b-row index).  A record whose every row is
+ *   excluded has no representative.  No two columns of a row lie in one record.
+ *   skip_lo, skip_hi int32 [n] as in gfy_pairwise_topk_ranges (the single-pair exclusions are
+ *   ranges of one row: skip_lo[i] = i + c, skip_hi[i] = i + c + 1; lo >= hi excludes nothing).
+ *   group_lo, group_hi int32 [m], device memory.  Precondition: they describe a partition of
+ *   [0, m) into contiguous ranges, group_lo[j] <= j < group_hi[j], the same pair for every row
+ *   of a range (gfy_pairwise_topk_ranges' bounds of a self-search over records are such a pair).
+ *   The values are only ever compared, never used as addresses: a violated precondition gives
+ *   unspecified columns and never an access outside the caller's buffers.
+ *   Keys, the value formulas, -1 with +inf / -inf behind the last candidate (a row with fewer
+ *   than k records that have a representative), the prefix property, independence of the other
+ *   rows of the call, the workspace and its size are those of gfy_pairwise_topk.  With every
+ *   record one row long the result is that of gfy_pairwise_topk_ranges bit for bit.
+ *   1 <= k <= GFY_PAIRWISE_TOPK_DISTINCT_MAX.  NULL pointers (a NULL group pointer is named as
+ *   "group_lo or group_hi"), k, n, m, metric and a short workspace are refused before any
+ *   launch, with the codes of gfy_pairwise_topk_ranges.                                        */
+#define GFY_PAIRWISE_TOPK_DISTINCT_MAX 16
+int gfy_pairwise_topk_distinct(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
+                               const int32_t* skip_lo, const int32_t* skip_hi,
+                               const int32_t* group_lo, const int32_t* group_hi,
+                               float* top_val, int32_t* top_idx,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,8 +18,13 @@ rows (sizes uniform in 1 .. 2 MEAN - 1, seed 0), searched with ``exclude_records
 to it in the same run, with ``exclude_self``; both times and their ratio are written, no ratio
 is expected in advance.
 
+``--distinct`` (with ``--records``) adds a further leg: ``exclude_records`` together with
+``distinct_records`` (at most one hit per record) next to ``exclude_records`` alone, same rows,
+same run; both times and their ratio are written, no ratio is expected in advance either.
+
     python tools/bench_topk.py --rows 1000000
     python tools/bench_topk.py --rows 1000000 --records 300
+    python tools/bench_topk.py --rows 1000000 --records 300 --distinct
 """
 from __future__ import annotations
 
@@ -42,7 +47,8 @@ from ginfinity_amd import distance, synthetic  # noqa: E402
 
 DENSE_ROWS = 4_096
 KERNEL_SOURCES = ("pairwise.hip", "pairwise_topk.hip", "pairwise_topk.inc",
-                  "pairwise_topk_ranges.hip", "gfy_common.h", "gfy_api.hip")
+                  "pairwise_topk_ranges.hip", "pairwise_topk_distinct.hip", "gfy_common.h",
+                  "gfy_api.hip")
 
 
 def _commit() -> str | None:
@@ -102,12 +108,16 @@ def main() -> None:
     parser.add_argument("--ks", default="1,4,8,16")
     parser.add_argument("--records", type=int, default=0, metavar="MEAN",
                         help="also time exclude_records over records of about MEAN rows")
+    parser.add_argument("--distinct", action="store_true",
+                        help="with --records: also time distinct_records next to exclude_records")
     parser.add_argument("--out", default=str(ROOT / "profiles" / "topk_bench.json"))
     args = parser.parse_args()
     if args.dense_blocks < 8:
         parser.error("--dense-blocks: at least 8")
     if args.records < 0:
         parser.error("--records: a positive mean")
+    if args.distinct and not args.records:
+        parser.error("--distinct needs --records MEAN")
     ks = [int(k) for k in args.ks.split(",")]
     rows = torch.from_numpy(synthetic.unit_rows(0, args.rows)).cuda()
     n = args.rows
@@ -173,6 +183,22 @@ def main() -> None:
                     "exclude_records_over_exclude_self": ratio}
                 print(f"{metric} k={k}: exclude_records {statistics.median(records):.4f} s = "
                       f"{ratio:.3f} x exclude_self", file=sys.stderr, flush=True)
+            if counts is not None and args.distinct:   # counts are checked on the host per call
+                beside = _timed(lambda: distance.topk(rows, k=k, metric=metric,
+                                                      exclude_records=counts, workspace=workspace),
+                                args.repeats, args.warmup)
+                distinct = _timed(lambda: distance.topk(rows, k=k, metric=metric,
+                                                        exclude_records=counts,
+                                                        distinct_records=counts,
+                                                        workspace=workspace),
+                                  args.repeats, args.warmup)
+                ratio = statistics.median(distinct) / statistics.median(beside)
+                entry["topk"][str(k)]["distinct"] = {
+                    "exclude_records_distinct_records_seconds": _span(distinct),
+                    "exclude_records_seconds": _span(beside),
+                    "distinct_over_exclude_records": ratio}
+                print(f"{metric} k={k}: distinct_records {statistics.median(distinct):.4f} s = "
+                      f"{ratio:.3f} x exclude_records", file=sys.stderr, flush=True)
         result["distances"][metric] = entry
     text = json.dumps(result, indent=1)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
