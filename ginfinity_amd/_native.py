@@ -26,6 +26,7 @@ GFY_F16, GFY_F32, GFY_F64 = 0, 1, 2
 GFY_L2, GFY_COSINE = 0, 1
 GFY_PAIRWISE_TOPK_MAX = 16
 GFY_PAIRWISE_TOPK_DISTINCT_MAX = 16
+GFY_PAIRWISE_RECORDS_MAX = 2097120
 GFY_OPT_SEPARATE_HEAD = 2
 GFY_OPT_LAYER_KERNEL = 3
 GFY_OPT_STAGGER = 4
@@ -122,6 +123,13 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_pairwise_topk_distinct": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int,
                                            c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gfy_pairwise_record_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "gfy_pairwise_record_chunks": (c_int, [c_int64, c_int64]),
+    "gfy_pairwise_record_best": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
+                                         c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gfy_pairwise_record_scores": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
+                                           c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                           c_size_t, c_void_p]),
 }
 
 

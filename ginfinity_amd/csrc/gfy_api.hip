@@ -1092,4 +1092,61 @@ int gfy_pairwise_topk_distinct(const void* a, int64_t n, const void* b, int64_t 
                               top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t gfy_pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_a,
+                                           int64_t records_b) {
+  (void)records_a;   // the scores need nothing per record of a
+  return pairwise_record_workspace_bytes(n < 1 ? 1 : n, m < 1 ? 1 : m,
+                                         records_b < 1 ? 1 : records_b);
+}
+
+int gfy_pairwise_record_chunks(int64_t n, int64_t m) {
+  return pairwise_record_chunks(n < 1 ? 1 : n, m < 1 ? 1 : m);
+}
+
+// the checks the two record calls share; `who` names the call in the message
+static int check_record_call(const char* who, const void* a, int64_t n, const void* b, int64_t m,
+                             int metric, const int32_t* ptr_b, int64_t records_b, const void* out,
+                             const char* out_name, const void* ws) {
+  GFY_REQUIRE(a, GFY_ERR_INVALID, "%s: a is NULL", who);
+  GFY_REQUIRE(b, GFY_ERR_INVALID, "%s: b is NULL", who);
+  GFY_REQUIRE(ptr_b, GFY_ERR_INVALID, "%s: ptr_b is NULL", who);
+  GFY_REQUIRE(out, GFY_ERR_INVALID, "%s: %s is NULL", who, out_name);
+  GFY_REQUIRE(ws, GFY_ERR_INVALID, "%s: workspace is NULL", who);
+  GFY_REQUIRE(n > 0 && m > 0 && n < INT32_MAX && m < INT32_MAX, GFY_ERR_INVALID,
+              "%s: bad arguments: n = %lld, m = %lld", who, (long long)n, (long long)m);
+  GFY_REQUIRE(records_b > 0 && records_b <= GFY_PAIRWISE_RECORDS_MAX, GFY_ERR_INVALID,
+              "%s: records_b = %lld outside 1..%d", who, (long long)records_b,
+              GFY_PAIRWISE_RECORDS_MAX);
+  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID, "%s: unknown metric %d",
+              who, metric);
+  return GFY_OK;
+}
+
+int gfy_pairwise_record_best(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                             const int32_t* ptr_b, int64_t records_b, float* out_best, void* ws,
+                             size_t ws_bytes, void* stream) {
+  clear_error();
+  if (const int rc = check_record_call("gfy_pairwise_record_best", a, n, b, m, metric, ptr_b,
+                                       records_b, out_best, "out_best", ws))
+    return rc;
+  return launch_pairwise_records(a, n, b, m, metric, nullptr, 0, ptr_b, records_b, out_best, ws,
+                                 ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                               const int32_t* ptr_a, int64_t records_a, const int32_t* ptr_b,
+                               int64_t records_b, float* out_scores, void* ws, size_t ws_bytes,
+                               void* stream) {
+  clear_error();
+  GFY_REQUIRE(ptr_a, GFY_ERR_INVALID, "gfy_pairwise_record_scores: ptr_a is NULL");
+  if (const int rc = check_record_call("gfy_pairwise_record_scores", a, n, b, m, metric, ptr_b,
+                                       records_b, out_scores, "out_scores", ws))
+    return rc;
+  GFY_REQUIRE(records_a > 0 && records_a < INT32_MAX, GFY_ERR_INVALID,
+              "gfy_pairwise_record_scores: records_a = %lld outside 1..2^31 - 2",
+              (long long)records_a);
+  return launch_pairwise_records(a, n, b, m, metric, ptr_a, records_a, ptr_b, records_b,
+                                 out_scores, ws, ws_bytes, (hipStream_t)stream);
+}
+
 }  // extern "C"

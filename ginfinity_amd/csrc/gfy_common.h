@@ -367,6 +367,14 @@ int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int
                          float* top_val, int32_t* top_idx, void* ws, size_t ws_bytes,
                          hipStream_t s);
 size_t pairwise_topk_workspace_bytes(int64_t n, int64_t m, int k);
+// pairwise_records.hip; ptr_a == nullptr: out is best [n][records_b], else scores
+// [records_a][records_b]
+int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                            const int32_t* ptr_a, int64_t records_a, const int32_t* ptr_b,
+                            int64_t records_b, float* out, void* ws, size_t ws_bytes,
+                            hipStream_t s);
+size_t pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_b);
+int pairwise_record_chunks(int64_t n, int64_t m);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS

@@ -13,6 +13,26 @@ materialise the N×M matrix.  ``topk`` and ``nearest`` can leave out a range of 
 (``exclude_ranges``) — in a search over a library of records, each row's own record
 (``exclude_records``, ``record_ranges``) — and can return at most one row per record
 (``distinct_records``, ``record_of``).
+
+Record-to-record best-match scores (``record_best``, ``record_scores``; also include/gfy.h).
+The rows of ``b`` are grouped in contiguous records of ``counts_b`` rows and the rows of ``a`` in
+records of ``counts_a`` rows (non-negative integers, checked as ``record_ranges`` checks them,
+``sum(counts_b) == m``, ``sum(counts_a) == n``).  The key and the value of a pair are those of
+``nearest`` / ``topk``, computed the same way.
+
+    row level     best[i, r]  = the value of the best pair (i, j) with j in record r (smallest
+                                L2 distance / largest cosine); a record of zero rows gives
+                                +inf (l2) / -inf (cosine)
+    record level  score[q, r] = the mean over the rows i of record q of best[i, r], summed in
+                                float64 in ascending row order, divided by |q| and rounded to
+                                float32 once; an a-record of zero rows gives a row of NaN, a
+                                b-record of zero rows +inf / -inf through the mean
+
+``best[:, r]`` equals ``nearest(a, b[ptr[r]:ptr[r + 1]])`` values bit for bit; an entry of
+``best`` or ``score`` depends neither on the other records and rows of the call nor on how the
+call is cut into blocks, chunks or workgroups, and is the same from run to run bit for bit.  The
+score is directional (``a`` onto ``b``): the symmetric form is two calls.  Nothing is excluded:
+in a self-search the pairs (i, i) are simply the best ones.
 """
 from __future__ import annotations
 
@@ -370,5 +390,171 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
     return values, indices
 
 
+class RecordWorkspace:
+    """Scratch memory of ``record_best`` / ``record_scores`` kept across calls, as
+    ``TopKWorkspace`` keeps that of ``topk`` (the results are always new tensors)."""
+
+    def __init__(self) -> None:
+        self.scratch: torch.Tensor | None = None
+
+    def buffer(self, device, scratch_bytes: int) -> torch.Tensor:
+        if self.scratch is None or self.scratch.numel() < scratch_bytes or \
+                self.scratch.device != device:
+            self.scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=device)
+        return self.scratch
+
+
+#: default ``max_workspace_bytes`` of ``record_scores``: the row-level intermediate of one block
+RECORD_WORKSPACE_BYTES = 1 << 30
+
+
+def _record_ptr(counts, rows: int, name: str, side: str) -> np.ndarray:
+    """The running sums (int64, records + 1 entries) of ``counts``, which must sum to ``rows``."""
+    counts = _checked_counts(counts)
+    ptr = np.concatenate(([0], np.cumsum(counts))).astype(np.int64)
+    if ptr[-1] != rows:
+        raise ValueError(f"{name} sums to {int(ptr[-1])} rows, {side} has {rows}")
+    if rows >= 2 ** 31 - 1:
+        raise ValueError("record counts must sum to fewer than 2^31 - 1 rows")
+    if counts.size > native.GFY_PAIRWISE_RECORDS_MAX:
+        raise ValueError(f"{name} must hold at most {native.GFY_PAIRWISE_RECORDS_MAX} records")
+    return ptr
+
+
+def plan_record_blocks(counts_a, records_b: int, max_workspace_bytes: int) -> list[tuple[int, int]]:
+    """How ``record_scores`` walks ``a``: half-open ranges ``(first, last)`` of records of ``a``,
+    in order, that cover every record once.  A block is whole records, as many as fit: its rows
+    times ``records_b`` words — the row-level intermediate of its native call — are at most
+    ``max_workspace_bytes``.  A pure function of its arguments; a single record that alone
+    exceeds the budget is a ``ValueError`` that names the bytes it needs."""
+    counts = _checked_counts(counts_a)
+    per_row = 4 * max(int(records_b), 0)
+    budget = int(max_workspace_bytes)
+    blocks, first, rows = [], 0, 0
+    for q, count in enumerate(counts.tolist()):
+        if count * per_row > budget:
+            raise ValueError(f"record {q} of a has {count} rows and needs {count * per_row} bytes "
+                             f"of workspace against {records_b} records of b: "
+                             f"max_workspace_bytes is {budget}")
+        if (rows + count) * per_row > budget:
+            blocks.append((first, q))
+            first, rows = q, 0
+        rows += count
+    if first < counts.size:
+        blocks.append((first, int(counts.size)))
+    return blocks
+
+
+def _worst(code: int) -> float:
+    """What a record of zero rows gives: no pair at all."""
+    return float("inf") if code == native.GFY_L2 else float("-inf")
+
+
+def record_best(a, b=None, *, counts_b, metric: str = "l2",
+                workspace: RecordWorkspace | None = None) -> torch.Tensor:
+    """For every row of ``a`` the best pair inside every record of ``b``: float32 ``[n, R]``,
+    ``best[i, r]`` the smallest L2 distance / largest cosine between row i and the rows of
+    record r, exact, the N×M matrix never written (the definitions are at the head of this
+    module).  ``counts_b`` are the row counts of ``b``'s contiguous records, ``sum(counts_b) ==
+    m``; a record of zero rows gives ``+inf`` (l2) / ``-inf`` (cosine).  Column r equals
+    ``nearest(a, b[ptr[r]:ptr[r + 1]])`` values bit for bit.  Meant for blocks that fit in
+    memory (n·R·4 bytes twice: the result and its transposed intermediate), as ``pairwise`` is.
+    With ``b`` omitted ``a`` is searched against itself."""
+    code = _metric(metric)
+    a = _checked(a)
+    b = None if b is None else _checked(b)   # every argument error before a device is touched
+    n, m = a.shape[0], a.shape[0] if b is None else b.shape[0]
+    ptr_b = _record_ptr(counts_b, m, "counts_b", "b")
+    records = ptr_b.size - 1
+    a = _prepare(a, None)
+    b = a if b is None else _prepare(b, a.device)
+    with torch.cuda.device(a.device):
+        if n == 0 or records == 0 or m == 0:
+            return torch.full((n, records), _worst(code), dtype=torch.float32, device=a.device)
+        lib = native.library()
+        best = torch.empty((n, records), dtype=torch.float32, device=a.device)
+        need = lib.gfy_pairwise_record_workspace_bytes(n, m, 0, records)
+        scratch = (workspace or RecordWorkspace()).buffer(a.device, need)
+        ptr = torch.from_numpy(ptr_b.astype(np.int32)).to(a.device)
+        native.check(lib.gfy_pairwise_record_best(
+            a.data_ptr(), n, b.data_ptr(), m, code, ptr.data_ptr(), records, best.data_ptr(),
+            scratch.data_ptr(), scratch.numel(),
+            torch.cuda.current_stream(a.device).cuda_stream), "gfy_pairwise_record_best")
+    return best
+
+
+def record_scores(a, b=None, *, counts_a, counts_b=None, metric: str = "l2",
+                  max_workspace_bytes: int = RECORD_WORKSPACE_BYTES,
+                  workspace: RecordWorkspace | None = None) -> torch.Tensor:
+    """How well every record of ``a`` matches every record of ``b``: float32 ``[Q, R]``,
+    ``score[q, r]`` the mean over the rows i of record q of ``record_best(a, b)[i, r]`` — the
+    float64 sum in ascending row order, divided by the record's rows, rounded to float32 once
+    (the definitions are at the head of this module).  Exact and dense: the ranking by which to
+    decide which pairs of records to align at all.  Small L2 scores / large cosine scores are
+    good matches.  An a-record of zero rows gives a row of NaN, a b-record of zero rows a column
+    of ``+inf`` (l2) / ``-inf`` (cosine).
+
+    ``counts_a`` / ``counts_b`` are the row counts of the contiguous records of ``a`` / ``b``.
+    With ``b`` omitted it is a self-search and ``counts_b`` defaults to ``counts_a``; nothing is
+    excluded, so the diagonal holds 0 (l2) / 1 (cosine, up to rounding).  The score is
+    directional, ``a`` onto ``b``: ``score(a, b)[q, r]`` and ``score(b, a)[r, q]`` differ, and
+    a symmetric score is two calls combined by the caller.
+
+    Neither the N×M matrix nor the n × R row-level intermediate is ever whole in memory: ``a``
+    is walked in blocks of whole records (``plan_record_blocks``) whose intermediates take at
+    most ``max_workspace_bytes`` each, one native call per block into the rows of the one
+    result; the blocking does not change a bit of it.  A single record of ``a`` that alone
+    exceeds the budget is a ``ValueError`` that names the bytes it needs."""
+    code = _metric(metric)
+    a = _checked(a)
+    if b is None:
+        counts_b = counts_a if counts_b is None else counts_b
+    else:
+        b = _checked(b)
+        if counts_b is None:
+            raise ValueError("counts_b is required with b: record counts of b's rows")
+    n, m = a.shape[0], a.shape[0] if b is None else b.shape[0]
+    ptr_a = _record_ptr(counts_a, n, "counts_a", "a")
+    ptr_b = _record_ptr(counts_b, m, "counts_b", "b")
+    queries, records = ptr_a.size - 1, ptr_b.size - 1
+    if isinstance(max_workspace_bytes, bool) or \
+            not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 0:
+        raise ValueError("max_workspace_bytes must be a non-negative integer")
+    blocks = plan_record_blocks(np.diff(ptr_a), records, max_workspace_bytes)
+    a = _prepare(a, None)
+    b = a if b is None else _prepare(b, a.device)
+    with torch.cuda.device(a.device):
+        scores = torch.empty((queries, records), dtype=torch.float32, device=a.device)
+        if queries == 0 or records == 0:
+            return scores
+        if n == 0 or m == 0:   # no pair at all: NaN for a record without rows, else the worst
+            scores.fill_(_worst(code))
+            empty = torch.from_numpy(np.diff(ptr_a) == 0).to(a.device)
+            scores[empty] = float("nan")
+            return scores
+        lib = native.library()
+        stream = torch.cuda.current_stream(a.device).cuda_stream
+        ptr_b_dev = torch.from_numpy(ptr_b.astype(np.int32)).to(a.device)
+        # every block's running sums, counted from the block's first row: one upload
+        relative = [ptr_a[first:last + 1] - ptr_a[first] for first, last in blocks]
+        starts = np.concatenate(([0], np.cumsum([piece.size for piece in relative])))
+        ptr_a_dev = torch.from_numpy(np.concatenate(relative).astype(np.int32)).to(a.device)
+        keeper = workspace or RecordWorkspace()
+        for (first, last), at in zip(blocks, starts.tolist()):
+            row_lo, row_hi = int(ptr_a[first]), int(ptr_a[last])
+            if row_hi == row_lo:   # records of zero rows only
+                scores[first:last] = float("nan")
+                continue
+            rows = row_hi - row_lo
+            need = lib.gfy_pairwise_record_workspace_bytes(rows, m, last - first, records)
+            scratch = keeper.buffer(a.device, need)
+            native.check(lib.gfy_pairwise_record_scores(
+                a[row_lo:row_hi].data_ptr(), rows, b.data_ptr(), m, code,
+                ptr_a_dev[at:].data_ptr(), last - first, ptr_b_dev.data_ptr(), records,
+                scores[first:last].data_ptr(), scratch.data_ptr(), scratch.numel(), stream),
+                "gfy_pairwise_record_scores")
+    return scores
+
+
 __all__ = ["pairwise", "nearest", "NearestWorkspace", "topk", "TopKWorkspace", "record_ranges",
-           "record_of"]
+           "record_of", "record_best", "record_scores", "RecordWorkspace", "plan_record_blocks"]

@@ -528,6 +528,60 @@ int gfy_pairwise_topk_distinct(const void* a, int64_t n, const void* b, int64_t 
                                float* top_val, int32_t* top_idx,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Record-to-record best-match scores: how well does record q of a match record r of b, for every
+ * pair of records — the cheap, exact, dense ranking by which a caller decides which pairs of
+ * records are worth aligning.  The N x M matrix is never materialised.
+ *   The rows of b are grouped in records_b contiguous records and the rows of a in records_a:
+ *   ptr_b int32 [records_b + 1] and ptr_a int32 [records_a + 1], device memory, are the running
+ *   sums of the records' row counts (ptr[0] = 0, ascending, ptr_b[records_b] = m,
+ *   ptr_a[records_a] = n); record r of b is the rows [ptr_b[r], ptr_b[r + 1]).  Counts of zero
+ *   are allowed.
+ *   The key and the value of a pair are those of gfy_pairwise_nearest / gfy_pairwise_topk,
+ *   computed the same way (the folded start values for GFY_L2, the fma key form for GFY_COSINE,
+ *   the same per-row terms, the same value formulas).
+ *   Row level (gfy_pairwise_record_best): out_best float32 [n][records_b], row-major;
+ *   best[i][r] is the value of the best pair (i, j) with j in record r — smallest distance
+ *   (GFY_L2) / largest similarity (GFY_COSINE).  A record of zero rows gives +inf / -inf.
+ *   Column r is gfy_pairwise_nearest(a, the rows of record r)'s best_val bit for bit.  (Only a
+ *   zero keeps no promise of its sign: a maximum does not tell +0 from -0.)
+ *   Record level (gfy_pairwise_record_scores): out_scores float32 [records_a][records_b];
+ *   score[q][r] is the mean over the rows i of record q of best[i][r]: summed in float64 in
+ *   ascending row order, divided by the record's row count, rounded to float32 once.  A record
+ *   of a with zero rows gives a row of NaN; a record of b with zero rows gives +inf / -inf
+ *   through the mean.  The score is directional (a onto b): the symmetric form is two calls.
+ *   Nothing is excluded: in a self-search the pairs (i, i) are simply the best ones.
+ *   An entry of best or of score depends neither on the other records and rows of the call nor
+ *   on how the call is cut into workgroups and chunks, and is the same from run to run, bit for
+ *   bit: per (a-row, record) the sweep keeps a maximum, which does not depend on the order of
+ *   its operands (integer atomic max on an order-preserving image of the fp32 value), and the
+ *   mean is summed in one fixed order without atomics.
+ *   Workspace: gfy_pairwise_record_workspace_bytes(n, m, records_a, records_b), the same for both
+ *   calls (records_a is ignored); it holds the row-level intermediate, n * records_b words, so
+ *   a caller with many rows walks a in blocks of whole records, one call per block into the
+ *   rows of one out_scores.  gfy_pairwise_record_chunks(n, m) tells into how many chunks a call
+ *   of that shape cuts b (its own query: the split is a copy of the top-k launcher's today and
+ *   need not stay one).
+ *   Cost (by reasoning, not measured): the MFMA work of gfy_pairwise_nearest with a lighter
+ *   epilogue, plus per (128 a-rows, record) at most one 64-lane atomic per wave that met the
+ *   record — up to 8 against about 1.3 us of MFMA work for a record of 200 rows.  Records of one
+ *   row each degrade to a dense write through atomics, which is correct and not meant to be fast.
+ *   ptr_b is only compared and ptr_a clipped to [0, n]: arrays that are no running sums give
+ *   unspecified values and no access outside the caller's buffers.
+ *   A NULL pointer (named in gfy_last_error), n or m outside 1..2^31 - 2, records_b outside
+ *   1..GFY_PAIRWISE_RECORDS_MAX, records_a < 1 and an unknown metric are GFY_ERR_INVALID, a short
+ *   workspace is GFY_ERR_WORKSPACE; all of it before any launch and without a device.          */
+#define GFY_PAIRWISE_RECORDS_MAX 2097120   /* 65,535 x 32: the grid of the transposing finish */
+size_t gfy_pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_a,
+                                           int64_t records_b);
+int gfy_pairwise_record_chunks(int64_t n, int64_t m);
+int gfy_pairwise_record_best(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                             const int32_t* ptr_b, int64_t records_b, float* out_best,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                               const int32_t* ptr_a, int64_t records_a,
+                               const int32_t* ptr_b, int64_t records_b, float* out_scores,
+                               void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
