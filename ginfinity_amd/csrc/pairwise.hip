@@ -24,36 +24,21 @@
 // the b-rows split over several workgroups the partial results are merged by a
 // second small kernel.  Workgroups are numbered chunk-major so the ones running
 // together sweep the same b-tiles and share them through L2.
+// The ring, the tile request, the a-block staging and the multiply are those of pairwise_sweep.inc,
+// which the top-k and record sweeps share; the tile loop here is this kernel's own.
 #include "gfy_common.h"
+#include "pairwise_sweep.inc"
 
 namespace gfy {
 namespace {
 
 constexpr int kBlockA = 256;  // a-rows per workgroup
-constexpr int kTileB = 128;   // b-rows per LDS tile
-constexpr int kThreads = 512;
-constexpr int kBuffers = 4;   // b-tile ring: tile i is consumed while i+1 .. i+3 are in flight
 #ifndef GFY_PAIRWISE_REQUEST_AFTER_MULTIPLY
 #define GFY_PAIRWISE_REQUEST_AFTER_MULTIPLY 1
 #endif
 #ifndef GFY_PAIRWISE_TILES_PER_BARRIER
 #define GFY_PAIRWISE_TILES_PER_BARRIER 2   // nearest: 2 = a barrier per pair of tiles, 1 = per tile
 #endif
-
-// pairwise_topk.hip carries its own copies of uniform_pointer, off256, the ring constants and the
-// `request` lambda (so that this file's machine code does not move with it): a fix to the DMA
-// addressing or the swizzle goes into both files.
-template <class T>
-__device__ __forceinline__ const T* uniform_pointer(const T* pointer) {
-  const uint64_t bits = (uint64_t)(uintptr_t)pointer;
-  const uint32_t low = __builtin_amdgcn_readfirstlane((uint32_t)bits);
-  const uint32_t high = __builtin_amdgcn_readfirstlane((uint32_t)(bits >> 32));
-  return reinterpret_cast<const T*>(((uint64_t)high << 32) | low);
-}
-
-__device__ __forceinline__ int off256(int row, int chunk) {
-  return row * 256 + ((chunk ^ (row & 15)) << 4);
-}
 
 // per-row (s, t) on the b side, (na or 1/|a|) on the a side
 // s/t are written for `padded` >= count rows: the rows past the end get key = +inf
@@ -108,10 +93,6 @@ struct PairArgs {
   float* dense;         // [n][m]        (dense)
 };
 
-constexpr int kRowBytes = kTileB * 256;        // one b-tile of rows
-constexpr int kTermBytes = 2 * kTileB * 4;     // its (s, t)
-constexpr int kTermSlots = 4;                  // (s, t) ring, like the rows
-
 // kFold (nearest, L2): see k_row_terms — the epilogue is a running maximum of the accumulators
 // themselves: no per-element fma, no (s, t) operand reads per a-tile.
 template <bool kDense, bool kFold = false>
@@ -133,67 +114,15 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise(const PairArgs p) {
   const int64_t j_begin = (int64_t)chunk * p.chunk_rows;
   const int64_t j_end = j_begin + p.chunk_rows < p.m ? j_begin + p.chunk_rows : p.m;
 
-  // one b-tile -> buffer `buf`: 128 rows as 32 DMA instructions (4 per wave, 4 rows each),
-  // (s, t) as one more by waves 0 and 1.  Rows past the end re-read the last row; their
-  // t is +inf (k_row_terms pads s/t to whole tiles).
-  // Per-lane byte offset of its 16-byte piece q inside a tile: row 16 wave + 4 q + sub, slot
-  // (lane & 15) ^ (row & 15)  =  (home ^ (q << 6)) + 1024 q  with ONE loop-invariant register
-  // (`home`); the tile's base travels in SGPRs.  (64-bit per-lane pointers, or the four
-  // offsets kept in registers, spilled — and a scratch reload is a vmcnt(0) wait that drains
-  // the DMA look-ahead.  The asm keeps hipcc from hoisting them out of the loop again.)
-  // `home` is rebuilt from threadIdx.x per request (six VALU operations): any loop-invariant
-  // register here is one that hipcc spills.
   auto request = [&](int k) __attribute__((always_inline)) {   // tile k of this workgroup's sweep
-    const int64_t j0 = j_begin + (int64_t)k * kTileB;
-    const uint32_t base = lds0 + (uint32_t)(k & (kBuffers - 1)) * kRowBytes;
-    // wave-uniform, and said so: with the carried reduce below in the loop hipcc's divergence
-    // analysis puts j0 in vector registers, which the DMA's scalar base operand cannot take
-    const f16* rows = uniform_pointer(p.b + j0 * 128);
-    uint32_t me = threadIdx.x;
-    asm volatile("" : "+v"(me));
-    const uint32_t sub = (me >> 4) & 3u, slot = me & 15u;
-    const uint32_t at_home = ((uint32_t)(16 * wave) + sub) * 256u + ((slot ^ sub) << 4);
-    if (j0 + kTileB <= p.m) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        dma16(rows, (at_home ^ (uint32_t)(q << 6)) + 1024u * q,
-              base + (uint32_t)(wave * 4 + q) * 1024u);
-    } else {   // ragged last tile: rows past the end re-read the last row (their t is +inf)
-      const int last = (int)(p.m - 1 - j0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint32_t full = (at_home ^ (uint32_t)(q << 6)) + 1024u * q;
-        const int row = (int)(full >> 8);   // 16 wave + 4 q + sub
-        const int from = row < last ? row : last;
-        dma16(rows, (uint32_t)from * 256u + (full & 255u),
-              base + (uint32_t)(wave * 4 + q) * 1024u);
-      }
-    }
-    if (wave < (kFold ? 1 : 2) && (me & 32u) == 0)   // 128 floats = 32 lanes x 16 B
-      dma16(uniform_pointer((wave == 0 && !kFold ? p.s : p.t) + j0), (me & 31u) * 16u,
-            lds0 + kBuffers * kRowBytes + (uint32_t)(k & (kTermSlots - 1)) * kTermBytes
-                + (uint32_t)(kFold ? 1 : wave) * (kTileB * 4));
+    sweep_request<kFold>(p, lds0, wave, j_begin, k);
   };
 
-  // stage the a-block through LDS once (coalesced), then keep ALL its fragments in registers
-  {
-    char* atile = smem + kRowBytes;   // buffers 1 and 2 (64 KB), not yet in use
-    for (int i = t; i < kBlockA * 16; i += kThreads) {
-      const int row = i >> 4, ch = i & 15;
-      f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (a0 + row < p.n) v = *reinterpret_cast<const f16x8*>(p.a + (a0 + row) * 128 + ch * 8);
-      *reinterpret_cast<f16x8*>(atile + off256(row, ch)) = v;
-    }
-  }
+  stage_a_block<kBlockA>(smem, p.a, p.n, a0);   // buffers 1 and 2 (64 KB)
   if (j_begin < j_end) request(0);
   __syncthreads();
   f16x8 af[4][8];
-#pragma unroll
-  for (int at = 0; at < 4; ++at)
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-      af[at][ks] = *reinterpret_cast<const f16x8*>(
-          smem + kRowBytes + off256(128 * wa + 32 * at + r, 2 * ks + hq));
+  load_a_fragments<4>(af, smem, wa, r, hq);
 
   float best[4];   // running minimum of key (kFold: running maximum of g = -key / 2)
   int bidx[4];
@@ -209,55 +138,16 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise(const PairArgs p) {
   if (tiles > 1) request(1);
   if (tiles > 2 && (kDense || GFY_PAIRWISE_TILES_PER_BARRIER != 2)) request(2);
 
-  // the wave's 32 x 128 block of tile k: four independent accumulator chains (a 32x32x16
-  // MFMA that reads the previous one's result stalls the issue port), the b operand read
-  // kAheadK k-steps ahead
-  f32x16 acc[4];   // [at]
+  f32x16 acc[4];   // [at]: the wave's 32 x 128 block of a tile
   const int jw = 32 * wb + 4 * hq;   // first of this lane's b-rows inside a tile
   auto multiply = [&](int k) __attribute__((always_inline)) {
-    const char* tile = smem + (k & (kBuffers - 1)) * kRowBytes;
-    f32x16 start;    // what every chain starts from: 0, or (kFold) -|b_j|^2 / 2 of the lane's 16 b-rows
-    if constexpr (kFold) {
-      const float* u_l = reinterpret_cast<const float*>(
-          smem + kBuffers * kRowBytes + (k & (kTermSlots - 1)) * kTermBytes) + kTileB;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 uv = *reinterpret_cast<const f32x4*>(u_l + jw + 8 * g);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) start[4 * g + i] = uv[i];
-      }
-    } else {
-#pragma unroll
-      for (int at = 0; at < 4; ++at)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc[at][q] = 0.f;
-    }
-    constexpr int kAheadK = 2, kRing = kAheadK + 1;
-    f16x8 bf[kRing];   // [ks % kRing]
-#pragma unroll
-    for (int ks = 0; ks < kAheadK; ++ks)
-      bf[ks] = *reinterpret_cast<const f16x8*>(tile + off256(32 * wb + r, 2 * ks + hq));
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      if (ks + kAheadK < 8)
-        bf[(ks + kAheadK) % kRing] = *reinterpret_cast<const f16x8*>(
-            tile + off256(32 * wb + r, 2 * (ks + kAheadK) + hq));
-      // hipcc otherwise sinks every operand read down to its MFMAs (one register quad,
-      // read -> lgkmcnt(0) -> MFMAs: the LDS latency exposed eight times a tile)
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int at = 0; at < 4; ++at)
-        acc[at] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[ks % kRing], af[at][ks],
-                                                         kFold && ks == 0 ? start : acc[at],
-                                                         0, 0, 0);
-    }
+    sweep_multiply<4, kFold>(acc, af, smem, k, wb, r, hq);
   };
 
   // what happens to the products of tile k (still in acc)
   auto reduce = [&](int k) __attribute__((always_inline)) {
     const int64_t j0 = j_begin + (int64_t)k * kTileB;
-    const float* s_l = reinterpret_cast<const float*>(
-        smem + kBuffers * kRowBytes + (k & (kTermSlots - 1)) * kTermBytes);
+    const float* s_l = sweep_terms(smem, k);
     const float* t_l = s_l + kTileB;
     if constexpr (kDense) {
 #pragma unroll
@@ -273,16 +163,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise(const PairArgs p) {
           for (int i = 0; i < 4; ++i) {
             const int64_t j = j0 + jl + i;
             const float key = __builtin_fmaf(acc[at][4 * g + i], sv[i], tv[i]);
-            if (ai < p.n && j < p.m) {
-              float val;
-              if (p.metric == GFY_L2) {
-                const float d2 = aterm + key;
-                val = __builtin_sqrtf(d2 > 0.f ? d2 : 0.f);
-              } else {
-                val = -key * aterm;
-              }
-              p.dense[ai * p.m + j] = val;
-            }
+            if (ai < p.n && j < p.m) p.dense[ai * p.m + j] = pair_value(key, aterm, p.metric);
           }
         }
       }
@@ -507,68 +388,32 @@ __global__ __launch_bounds__(256) void k_nearest_finish(const float* __restrict_
       idx = oi;
     }
   }
-  const float at = a_term[i];
-  float out;
-  if (metric == GFY_L2) {
-    const float d2 = at + v;
-    out = __builtin_sqrtf(d2 > 0.f ? d2 : 0.f);
-  } else {
-    out = -v * at;
-  }
-  best_val[i] = out;
+  best_val[i] = pair_value(v, a_term[i], metric);
   best_idx[i] = idx == 0x7fffffff ? -1 : idx;
 }
 
 struct PairWorkspace {
   float *s, *t, *a_term, *part_val;
   int32_t* part_idx;
-  int blocks_a, chunks;
-  int64_t chunk_rows;
+  BSplit split;
   size_t bytes;
 };
 
+// Layout: the terms (pairwise_sweep.inc), then part_val and part_idx ([chunks][n] each)
 PairWorkspace carve(void* base, int64_t n, int64_t m) {
   PairWorkspace w;
-  w.blocks_a = (int)((n + kBlockA - 1) / kBlockA);
-  const int64_t tiles_b = (m + kTileB - 1) / kTileB;
-  int64_t chunks = (1024 + w.blocks_a - 1) / w.blocks_a;
-  {
-    // One workgroup per CU at a time, all of one length: a grid of blocks_a x chunks workgroups
-    // ends after ceil(grid / CUs) of them, each 1 / chunks of a sweep long.  1,000,000 rows are
-    // 3,907 a-blocks = 15.26 per CU: one chunk ends after 16 sweeps, three after 46 / 3 = 15.33.
-    // A few more chunks than the minimum cost a merge entry per a-row and chunk (k_nearest_finish).
-    constexpr int64_t kCus = 256;   // MI355X; another part only loses the fit
-    const int64_t least = chunks;
-    double best = 1e300;
-    for (int64_t c = least; c < least + 6; ++c) {
-      const double sweeps = (double)((w.blocks_a * c + kCus - 1) / kCus) / (double)c;
-      if (sweeps < best * 0.99) best = sweeps, chunks = c;   // a later count only for a real gain
-    }
-  }
-#ifdef GFY_DIAG_PAIRWISE_CHUNKS   // diagnostic builds: the sweep behind the choice above (profiles/README.md)
-  if (const char* forced = getenv("GFY_PAIRWISE_CHUNKS")) chunks = atoll(forced);
+  Carver carver{base};
+  int64_t forced_chunks = 0;
+#ifdef GFY_DIAG_PAIRWISE_CHUNKS   // diagnostic builds: the sweep behind the choice of split_b (profiles/README.md)
+  if (const char* forced = getenv("GFY_PAIRWISE_CHUNKS")) forced_chunks = atoll(forced);
 #endif
-  if (chunks > tiles_b) chunks = tiles_b;
-  if (chunks < 1) chunks = 1;
-  const int64_t tiles_per_chunk = (tiles_b + chunks - 1) / chunks;
-  w.chunk_rows = tiles_per_chunk * kTileB;
-  w.chunks = (int)((tiles_b + tiles_per_chunk - 1) / tiles_per_chunk);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* ptr = base ? (char*)base + off : nullptr;
-    off += align_up(bytes, 256);
-    return ptr;
-  };
-  w.s = (float*)take((size_t)tiles_b * kTileB * 4);   // padded to whole tiles
-  w.t = (float*)take((size_t)tiles_b * kTileB * 4);
-  w.a_term = (float*)take((size_t)n * 4);
-  w.part_val = (float*)take((size_t)w.chunks * n * 4);
-  w.part_idx = (int32_t*)take((size_t)w.chunks * n * 4);
-  w.bytes = off;
+  w.split = split_b(n, m, kBlockA, forced_chunks);
+  carver.terms(n, m, w.s, w.t, w.a_term);
+  w.part_val = (float*)carver.take((size_t)w.split.chunks * n * 4);
+  w.part_idx = (int32_t*)carver.take((size_t)w.split.chunks * n * 4);
+  w.bytes = carver.bytes;
   return w;
 }
-
-constexpr int kPairLds = kBuffers * kRowBytes + kTermSlots * kTermBytes;   // row ring (buffers 1, 2 stage the a-block first) + (s, t) ring
 
 }  // namespace
 
@@ -582,20 +427,6 @@ int launch_pairwise_row_terms(const void* rows, int64_t count, int64_t padded, i
                                                                metric, fold, s_out, t_out, a_term);
   GFY_CHECK_HIP(hipGetLastError());
   return GFY_OK;
-}
-
-// > 64 KB of dynamic LDS: opt in once per device, thread-safe (gfy_common.h)
-static PerDeviceOnce g_pairwise_lds_opt_in;
-static int opt_in_pairwise_lds() {
-  return g_pairwise_lds_opt_in.run([]() -> int {
-    GFY_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pairwise<false>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kPairLds));
-    GFY_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pairwise<true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kPairLds));
-    GFY_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pairwise<false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, kPairLds));
-    return GFY_OK;
-  });
 }
 
 int launch_pairwise_nearest(const void* a, int64_t n, const void* b, int64_t m,
@@ -622,16 +453,17 @@ int launch_pairwise_nearest(const void* a, int64_t n, const void* b, int64_t m,
   p.metric = metric;
   p.exclude_offset = exclude_offset;
   p.exclude_on = exclude_on;
-  p.blocks_a = w.blocks_a;
-  p.chunks = w.chunks;
-  p.chunk_rows = w.chunk_rows;
+  p.blocks_a = w.split.blocks_a;
+  p.chunks = w.split.chunks;
+  p.chunk_rows = w.split.chunk_rows;
   p.part_val = w.part_val;
   p.part_idx = w.part_idx;
-  if (const int rc = opt_in_pairwise_lds()) return rc;
-  if (fold) k_pairwise<false, true><<<w.blocks_a * w.chunks, kThreads, kPairLds, s>>>(p);
-  else k_pairwise<false><<<w.blocks_a * w.chunks, kThreads, kPairLds, s>>>(p);
+  const int grid = p.blocks_a * p.chunks;
+  if (const int rc = fold ? launch_sweep<&k_pairwise<false, true>, kSweepLds>(p, grid, s)
+                          : launch_sweep<&k_pairwise<false, false>, kSweepLds>(p, grid, s))
+    return rc;
   k_nearest_finish<<<(int)((n + 255) / 256), 256, 0, s>>>(
-      w.part_val, w.part_idx, w.a_term, n, w.chunks, metric, best_val, best_idx);
+      w.part_val, w.part_idx, w.a_term, n, p.chunks, metric, best_val, best_idx);
   GFY_CHECK_HIP(hipGetLastError());
   return GFY_OK;
 }
@@ -665,8 +497,7 @@ int launch_pairwise_dense(const void* a, int64_t n, const void* b, int64_t m,
   p.chunks = 1;
   p.chunk_rows = (m + kTileB - 1) / kTileB * kTileB;
   p.dense = out;
-  if (const int rc = opt_in_pairwise_lds()) return rc;
-  k_pairwise<true><<<p.blocks_a, kThreads, kPairLds, s>>>(p);
+  if (const int rc = launch_sweep<&k_pairwise<true, false>, kSweepLds>(p, p.blocks_a, s)) return rc;
   GFY_CHECK_HIP(hipGetLastError());
   return GFY_OK;
 }

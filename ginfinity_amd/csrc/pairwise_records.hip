@@ -3,8 +3,8 @@
 // every record of b, and the mean of those over the rows of every record of a, without ever
 // writing the n x m matrix.
 //
-// The sweep is that of k_pairwise_topk (pairwise_topk.inc; told at the head of pairwise_topk.hip):
-// 128 a-rows per workgroup (8 waves, 2 x 4, a wave holds 64 a-rows against 32 b-rows of every
+// The sweep is the shared one of pairwise_sweep.inc in the shape of k_pairwise_topk (told at the head
+// of pairwise_topk.hip): 128 a-rows per workgroup (8 waves, 2 x 4, a wave holds 64 a-rows against 32 b-rows of every
 // tile), b in 128-row tiles by LDS-DMA into the ring of four, two tiles per barrier, the next
 // pair requested behind the first multiply, the a-row on the MFMA lane with 16 values per lane
 // and a-row slot.  The pair's value g (maximised) is computed exactly as there and in the
@@ -35,18 +35,12 @@
 // order — one thread per pair, the values staged through LDS so that the reads of bits stay
 // coalesced along the a-rows — divides by the record's rows and rounds to float32 once.
 #include "gfy_common.h"
+#include "pairwise_sweep.inc"
 
 namespace gfy {
 namespace {
 
 constexpr int kBlockA = 128;  // a-rows per workgroup
-constexpr int kTileB = 128;   // b-rows per LDS tile
-constexpr int kThreads = 512;
-constexpr int kBuffers = 4;   // b-tile ring: the pair being consumed and the pair in flight
-constexpr int kRowBytes = kTileB * 256;        // one b-tile of rows
-constexpr int kTermBytes = 2 * kTileB * 4;     // its (s, t)
-constexpr int kTermSlots = 4;                  // (s, t) ring, like the rows
-constexpr int kRecordLds = kBuffers * kRowBytes + kTermSlots * kTermBytes;
 constexpr uint32_t kBelowAll = 0x007fffffu;    // ordered(-inf)
 
 struct RecordArgs {
@@ -61,31 +55,6 @@ struct RecordArgs {
   int records_b;
   uint32_t* bits;       // [records_b][n]: ordered(max g)
 };
-
-// COPIES of pairwise_topk.inc (which copies pairwise.hip), kept here so that the machine code of
-// those kernels cannot move with this file: uniform_pointer, off256, the ring constants above,
-// max16, and in the kernel the `request` and `multiply` lambdas and the loop around them.  A fix
-// to the DMA addressing, to the swizzle or to the key forms there has to be made here too, and
-// the other way round.
-template <class T>
-__device__ __forceinline__ const T* uniform_pointer(const T* pointer) {
-  const uint64_t bits = (uint64_t)(uintptr_t)pointer;
-  const uint32_t low = __builtin_amdgcn_readfirstlane((uint32_t)bits);
-  const uint32_t high = __builtin_amdgcn_readfirstlane((uint32_t)(bits >> 32));
-  return reinterpret_cast<const T*>(((uint64_t)high << 32) | low);
-}
-
-__device__ __forceinline__ int off256(int row, int chunk) {
-  return row * 256 + ((chunk ^ (row & 15)) << 4);
-}
-
-__device__ __forceinline__ float max16(const f32x16& g) {
-  float high = __builtin_fmaxf(g[0], g[1]);
-#pragma unroll
-  for (int q = 2; q < 16; q += 2)
-    high = __builtin_fmaxf(__builtin_fmaxf(high, g[q]), g[q + 1]);   // v_max3_f32
-  return high;
-}
 
 // max16 over the lane's values whose b-row lies in [from, from + count): b-row of position q is
 // jb + 8 (q >> 2) + (q & 3); one unsigned comparison since 0 <= from <= from + count < 2^31
@@ -107,14 +76,11 @@ __device__ __forceinline__ float unordered(uint32_t u) {
   return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu));
 }
 
-// the value of k_nearest_finish for the maximum g of an (a-row, record) pair
+// the value of k_nearest_finish for the maximum g of an (a-row, record) pair: the key is -2 g (L2)
+// or -g (cosine), both exact
 __device__ __forceinline__ float value_of(uint32_t bits, float a_term, int metric) {
   const float g = unordered(bits);
-  if (metric == GFY_L2) {
-    const float d2 = a_term + -2.0f * g;   // -2 g: the key, exact
-    return __builtin_sqrtf(d2 > 0.f ? d2 : 0.f);
-  }
-  return g * a_term;   // -key * a_term, key = -g
+  return pair_value(metric == GFY_L2 ? -2.0f * g : -g, a_term, metric);
 }
 
 template <bool kFold>
@@ -133,57 +99,15 @@ __global__ __launch_bounds__(kThreads, 1) void k_record_sweep(const RecordArgs p
   const int64_t j_begin = (int64_t)chunk * p.chunk_rows;
   const int64_t j_end = j_begin + p.chunk_rows < p.m ? j_begin + p.chunk_rows : p.m;
 
-  // one b-tile -> its ring buffer, (s, t) -> the term ring.  A copy: see the note at
-  // uniform_pointer — change all or none.
   auto request = [&](int k) __attribute__((always_inline)) {
-    const int64_t j0 = j_begin + (int64_t)k * kTileB;
-    const uint32_t base = lds0 + (uint32_t)(k & (kBuffers - 1)) * kRowBytes;
-    const f16* rows = uniform_pointer(p.b + j0 * 128);
-    uint32_t me = threadIdx.x;
-    asm volatile("" : "+v"(me));
-    const uint32_t sub = (me >> 4) & 3u, slot = me & 15u;
-    const uint32_t at_home = ((uint32_t)(16 * wave) + sub) * 256u + ((slot ^ sub) << 4);
-    if (j0 + kTileB <= p.m) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        dma16(rows, (at_home ^ (uint32_t)(q << 6)) + 1024u * q,
-              base + (uint32_t)(wave * 4 + q) * 1024u);
-    } else {   // ragged last tile: rows past the end re-read the last row (their t never wins)
-      const int last = (int)(p.m - 1 - j0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint32_t full = (at_home ^ (uint32_t)(q << 6)) + 1024u * q;
-        const int row = (int)(full >> 8);   // 16 wave + 4 q + sub
-        const int from = row < last ? row : last;
-        dma16(rows, (uint32_t)from * 256u + (full & 255u),
-              base + (uint32_t)(wave * 4 + q) * 1024u);
-      }
-    }
-    if (wave < (kFold ? 1 : 2) && (me & 32u) == 0)   // 128 floats = 32 lanes x 16 B
-      dma16(uniform_pointer((wave == 0 && !kFold ? p.s : p.t) + j0), (me & 31u) * 16u,
-            lds0 + kBuffers * kRowBytes + (uint32_t)(k & (kTermSlots - 1)) * kTermBytes
-                + (uint32_t)(kFold ? 1 : wave) * (kTileB * 4));
+    sweep_request<kFold>(p, lds0, wave, j_begin, k);
   };
 
-  // stage the a-block through LDS once (coalesced), then keep all its fragments in registers
-  {
-    char* atile = smem + kRowBytes;   // buffer 1 (32 KB), not yet in use
-    for (int i = t; i < kBlockA * 16; i += kThreads) {
-      const int row = i >> 4, ch = i & 15;
-      f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (a0 + row < p.n) v = *reinterpret_cast<const f16x8*>(p.a + (a0 + row) * 128 + ch * 8);
-      *reinterpret_cast<f16x8*>(atile + off256(row, ch)) = v;
-    }
-  }
+  stage_a_block<kBlockA>(smem, p.a, p.n, a0);
   if (j_begin < j_end) request(0);
   __syncthreads();
   f16x8 af[2][8];
-#pragma unroll
-  for (int at = 0; at < 2; ++at)
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-      af[at][ks] = *reinterpret_cast<const f16x8*>(
-          smem + kRowBytes + off256(64 * wa + 32 * at + r, 2 * ks + hq));
+  load_a_fragments<2>(af, smem, wa, r, hq);
 
   __syncthreads();   // the a-block has left buffer 1
   const int tiles = j_begin < j_end ? (int)((j_end - j_begin + kTileB - 1) / kTileB) : 0;
@@ -224,34 +148,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_record_sweep(const RecordArgs p
   f32x16 acc[2];   // [at]
   const int jw = 32 * wb + 4 * hq;   // first of this lane's b-rows inside a tile
   auto multiply = [&](int k) __attribute__((always_inline)) {
-    const char* tile = smem + (k & (kBuffers - 1)) * kRowBytes;
-    f32x16 start = {};   // what every chain starts from: 0, or (kFold) -|b_j|^2 / 2 of the lane's 16 b-rows
-    if constexpr (kFold) {
-      const float* u_l = reinterpret_cast<const float*>(
-          smem + kBuffers * kRowBytes + (k & (kTermSlots - 1)) * kTermBytes) + kTileB;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 uv = *reinterpret_cast<const f32x4*>(u_l + jw + 8 * g);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) start[4 * g + i] = uv[i];
-      }
-    }
-    constexpr int kAheadK = 2, kRing = kAheadK + 1;
-    f16x8 bf[kRing];   // [ks % kRing]
-#pragma unroll
-    for (int ks = 0; ks < kAheadK; ++ks)
-      bf[ks] = *reinterpret_cast<const f16x8*>(tile + off256(32 * wb + r, 2 * ks + hq));
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      if (ks + kAheadK < 8)
-        bf[(ks + kAheadK) % kRing] = *reinterpret_cast<const f16x8*>(
-            tile + off256(32 * wb + r, 2 * (ks + kAheadK) + hq));
-      __builtin_amdgcn_sched_barrier(0);   // operand reads stay ahead of their MFMAs (pairwise.hip)
-#pragma unroll
-      for (int at = 0; at < 2; ++at)
-        acc[at] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[ks % kRing], af[at][ks],
-                                                         ks == 0 ? start : acc[at], 0, 0, 0);
-    }
+    sweep_multiply<2, kFold>(acc, af, smem, k, wb, r, hq);
   };
 
   // what happens to the products of tile k (still in acc)
@@ -262,8 +159,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_record_sweep(const RecordArgs p
     const int w_lo = j0 + 32 * wb, w_hi = w_lo + 32;   // this wave's b-rows
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (!kFold) {
-      const float* s_l = reinterpret_cast<const float*>(
-          smem + kBuffers * kRowBytes + (k & (kTermSlots - 1)) * kTermBytes);
+      const float* s_l = sweep_terms(smem, k);
       const float* t_l = s_l + kTileB;
 #pragma unroll
       for (int at = 0; at < 2; ++at)
@@ -308,21 +204,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_record_sweep(const RecordArgs p
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // Two tiles per barrier: the ring holds the pair being consumed and the pair in flight; the
-  // next pair is requested behind the first multiply (pairwise.hip).
-  for (int ti = 0; ti < tiles; ti += 2) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): this wave's share of the pair
-    asm volatile("" ::: "memory");
-    __syncthreads();                             // everybody's share; the previous pair is spent
-    multiply(ti);
-    if (ti + 2 < tiles) request(ti + 2);
-    if (ti + 3 < tiles) request(ti + 3);
-    reduce(ti);
-    if (ti + 1 < tiles) {
-      multiply(ti + 1);
-      reduce(ti + 1);
-    }
-  }
+  sweep_tile_pairs(tiles, multiply, request, reduce);
   if (dirty) flush(rec);   // the record that goes on behind the chunk, or the last one
 }
 
@@ -380,60 +262,19 @@ __global__ __launch_bounds__(256) void k_record_finish_scores(
 struct RecordWorkspace {
   float *s, *t, *a_term;
   uint32_t* bits;
-  int blocks_a, chunks;
-  int64_t chunk_rows;
+  BSplit split;
   size_t bytes;
 };
 
-// Layout: s and t (tiles_b * 128 floats each), a_term (n floats), bits ([records_b][n] words),
-// every array rounded up to 256 bytes.  The split of b into chunks is that of carve_topk
-// (pairwise_topk.hip) — a copy, change both: enough workgroups for four per CU, and of the next
-// few counts the one whose grid ends in the fewest sweeps.
+// Layout: the terms (pairwise_sweep.inc), then bits ([records_b][n] words)
 RecordWorkspace carve_records(void* base, int64_t n, int64_t m, int64_t records_b) {
   RecordWorkspace w;
-  w.blocks_a = (int)((n + kBlockA - 1) / kBlockA);
-  const int64_t tiles_b = (m + kTileB - 1) / kTileB;
-  int64_t chunks = (1024 + w.blocks_a - 1) / w.blocks_a;
-  {
-    constexpr int64_t kCus = 256;   // MI355X; another part only loses the fit
-    const int64_t least = chunks;
-    double best = 1e300;
-    for (int64_t c = least; c < least + 6; ++c) {
-      const double sweeps = (double)((w.blocks_a * c + kCus - 1) / kCus) / (double)c;
-      if (sweeps < best * 0.99) best = sweeps, chunks = c;   // a later count only for a real gain
-    }
-  }
-  if (chunks > tiles_b) chunks = tiles_b;
-  if (chunks < 1) chunks = 1;
-  const int64_t tiles_per_chunk = (tiles_b + chunks - 1) / chunks;
-  w.chunk_rows = tiles_per_chunk * kTileB;
-  w.chunks = (int)((tiles_b + tiles_per_chunk - 1) / tiles_per_chunk);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* ptr = base ? (char*)base + off : nullptr;
-    off += align_up(bytes, 256);
-    return ptr;
-  };
-  w.s = (float*)take((size_t)tiles_b * kTileB * 4);   // padded to whole tiles
-  w.t = (float*)take((size_t)tiles_b * kTileB * 4);
-  w.a_term = (float*)take((size_t)n * 4);
-  w.bits = (uint32_t*)take((size_t)records_b * (size_t)n * 4);
-  w.bytes = off;
+  Carver carver{base};
+  w.split = split_b(n, m, kBlockA);
+  carver.terms(n, m, w.s, w.t, w.a_term);
+  w.bits = (uint32_t*)carver.take((size_t)records_b * (size_t)n * 4);
+  w.bytes = carver.bytes;
   return w;
-}
-
-template <bool kFold>
-int launch_sweep(const RecordArgs& p, hipStream_t s) {
-  static_assert(kRecordLds <= 160 * 1024, "the LDS of a compute unit");
-  static PerDeviceOnce opt_in;   // > 64 KB of dynamic LDS: once per device (gfy_common.h)
-  if (const int rc = opt_in.run([]() -> int {
-        GFY_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_record_sweep<kFold>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, kRecordLds));
-        return GFY_OK;
-      }))
-    return rc;
-  k_record_sweep<kFold><<<p.blocks_a * p.chunks, kThreads, kRecordLds, s>>>(p);
-  return GFY_OK;
 }
 
 }  // namespace
@@ -442,7 +283,7 @@ size_t pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_b) 
   return carve_records(nullptr, n, m, records_b).bytes;
 }
 
-int pairwise_record_chunks(int64_t n, int64_t m) { return carve_records(nullptr, n, m, 1).chunks; }
+int pairwise_record_chunks(int64_t n, int64_t m) { return split_b(n, m, kBlockA).chunks; }
 
 // ptr_a == nullptr: out is best [n][records_b]; else out is scores [records_a][records_b]
 int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, int metric,
@@ -468,13 +309,16 @@ int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, 
   p.t = w.t;
   p.n = n;
   p.m = m;
-  p.blocks_a = w.blocks_a;
-  p.chunks = w.chunks;
-  p.chunk_rows = w.chunk_rows;
+  p.blocks_a = w.split.blocks_a;
+  p.chunks = w.split.chunks;
+  p.chunk_rows = w.split.chunk_rows;
   p.ptr_b = ptr_b;
   p.records_b = (int)records_b;
   p.bits = w.bits;
-  if (const int rc = fold ? launch_sweep<true>(p, s) : launch_sweep<false>(p, s)) return rc;
+  const int grid = p.blocks_a * p.chunks;
+  if (const int rc = fold ? launch_sweep<&k_record_sweep<true>, kSweepLds>(p, grid, s)
+                          : launch_sweep<&k_record_sweep<false>, kSweepLds>(p, grid, s))
+    return rc;
   if (ptr_a) {
     const dim3 grid((unsigned)records_a, (unsigned)((records_b + 63) / 64));
     k_record_finish_scores<<<grid, 256, 0, s>>>(w.bits, w.a_term, ptr_a, n, (int)records_b, metric,

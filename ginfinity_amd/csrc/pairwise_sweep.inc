@@ -1,0 +1,273 @@
+// The all-pairs sweep that nearest (pairwise.hip), top-k (pairwise_topk.inc) and the record
+// scores (pairwise_records.hip) share — the ONLY copy of: the b-tile ring and its LDS-DMA request,
+// the staging of the a-block, the MFMA multiply of one tile, the two-tiles-per-barrier loop, the
+// value formula, the split of b into chunks, the front of the workspace and the launch with
+// more than 64 KB of LDS.  Included after gfy_common.h; everything is inlined into the kernels of
+// the including file, whose a-block size (kBlockA: 256 or 128 rows) and epilogue are their own.
+//
+// A workgroup of 8 waves keeps the MFMA fragments of its a-block in registers and sweeps its
+// chunk of b in 128-row tiles that LDS-DMA lands in a ring of four buffers, XOR-swizzled so that
+// the operand reads are conflict-free; the (s, t) terms of a tile travel the same way into a
+// ring of their own behind the rows.  The product is (B-tile) x (A-block)^T: the a-row sits on
+// the MFMA lane and a lane's 16 accumulator registers are 4 x 4 consecutive b-rows.
+
+namespace gfy {
+namespace {
+
+constexpr int kTileB = 128;   // b-rows per LDS tile
+constexpr int kThreads = 512;
+constexpr int kBuffers = 4;   // b-tile ring: tile i is consumed while the next ones are in flight
+constexpr int kRowBytes = kTileB * 256;        // one b-tile of rows
+constexpr int kTermBytes = 2 * kTileB * 4;     // its (s, t)
+constexpr int kTermSlots = 4;                  // (s, t) ring, like the rows
+// row ring (its buffers from 1 on stage the a-block first) + (s, t) ring
+constexpr int kSweepLds = kBuffers * kRowBytes + kTermSlots * kTermBytes;
+
+template <class T>
+__device__ __forceinline__ const T* uniform_pointer(const T* pointer) {
+  const uint64_t bits = (uint64_t)(uintptr_t)pointer;
+  const uint32_t low = __builtin_amdgcn_readfirstlane((uint32_t)bits);
+  const uint32_t high = __builtin_amdgcn_readfirstlane((uint32_t)(bits >> 32));
+  return reinterpret_cast<const T*>(((uint64_t)high << 32) | low);
+}
+
+// byte offset of 16-byte piece `chunk` of row `row` in a swizzled tile of 256-byte rows
+__device__ __forceinline__ int off256(int row, int chunk) {
+  return row * 256 + ((chunk ^ (row & 15)) << 4);
+}
+
+__device__ __forceinline__ float max16(const f32x16& g) {
+  float high = __builtin_fmaxf(g[0], g[1]);
+#pragma unroll
+  for (int q = 2; q < 16; q += 2)
+    high = __builtin_fmaxf(__builtin_fmaxf(high, g[q]), g[q + 1]);   // v_max3_f32
+  return high;
+}
+
+// What leaves every search for the pair with key `key` (key_ij = fma(dot_ij, s_j, t_j), head of
+// pairwise.hip): L2 sqrt(max(|a_i|^2 + key, 0)) with a_term = |a_i|^2, cosine -key / |a_i| with
+// a_term = 1 / |a_i|.
+__device__ __forceinline__ float pair_value(float key, float a_term, int metric) {
+  if (metric == GFY_L2) {
+    const float d2 = a_term + key;
+    return __builtin_sqrtf(d2 > 0.f ? d2 : 0.f);
+  }
+  return -key * a_term;
+}
+
+// Tile k of the sweep that starts at b-row j_begin -> buffer k % kBuffers: 128 rows as 32 DMA
+// instructions (4 per wave, 4 rows each), (s, t) -> slot k % kTermSlots as one more by waves 0
+// and 1 (kFold: t alone, by wave 0).  Rows past the end re-read the last row; their t never wins
+// (k_row_terms pads s / t to whole tiles).  `p` is the kernel's argument struct (b, s, t, m).
+// Per-lane byte offset of its 16-byte piece q inside a tile: row 16 wave + 4 q + sub, slot
+// (lane & 15) ^ (row & 15)  =  (home ^ (q << 6)) + 1024 q  with ONE loop-invariant register
+// (`home`); the tile's base travels in SGPRs.  (64-bit per-lane pointers, or the four
+// offsets kept in registers, spilled — and a scratch reload is a vmcnt(0) wait that drains
+// the DMA look-ahead.  The asm keeps hipcc from hoisting them out of the loop again.)
+// `home` is rebuilt from threadIdx.x per request (six VALU operations): any loop-invariant
+// register here is one that hipcc spills in k_pairwise, which sits at the 256-register ceiling.
+template <bool kFold, class Args>
+__device__ __forceinline__ void sweep_request(const Args& p, uint32_t lds0, int wave,
+                                              int64_t j_begin, int k) {
+  const int64_t j0 = j_begin + (int64_t)k * kTileB;
+  const uint32_t base = lds0 + (uint32_t)(k & (kBuffers - 1)) * kRowBytes;
+  // wave-uniform, and said so: with a reduce carried over the barrier in the loop (k_pairwise)
+  // hipcc's divergence analysis puts j0 in vector registers, which the DMA's scalar base operand
+  // cannot take
+  const f16* rows = uniform_pointer(p.b + j0 * 128);
+  uint32_t me = threadIdx.x;
+  asm volatile("" : "+v"(me));
+  const uint32_t sub = (me >> 4) & 3u, slot = me & 15u;
+  const uint32_t at_home = ((uint32_t)(16 * wave) + sub) * 256u + ((slot ^ sub) << 4);
+  if (j0 + kTileB <= p.m) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      dma16(rows, (at_home ^ (uint32_t)(q << 6)) + 1024u * q,
+            base + (uint32_t)(wave * 4 + q) * 1024u);
+  } else {   // ragged last tile
+    const int last = (int)(p.m - 1 - j0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const uint32_t full = (at_home ^ (uint32_t)(q << 6)) + 1024u * q;
+      const int row = (int)(full >> 8);   // 16 wave + 4 q + sub
+      const int from = row < last ? row : last;
+      dma16(rows, (uint32_t)from * 256u + (full & 255u),
+            base + (uint32_t)(wave * 4 + q) * 1024u);
+    }
+  }
+  if (wave < (kFold ? 1 : 2) && (me & 32u) == 0)   // 128 floats = 32 lanes x 16 B
+    dma16(uniform_pointer((wave == 0 && !kFold ? p.s : p.t) + j0), (me & 31u) * 16u,
+          lds0 + kBuffers * kRowBytes + (uint32_t)(k & (kTermSlots - 1)) * kTermBytes
+              + (uint32_t)(kFold ? 1 : wave) * (kTileB * 4));
+}
+
+// (s, t) of tile k in the term ring: s at [0, kTileB), t behind it
+__device__ __forceinline__ const float* sweep_terms(const char* smem, int k) {
+  return reinterpret_cast<const float*>(smem + kBuffers * kRowBytes
+                                        + (k & (kTermSlots - 1)) * kTermBytes);
+}
+
+// The a-block [a0, a0 + kRows) through LDS once (coalesced; rows past n are zero), swizzled like
+// a b-tile, into the ring from buffer 1 on (kRows / 128 buffers, not yet in use).  A barrier
+// later load_a_fragments keeps ALL the fragments of the wave's 32 kTilesA a-rows in registers;
+// another barrier later the buffers are the ring's again.
+template <int kRows>
+__device__ __forceinline__ void stage_a_block(char* smem, const f16* a, int64_t n, int64_t a0) {
+  char* atile = smem + kRowBytes;
+  for (int i = threadIdx.x; i < kRows * 16; i += kThreads) {
+    const int row = i >> 4, ch = i & 15;
+    f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (a0 + row < n) v = *reinterpret_cast<const f16x8*>(a + (a0 + row) * 128 + ch * 8);
+    *reinterpret_cast<f16x8*>(atile + off256(row, ch)) = v;
+  }
+}
+
+template <int kTilesA>
+__device__ __forceinline__ void load_a_fragments(f16x8 (&af)[kTilesA][8], const char* smem, int wa,
+                                                 int r, int hq) {
+#pragma unroll
+  for (int at = 0; at < kTilesA; ++at)
+#pragma unroll
+    for (int ks = 0; ks < 8; ++ks)
+      af[at][ks] = *reinterpret_cast<const f16x8*>(
+          smem + kRowBytes + off256(32 * kTilesA * wa + 32 * at + r, 2 * ks + hq));
+}
+
+// The wave's 32 x (32 kTilesA) block of tile k into acc: kTilesA independent accumulator chains
+// (a 32x32x16 MFMA that reads the previous one's result stalls the issue port), the b operand
+// read kAheadK k-steps ahead.  Every chain starts from 0, or (kFold) from -|b_j|^2 / 2 of the
+// lane's 16 b-rows, so that what comes out is g_ij = a_i.b_j - |b_j|^2 / 2 (k_row_terms).
+template <int kTilesA, bool kFold>
+__device__ __forceinline__ void sweep_multiply(f32x16 (&acc)[kTilesA],
+                                               const f16x8 (&af)[kTilesA][8], const char* smem,
+                                               int k, int wb, int r, int hq) {
+  const char* tile = smem + (k & (kBuffers - 1)) * kRowBytes;
+  f32x16 start = {};
+  if constexpr (kFold) {
+    const float* u_l = sweep_terms(smem, k) + kTileB;
+    const int jw = 32 * wb + 4 * hq;   // first of this lane's b-rows inside a tile
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      const f32x4 uv = *reinterpret_cast<const f32x4*>(u_l + jw + 8 * g);
+#pragma unroll
+      for (int i = 0; i < 4; ++i) start[4 * g + i] = uv[i];
+    }
+  }
+  constexpr int kAheadK = 2, kRing = kAheadK + 1;
+  f16x8 bf[kRing];   // [ks % kRing]
+#pragma unroll
+  for (int ks = 0; ks < kAheadK; ++ks)
+    bf[ks] = *reinterpret_cast<const f16x8*>(tile + off256(32 * wb + r, 2 * ks + hq));
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    if (ks + kAheadK < 8)
+      bf[(ks + kAheadK) % kRing] = *reinterpret_cast<const f16x8*>(
+          tile + off256(32 * wb + r, 2 * (ks + kAheadK) + hq));
+    // hipcc otherwise sinks every operand read down to its MFMAs (one register quad,
+    // read -> lgkmcnt(0) -> MFMAs: the LDS latency exposed eight times a tile)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int at = 0; at < kTilesA; ++at)
+      acc[at] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[ks % kRing], af[at][ks],
+                                                       ks == 0 ? start : acc[at], 0, 0, 0);
+  }
+}
+
+// Two tiles per barrier: the ring holds the pair being consumed and the pair in flight (tiles 0
+// and 1 are requested by the caller).  Between two barriers each wave runs multiply, reduce,
+// multiply, reduce on its own, so the two waves of a SIMD interleave.  The next pair is requested
+// BEHIND the first multiply: issuing a tile's DMA pieces costs a wave several hundred cycles, and
+// right behind the barrier all eight waves would pay them at once with the matrix cores idle.
+template <class Multiply, class Request, class Reduce>
+__device__ __forceinline__ void sweep_tile_pairs(int tiles, Multiply&& multiply, Request&& request,
+                                                 Reduce&& reduce) {
+  for (int ti = 0; ti < tiles; ti += 2) {
+    __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): this wave's share of the pair
+    asm volatile("" ::: "memory");
+    __syncthreads();                             // everybody's share; the previous pair is spent
+    multiply(ti);
+    if (ti + 2 < tiles) request(ti + 2);
+    if (ti + 3 < tiles) request(ti + 3);
+    reduce(ti);
+    if (ti + 1 < tiles) {
+      multiply(ti + 1);
+      reduce(ti + 1);
+    }
+  }
+}
+
+// ---- host side ---------------------------------------------------------------------------------
+
+// How a sweep of n a-rows (in blocks of block_a) against m b-rows is cut: b into `chunks` pieces
+// of chunk_rows rows (whole tiles), one workgroup per (a-block, chunk).
+struct BSplit {
+  int blocks_a, chunks;
+  int64_t chunk_rows;   // multiple of kTileB
+};
+
+// Enough workgroups for four per CU (1024), and of the next few chunk counts the one whose grid
+// ends in the fewest sweeps.  One workgroup per CU at a time, all of one length: a grid of
+// blocks_a x chunks workgroups ends after ceil(grid / CUs) of them, each 1 / chunks of a sweep
+// long.  1,000,000 rows are 3,907 a-blocks of 256 = 15.26 per CU: one chunk ends after 16 sweeps,
+// three after 46 / 3 = 15.33.  A few more chunks than the minimum cost a merge entry per a-row
+// and chunk.  forced_chunks > 0 (diagnostic builds of pairwise.hip) replaces the choice.
+inline BSplit split_b(int64_t n, int64_t m, int block_a, int64_t forced_chunks = 0) {
+  BSplit w;
+  w.blocks_a = (int)((n + block_a - 1) / block_a);
+  const int64_t tiles_b = (m + kTileB - 1) / kTileB;
+  int64_t chunks = (1024 + w.blocks_a - 1) / w.blocks_a;
+  {
+    constexpr int64_t kCus = 256;   // MI355X; another part only loses the fit
+    const int64_t least = chunks;
+    double best = 1e300;
+    for (int64_t c = least; c < least + 6; ++c) {
+      const double sweeps = (double)((w.blocks_a * c + kCus - 1) / kCus) / (double)c;
+      if (sweeps < best * 0.99) best = sweeps, chunks = c;   // a later count only for a real gain
+    }
+  }
+  if (forced_chunks > 0) chunks = forced_chunks;
+  if (chunks > tiles_b) chunks = tiles_b;
+  if (chunks < 1) chunks = 1;
+  const int64_t tiles_per_chunk = (tiles_b + chunks - 1) / chunks;
+  w.chunk_rows = tiles_per_chunk * kTileB;
+  w.chunks = (int)((tiles_b + tiles_per_chunk - 1) / tiles_per_chunk);
+  return w;
+}
+
+// A workspace handed out front to back, every array rounded up to 256 bytes (base == nullptr:
+// only `bytes` is wanted).  Every sweep's workspace starts with terms(): s and t of b padded to
+// whole tiles, then the a-side term; what follows is the caller's.
+struct Carver {
+  void* base;
+  size_t bytes = 0;
+  void* take(size_t size) {
+    void* ptr = base ? (char*)base + bytes : nullptr;
+    bytes += align_up(size, 256);
+    return ptr;
+  }
+  void terms(int64_t n, int64_t m, float*& s, float*& t, float*& a_term) {
+    const size_t padded = (size_t)((m + kTileB - 1) / kTileB) * kTileB;
+    s = (float*)take(padded * 4);
+    t = (float*)take(padded * 4);
+    a_term = (float*)take((size_t)n * 4);
+  }
+};
+
+// kKernel<<<grid, kThreads, kLds>>>(p) with more than 64 KB of dynamic LDS: the opt-in once per
+// device and kernel, thread-safe (PerDeviceOnce, gfy_common.h)
+template <auto kKernel, int kLds, class Args>
+int launch_sweep(const Args& p, int grid, hipStream_t s) {
+  static_assert(kLds <= 160 * 1024, "the LDS of a compute unit");
+  static PerDeviceOnce opt_in;
+  if (const int rc = opt_in.run([]() -> int {
+        GFY_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
+        return GFY_OK;
+      }))
+    return rc;
+  kKernel<<<grid, kThreads, kLds, s>>>(p);
+  return GFY_OK;
+}
+
+}  // namespace
+}  // namespace gfy

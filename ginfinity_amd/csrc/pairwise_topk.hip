@@ -20,8 +20,8 @@
 // lane's D-th best, then __ballot; the extract-and-insert loop runs only when a lane beats it.
 // After the sweep the ring is free: 128 rows x 8 holders (2 lane halves x 4 b-waves) x D x 8 B
 // (128 KB at D = 16) go there and one thread per a-row merges them.  The per-chunk lists go to
-// the workspace as [chunks][n][k]; k_topk_finish merges the chunks and applies the value formulas
-// of k_nearest_finish.
+// the workspace as [chunks][n][k]; k_topk_finish merges the chunks and applies pair_value, the
+// value formula of k_nearest_finish.
 //
 // Ranges (gfy_pairwise_topk_ranges; instantiated in pairwise_topk_ranges.hip from the same
 // pairwise_topk.inc): every a-row skips a half-open range of b-rows, its own record in a
@@ -41,94 +41,34 @@
 namespace gfy {
 namespace {
 
-// one thread per a-row: the chunks' lists (each sorted by (key, index), chunks in ascending
-// index order) into one, then the values of k_nearest_finish
+// topk_finish (pairwise_topk.inc) for the plain lists
 __global__ __launch_bounds__(256) void k_topk_finish(const float* __restrict__ part_key,
                                                      const int32_t* __restrict__ part_idx,
                                                      const float* __restrict__ a_term, int64_t n,
                                                      int chunks, int k, int metric,
                                                      float* __restrict__ top_val,
                                                      int32_t* __restrict__ top_idx) {
-  constexpr int D = GFY_PAIRWISE_TOPK_MAX;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float lk[D];   // -key, descending
-  int li[D];
-#pragma unroll
-  for (int q = 0; q < D; ++q) {
-    lk[q] = -__builtin_inff();
-    li[q] = kNoIndex;
-  }
-  for (int c = 0; c < chunks; ++c) {
-    const float* keys = part_key + ((int64_t)c * n + i) * k;
-    const int32_t* idx = part_idx + ((int64_t)c * n + i) * k;
-    for (int q = 0; q < k; ++q) {
-      const float g = -keys[q];
-      if (!(g > lk[D - 1])) break;   // sorted: nothing behind it gets in either
-      list_insert<D>(lk, li, g, idx[q]);
-    }
-  }
-  const float at = a_term[i];
-#pragma unroll
-  for (int q = 0; q < D; ++q) {
-    if (q < k) {
-      const float v = -lk[q];
-      float out;
-      if (metric == GFY_L2) {
-        const float d2 = at + v;
-        out = __builtin_sqrtf(d2 > 0.f ? d2 : 0.f);
-      } else {
-        out = -v * at;
-      }
-      top_val[i * k + q] = out;
-      top_idx[i * k + q] = li[q] == kNoIndex ? -1 : li[q];
-    }
-  }
+  topk_finish<false>(part_key, part_idx, a_term, nullptr, nullptr, n, chunks, k, metric, top_val,
+                     top_idx);
 }
 
 struct TopkWorkspace {
   float *s, *t, *a_term, *part_key;
   int32_t* part_idx;
-  int blocks_a, chunks;
-  int64_t chunk_rows;
+  BSplit split;
   size_t bytes;
 };
 
-// Layout: s and t (tiles_b * 128 floats each), a_term (n floats), part_key and part_idx
-// ([chunks][n][k] each), every array rounded up to 256 bytes.  chunks: enough workgroups for
-// four per CU, and of the next few counts the one whose grid ends in the fewest sweeps (the
-// reasoning of carve() in pairwise.hip, for 128-row a-blocks); it does not depend on k.
+// Layout: the terms (pairwise_sweep.inc), then part_key and part_idx ([chunks][n][k] each); the
+// split of b does not depend on k
 TopkWorkspace carve_topk(void* base, int64_t n, int64_t m, int k) {
   TopkWorkspace w;
-  w.blocks_a = (int)((n + kBlockA - 1) / kBlockA);
-  const int64_t tiles_b = (m + kTileB - 1) / kTileB;
-  int64_t chunks = (1024 + w.blocks_a - 1) / w.blocks_a;
-  {
-    constexpr int64_t kCus = 256;   // MI355X; another part only loses the fit
-    const int64_t least = chunks;
-    double best = 1e300;
-    for (int64_t c = least; c < least + 6; ++c) {
-      const double sweeps = (double)((w.blocks_a * c + kCus - 1) / kCus) / (double)c;
-      if (sweeps < best * 0.99) best = sweeps, chunks = c;   // a later count only for a real gain
-    }
-  }
-  if (chunks > tiles_b) chunks = tiles_b;
-  if (chunks < 1) chunks = 1;
-  const int64_t tiles_per_chunk = (tiles_b + chunks - 1) / chunks;
-  w.chunk_rows = tiles_per_chunk * kTileB;
-  w.chunks = (int)((tiles_b + tiles_per_chunk - 1) / tiles_per_chunk);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    void* ptr = base ? (char*)base + off : nullptr;
-    off += align_up(bytes, 256);
-    return ptr;
-  };
-  w.s = (float*)take((size_t)tiles_b * kTileB * 4);   // padded to whole tiles
-  w.t = (float*)take((size_t)tiles_b * kTileB * 4);
-  w.a_term = (float*)take((size_t)n * 4);
-  w.part_key = (float*)take((size_t)w.chunks * n * k * 4);
-  w.part_idx = (int32_t*)take((size_t)w.chunks * n * k * 4);
-  w.bytes = off;
+  Carver carver{base};
+  w.split = split_b(n, m, kBlockA);
+  carver.terms(n, m, w.s, w.t, w.a_term);
+  w.part_key = (float*)carver.take((size_t)w.split.chunks * n * k * 4);
+  w.part_idx = (int32_t*)carver.take((size_t)w.split.chunks * n * k * 4);
+  w.bytes = carver.bytes;
   return w;
 }
 
@@ -161,9 +101,9 @@ int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int
   p.m = m;
   p.exclude_offset = exclude_offset;
   p.exclude_on = exclude_on;
-  p.blocks_a = w.blocks_a;
-  p.chunks = w.chunks;
-  p.chunk_rows = w.chunk_rows;
+  p.blocks_a = w.split.blocks_a;
+  p.chunks = w.split.chunks;
+  p.chunk_rows = w.split.chunk_rows;
   p.k = k;
   p.part_key = w.part_key;
   p.part_idx = w.part_idx;
@@ -175,14 +115,12 @@ int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int
     if (const int rc = launch_topk_sweep_distinct(p, fold, s)) return rc;
     return launch_topk_finish_distinct(p, w.a_term, metric, top_val, top_idx, s);
   }
-  int rc;
-  if (skip_lo) rc = launch_topk_sweep_ranges(p, fold, s);   // per-row ranges: pairwise_topk_ranges.hip
-  else if (k <= 4) rc = fold ? launch_sweep<4, true, false>(p, s) : launch_sweep<4, false, false>(p, s);
-  else if (k <= 8) rc = fold ? launch_sweep<8, true, false>(p, s) : launch_sweep<8, false, false>(p, s);
-  else rc = fold ? launch_sweep<16, true, false>(p, s) : launch_sweep<16, false, false>(p, s);
-  if (rc) return rc;
+  // per-row ranges: the instantiations of pairwise_topk_ranges.hip
+  if (const int rc = skip_lo ? launch_topk_sweep_ranges(p, fold, s)
+                             : launch_topk_sweep<false>(p, fold, s))
+    return rc;
   k_topk_finish<<<(int)((n + 255) / 256), 256, 0, s>>>(w.part_key, w.part_idx, w.a_term, n,
-                                                        w.chunks, k, metric, top_val, top_idx);
+                                                        p.chunks, k, metric, top_val, top_idx);
   GFY_CHECK_HIP(hipGetLastError());
   return GFY_OK;
 }

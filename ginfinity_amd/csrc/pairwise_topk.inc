@@ -1,10 +1,13 @@
-// The sweep of the exact top-k search: k_pairwise_topk<D, kFold, kRanges, kDistinct> and its
-// launcher (the design is told at the head of pairwise_topk.hip).
+// The sweep of the exact top-k search: k_pairwise_topk<D, kFold, kRanges, kDistinct>, its
+// launcher and the merge of the chunks' lists, topk_finish<kDistinct> (the design is told at the
+// head of pairwise_topk.hip; the ring, the tile request, the multiply and the tile loop are those
+// of pairwise_sweep.inc).
 // Included by the three translation units that instantiate it: pairwise_topk.hip (kRanges =
 // false: one excluded pair per a-row at most), pairwise_topk_ranges.hip (kRanges = true: an
 // excluded range of b-rows per a-row) and pairwise_topk_distinct.hip (kDistinct = true: at most
 // one hit per record of b, told at its head), so that the device code of the one does not move
 // with the others.
+#include "pairwise_sweep.inc"
 
 namespace gfy {
 
@@ -38,13 +41,6 @@ int launch_topk_finish_distinct(const TopkArgs& p, const float* a_term, int metr
 namespace {
 
 constexpr int kBlockA = 128;  // a-rows per workgroup
-constexpr int kTileB = 128;   // b-rows per LDS tile
-constexpr int kThreads = 512;
-constexpr int kBuffers = 4;   // b-tile ring: the pair being consumed and the pair in flight
-constexpr int kRowBytes = kTileB * 256;        // one b-tile of rows
-constexpr int kTermBytes = 2 * kTileB * 4;     // its (s, t)
-constexpr int kTermSlots = 4;                  // (s, t) ring, like the rows
-constexpr int kTopkLds = kBuffers * kRowBytes + kTermSlots * kTermBytes;
 constexpr int kRangeBytes = kBlockA * 8;       // kRanges: (first, count) of every a-row, behind the rings
 constexpr int kGroupBytes = 2 * kTileB * 4;    // kDistinct: (group_lo, group_hi) of a b-tile, a
 constexpr int kGroupSlots = 4;                 // ring like that of the terms, behind the ranges
@@ -52,23 +48,6 @@ constexpr int kHolders = 8;                    // lists per a-row at the end of 
 constexpr int kNoIndex = 0x7fffffff;
 static_assert(kHolders * GFY_PAIRWISE_TOPK_MAX * kBlockA * 8 <= kBuffers * kRowBytes,
               "the holders' lists are merged in the row ring");
-
-// COPIES of pairwise.hip, kept here so that the machine code of its kernels cannot move with
-// this file: uniform_pointer, off256, the ring constants above (kTileB, kBuffers, kRowBytes,
-// kTermBytes, kTermSlots) and the `request` lambda of the kernel (the LDS-DMA addressing of a
-// b-tile and of its terms).  A fix to the DMA addressing or to the swizzle there has to be made
-// here too, and the other way round.
-template <class T>
-__device__ __forceinline__ const T* uniform_pointer(const T* pointer) {
-  const uint64_t bits = (uint64_t)(uintptr_t)pointer;
-  const uint32_t low = __builtin_amdgcn_readfirstlane((uint32_t)bits);
-  const uint32_t high = __builtin_amdgcn_readfirstlane((uint32_t)(bits >> 32));
-  return reinterpret_cast<const T*>(((uint64_t)high << 32) | low);
-}
-
-__device__ __forceinline__ int off256(int row, int chunk) {
-  return row * 256 + ((chunk ^ (row & 15)) << 4);
-}
 
 // (ck, ci) into a list sorted by g descending; the entry that falls off the end is dropped.
 // Strict: among equal values the entries already there (lower indices) stay in front.  From the
@@ -126,14 +105,6 @@ __device__ __forceinline__ void dma4(const void* gbase /* uniform */, uint32_t g
       : "memory");
 }
 
-__device__ __forceinline__ float max16(const f32x16& g) {
-  float high = __builtin_fmaxf(g[0], g[1]);
-#pragma unroll
-  for (int q = 2; q < 16; q += 2)
-    high = __builtin_fmaxf(__builtin_fmaxf(high, g[q]), g[q + 1]);   // v_max3_f32
-  return high;
-}
-
 template <int D, bool kFold, bool kRanges, bool kDistinct>
 __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p) {
   static_assert(kRanges || !kDistinct, "the distinct sweep takes its exclusions as ranges");
@@ -151,68 +122,33 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
   const int64_t j_begin = (int64_t)chunk * p.chunk_rows;
   const int64_t j_end = j_begin + p.chunk_rows < p.m ? j_begin + p.chunk_rows : p.m;
 
-  // one b-tile -> its ring buffer, (s, t) -> the term ring: the request of pairwise.hip (per-lane
-  // offsets rebuilt per request, the tile's base in SGPRs; the reasons are recorded there).
-  // A copy: see the note at uniform_pointer — change both or neither.
   auto request = [&](int k) __attribute__((always_inline)) {
-    const int64_t j0 = j_begin + (int64_t)k * kTileB;
-    const uint32_t base = lds0 + (uint32_t)(k & (kBuffers - 1)) * kRowBytes;
-    const f16* rows = uniform_pointer(p.b + j0 * 128);
-    uint32_t me = threadIdx.x;
-    asm volatile("" : "+v"(me));
-    const uint32_t sub = (me >> 4) & 3u, slot = me & 15u;
-    const uint32_t at_home = ((uint32_t)(16 * wave) + sub) * 256u + ((slot ^ sub) << 4);
-    if (j0 + kTileB <= p.m) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-        dma16(rows, (at_home ^ (uint32_t)(q << 6)) + 1024u * q,
-              base + (uint32_t)(wave * 4 + q) * 1024u);
-    } else {   // ragged last tile: rows past the end re-read the last row (their t never wins)
-      const int last = (int)(p.m - 1 - j0);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const uint32_t full = (at_home ^ (uint32_t)(q << 6)) + 1024u * q;
-        const int row = (int)(full >> 8);   // 16 wave + 4 q + sub
-        const int from = row < last ? row : last;
-        dma16(rows, (uint32_t)from * 256u + (full & 255u),
-              base + (uint32_t)(wave * 4 + q) * 1024u);
-      }
-    }
-    if (wave < (kFold ? 1 : 2) && (me & 32u) == 0)   // 128 floats = 32 lanes x 16 B
-      dma16(uniform_pointer((wave == 0 && !kFold ? p.s : p.t) + j0), (me & 31u) * 16u,
-            lds0 + kBuffers * kRowBytes + (uint32_t)(k & (kTermSlots - 1)) * kTermBytes
-                + (uint32_t)(kFold ? 1 : wave) * (kTileB * 4));
+    sweep_request<kFold>(p, lds0, wave, j_begin, k);
     if constexpr (kDistinct) {
       // the records of the tile's rows, behind the ranges: waves 4 .. 7 bring group_lo[0, 64),
       // group_lo[64, 128), group_hi[0, 64) and group_hi[64, 128), a dword per lane.  The arrays
       // end at m: the rows of a ragged tile past it re-read the last row's (their t never wins).
       if (wave >= 4) {
+        const int64_t j0 = j_begin + (int64_t)k * kTileB;
         const int part = wave - 4;
         const int last = (int)(p.m - 1 - j0);
+        uint32_t me = threadIdx.x;   // rebuilt per request, as in sweep_request
+        asm volatile("" : "+v"(me));
         const int row = 64 * (part & 1) + (int)(me & 63u);
         dma4(uniform_pointer((part < 2 ? p.group_lo : p.group_hi) + j0),
              (uint32_t)(row < last ? row : last) * 4u,
-             lds0 + kTopkLds + kRangeBytes + (uint32_t)(k & (kGroupSlots - 1)) * kGroupBytes
+             lds0 + kSweepLds + kRangeBytes + (uint32_t)(k & (kGroupSlots - 1)) * kGroupBytes
                  + (uint32_t)part * 256u);
       }
     }
   };
 
-  // stage the a-block through LDS once (coalesced), then keep all its fragments in registers
-  {
-    char* atile = smem + kRowBytes;   // buffer 1 (32 KB), not yet in use
-    for (int i = t; i < kBlockA * 16; i += kThreads) {
-      const int row = i >> 4, ch = i & 15;
-      f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (a0 + row < p.n) v = *reinterpret_cast<const f16x8*>(p.a + (a0 + row) * 128 + ch * 8);
-      *reinterpret_cast<f16x8*>(atile + off256(row, ch)) = v;
-    }
-  }
+  stage_a_block<kBlockA>(smem, p.a, p.n, a0);
   // kRanges: every a-row's range, clipped to [0, m), as (first, count) with 0 <= first and
   // first + count <= m < 2^31 (count 0: nothing, also for the rows past n); it stays in LDS
   // behind the rings for the whole sweep, so that a tile that needs it reads two words per
   // a-row slot and no register holds a bound in between
-  int2* const ranges = reinterpret_cast<int2*>(smem + kTopkLds);
+  int2* const ranges = reinterpret_cast<int2*>(smem + kSweepLds);
   if constexpr (kRanges) {
     if (t < kBlockA) {
       int lo = 0, hi = 0;
@@ -228,12 +164,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
   if (j_begin < j_end) request(0);
   __syncthreads();
   f16x8 af[2][8];
-#pragma unroll
-  for (int at = 0; at < 2; ++at)
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-      af[at][ks] = *reinterpret_cast<const f16x8*>(
-          smem + kRowBytes + off256(64 * wa + 32 * at + r, 2 * ks + hq));
+  load_a_fragments<2>(af, smem, wa, r, hq);
 
   // kRanges: [skip_from, skip_to) is the union of the block's non-empty ranges, the same in
   // every wave and held in SGPRs; a tile outside it takes the path of the other instantiations
@@ -272,34 +203,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
   f32x16 acc[2];   // [at]
   const int jw = 32 * wb + 4 * hq;   // first of this lane's b-rows inside a tile
   auto multiply = [&](int k) __attribute__((always_inline)) {
-    const char* tile = smem + (k & (kBuffers - 1)) * kRowBytes;
-    f32x16 start = {};   // what every chain starts from: 0, or (kFold) -|b_j|^2 / 2 of the lane's 16 b-rows
-    if constexpr (kFold) {
-      const float* u_l = reinterpret_cast<const float*>(
-          smem + kBuffers * kRowBytes + (k & (kTermSlots - 1)) * kTermBytes) + kTileB;
-#pragma unroll
-      for (int g = 0; g < 4; ++g) {
-        const f32x4 uv = *reinterpret_cast<const f32x4*>(u_l + jw + 8 * g);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) start[4 * g + i] = uv[i];
-      }
-    }
-    constexpr int kAheadK = 2, kRing = kAheadK + 1;
-    f16x8 bf[kRing];   // [ks % kRing]
-#pragma unroll
-    for (int ks = 0; ks < kAheadK; ++ks)
-      bf[ks] = *reinterpret_cast<const f16x8*>(tile + off256(32 * wb + r, 2 * ks + hq));
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      if (ks + kAheadK < 8)
-        bf[(ks + kAheadK) % kRing] = *reinterpret_cast<const f16x8*>(
-            tile + off256(32 * wb + r, 2 * (ks + kAheadK) + hq));
-      __builtin_amdgcn_sched_barrier(0);   // operand reads stay ahead of their MFMAs (pairwise.hip)
-#pragma unroll
-      for (int at = 0; at < 2; ++at)
-        acc[at] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bf[ks % kRing], af[at][ks],
-                                                         ks == 0 ? start : acc[at], 0, 0, 0);
-    }
+    sweep_multiply<2, kFold>(acc, af, smem, k, wb, r, hq);
   };
 
   // what happens to the products of tile k (still in acc)
@@ -317,8 +221,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
       __builtin_amdgcn_sched_barrier(0);   // one a-row at a time: its terms are not read early
       f32x16& g = acc[at];   // one a-row's 16 values at a time, in place: the products are spent
       if constexpr (!kFold) {
-        const float* s_l = reinterpret_cast<const float*>(
-            smem + kBuffers * kRowBytes + (k & (kTermSlots - 1)) * kTermBytes);
+        const float* s_l = sweep_terms(smem, k);
         const float* t_l = s_l + kTileB;
 #pragma unroll
         for (int q4 = 0; q4 < 4; ++q4) {
@@ -358,7 +261,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
         if constexpr (kDistinct) {
           // only now the candidate's record is looked at: two words of the tile's ring
           const int* lo_l = reinterpret_cast<const int*>(
-              smem + kTopkLds + kRangeBytes + (k & (kGroupSlots - 1)) * kGroupBytes);
+              smem + kSweepLds + kRangeBytes + (k & (kGroupSlots - 1)) * kGroupBytes);
           const int in_tile = jw + 8 * (first >> 2) + (first & 3);
           const int from = lo_l[in_tile];
           list_insert_distinct<D>(lk[at], li[at], better ? high : -__builtin_inff(),
@@ -376,22 +279,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  // Two tiles per barrier: the ring holds the pair being consumed and the pair in flight; the
-  // next pair is requested behind the first multiply (pairwise.hip: right behind the barrier all
-  // eight waves would pay the DMA issue at once with the matrix cores idle).
-  for (int ti = 0; ti < tiles; ti += 2) {
-    __builtin_amdgcn_s_waitcnt(0x0F70);          // vmcnt(0): this wave's share of the pair
-    asm volatile("" ::: "memory");
-    __syncthreads();                             // everybody's share; the previous pair is spent
-    multiply(ti);
-    if (ti + 2 < tiles) request(ti + 2);
-    if (ti + 3 < tiles) request(ti + 3);
-    reduce(ti);
-    if (ti + 1 < tiles) {
-      multiply(ti + 1);
-      reduce(ti + 1);
-    }
-  }
+  sweep_tile_pairs(tiles, multiply, request, reduce);
   __syncthreads();   // the merge below reuses the row ring
 
   // [holder][position][a-row]: a lane's stores and the merging thread's reads (at a position
@@ -411,6 +299,27 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
     uint64_t heads = 0;   // 8 bits per holder: entries taken from its list
     float* out_key = p.part_key + ((int64_t)chunk * p.n + a0 + t) * p.k;
     int32_t* out_idx = p.part_idx + ((int64_t)chunk * p.n + a0 + t) * p.k;
+    // the best of the eight holders' heads by (key, index): its holder, (bk, bi) the entry;
+    // bi == kNoIndex when every list is at its end or at its empty entries
+    auto best_head = [&](float& bk, int& bi) __attribute__((always_inline)) {
+      int bh = 0;
+      bk = -__builtin_inff();
+      bi = kNoIndex;
+#pragma unroll
+      for (int h = 0; h < kHolders; ++h) {
+        const int pos = (int)((heads >> (8 * h)) & 0xffu);
+        if (pos < D) {
+          const float hk = m_key[(h * D + pos) * kBlockA + t];
+          const int hi = m_idx[(h * D + pos) * kBlockA + t];
+          if (hk > bk || (hk == bk && hi < bi)) {
+            bk = hk;
+            bi = hi;
+            bh = h;
+          }
+        }
+      }
+      return bh;
+    };
     if constexpr (kDistinct) {
       // the best head is taken unless a column already holds a row of its record (looked up
       // where the caller keeps it: a record may lie in several holders' lists, its best row
@@ -420,22 +329,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
       for (int q = 0; q < D; ++q) taken[q] = kNoIndex;
       int c = 0;
       for (int step = 0; step < kHolders * D && c < p.k; ++step) {
-        float bk = -__builtin_inff();
-        int bi = kNoIndex, bh = 0;
-#pragma unroll
-        for (int h = 0; h < kHolders; ++h) {
-          const int pos = (int)((heads >> (8 * h)) & 0xffu);
-          if (pos < D) {
-            const float hk = m_key[(h * D + pos) * kBlockA + t];
-            const int hi = m_idx[(h * D + pos) * kBlockA + t];
-            if (hk > bk || (hk == bk && hi < bi)) {
-              bk = hk;
-              bi = hi;
-              bh = h;
-            }
-          }
-        }
-        if (bi == kNoIndex) break;   // every list is at its end or at its empty entries
+        float bk;
+        int bi;
+        const int bh = best_head(bk, bi);
+        if (bi == kNoIndex) break;
         heads += 1ull << (8 * bh);
         const int from = p.group_lo[bi], count = p.group_hi[bi] - from;
         bool seen = false;
@@ -455,21 +352,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
       }
     } else
     for (int c = 0; c < p.k; ++c) {
-      float bk = -__builtin_inff();
-      int bi = kNoIndex, bh = 0;
-#pragma unroll
-      for (int h = 0; h < kHolders; ++h) {
-        const int pos = (int)((heads >> (8 * h)) & 0xffu);
-        if (pos < D) {
-          const float hk = m_key[(h * D + pos) * kBlockA + t];
-          const int hi = m_idx[(h * D + pos) * kBlockA + t];
-          if (hk > bk || (hk == bk && hi < bi)) {
-            bk = hk;
-            bi = hi;
-            bh = h;
-          }
-        }
-      }
+      float bk;
+      int bi;
+      const int bh = best_head(bk, bi);
       heads += 1ull << (8 * bh);
       out_key[c] = kFold ? -2.0f * bk : -bk;   // back to keys: exact, order and ties carry over
       out_idx[c] = bi;
@@ -478,20 +363,73 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
 }
 
 template <int D, bool kFold, bool kRanges, bool kDistinct = false>
-int launch_sweep(const TopkArgs& p, hipStream_t s) {
-  constexpr int kLds = kTopkLds + (kRanges ? kRangeBytes : 0)
+int launch_topk_sweep(const TopkArgs& p, hipStream_t s) {
+  constexpr int kLds = kSweepLds + (kRanges ? kRangeBytes : 0)
                        + (kDistinct ? kGroupSlots * kGroupBytes : 0);
-  static_assert(kLds <= 160 * 1024, "the LDS of a compute unit");
-  static PerDeviceOnce opt_in;   // > 64 KB of dynamic LDS: once per device (gfy_common.h)
-  if (const int rc = opt_in.run([]() -> int {
-        GFY_CHECK_HIP(hipFuncSetAttribute(
-            reinterpret_cast<const void*>(&k_pairwise_topk<D, kFold, kRanges, kDistinct>),
-            hipFuncAttributeMaxDynamicSharedMemorySize, kLds));
-        return GFY_OK;
-      }))
-    return rc;
-  k_pairwise_topk<D, kFold, kRanges, kDistinct><<<p.blocks_a * p.chunks, kThreads, kLds, s>>>(p);
-  return GFY_OK;
+  return launch_sweep<&k_pairwise_topk<D, kFold, kRanges, kDistinct>, kLds>(
+      p, p.blocks_a * p.chunks, s);
+}
+
+// the sweep at the list depth p.k asks for, folded (L2) or not
+template <bool kRanges, bool kDistinct = false>
+int launch_topk_sweep(const TopkArgs& p, bool fold, hipStream_t s) {
+  if (p.k <= 4)
+    return fold ? launch_topk_sweep<4, true, kRanges, kDistinct>(p, s)
+                : launch_topk_sweep<4, false, kRanges, kDistinct>(p, s);
+  if (p.k <= 8)
+    return fold ? launch_topk_sweep<8, true, kRanges, kDistinct>(p, s)
+                : launch_topk_sweep<8, false, kRanges, kDistinct>(p, s);
+  return fold ? launch_topk_sweep<16, true, kRanges, kDistinct>(p, s)
+              : launch_topk_sweep<16, false, kRanges, kDistinct>(p, s);
+}
+
+// The body of the finish kernels, one thread per a-row: the chunks' lists (each sorted by (key,
+// index), chunks in ascending index order, so that an equal key met later has the higher index)
+// into one, then the values of k_nearest_finish.  kDistinct: the lists hold one entry per record
+// (group_lo, group_hi) and so does the result.  The kernels themselves are k_topk_finish
+// (pairwise_topk.hip) and k_topk_finish_distinct (pairwise_topk_distinct.hip).
+template <bool kDistinct>
+__device__ __forceinline__ void topk_finish(const float* __restrict__ part_key,
+                                            const int32_t* __restrict__ part_idx,
+                                            const float* __restrict__ a_term,
+                                            const int32_t* __restrict__ group_lo,
+                                            const int32_t* __restrict__ group_hi, int64_t n,
+                                            int chunks, int k, int metric,
+                                            float* __restrict__ top_val,
+                                            int32_t* __restrict__ top_idx) {
+  constexpr int D = kDistinct ? GFY_PAIRWISE_TOPK_DISTINCT_MAX : GFY_PAIRWISE_TOPK_MAX;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float lk[D];   // -key, descending
+  int li[D];
+#pragma unroll
+  for (int q = 0; q < D; ++q) {
+    lk[q] = -__builtin_inff();
+    li[q] = kNoIndex;
+  }
+  for (int c = 0; c < chunks; ++c) {
+    const float* keys = part_key + ((int64_t)c * n + i) * k;
+    const int32_t* idx = part_idx + ((int64_t)c * n + i) * k;
+    for (int q = 0; q < k; ++q) {
+      const float g = -keys[q];
+      if (!(g > lk[D - 1])) break;   // sorted: nothing behind it gets in either (empty: g = -inf)
+      if constexpr (kDistinct) {
+        const int j = idx[q];
+        const int from = group_lo[j];
+        list_insert_distinct<D>(lk, li, g, j, from, group_hi[j] - from);
+      } else {
+        list_insert<D>(lk, li, g, idx[q]);
+      }
+    }
+  }
+  const float at = a_term[i];
+#pragma unroll
+  for (int q = 0; q < D; ++q) {
+    if (q < k) {
+      top_val[i * k + q] = pair_value(-lk[q], at, metric);
+      top_idx[i * k + q] = li[q] == kNoIndex ? -1 : li[q];
+    }
+  }
 }
 
 }  // namespace

@@ -46,61 +46,20 @@
 namespace gfy {
 namespace {
 
-// k_topk_finish (pairwise_topk.hip) for lists with one entry per record: one thread per a-row,
-// the chunks' lists (each sorted by (key, index), chunks in ascending index order, so that an
-// equal key met later has the higher index) into one such list, then the same values
+// topk_finish (pairwise_topk.inc) for lists with one entry per record
 __global__ __launch_bounds__(256) void k_topk_finish_distinct(
     const float* __restrict__ part_key, const int32_t* __restrict__ part_idx,
     const float* __restrict__ a_term, const int32_t* __restrict__ group_lo,
     const int32_t* __restrict__ group_hi, int64_t n, int chunks, int k, int metric,
     float* __restrict__ top_val, int32_t* __restrict__ top_idx) {
-  constexpr int D = GFY_PAIRWISE_TOPK_DISTINCT_MAX;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  float lk[D];   // -key, descending
-  int li[D];
-#pragma unroll
-  for (int q = 0; q < D; ++q) {
-    lk[q] = -__builtin_inff();
-    li[q] = kNoIndex;
-  }
-  for (int c = 0; c < chunks; ++c) {
-    const float* keys = part_key + ((int64_t)c * n + i) * k;
-    const int32_t* idx = part_idx + ((int64_t)c * n + i) * k;
-    for (int q = 0; q < k; ++q) {
-      const float g = -keys[q];
-      if (!(g > lk[D - 1])) break;   // sorted: nothing behind it gets in either (empty: g = -inf)
-      const int j = idx[q];
-      const int from = group_lo[j];
-      list_insert_distinct<D>(lk, li, g, j, from, group_hi[j] - from);
-    }
-  }
-  const float at = a_term[i];
-#pragma unroll
-  for (int q = 0; q < D; ++q) {
-    if (q < k) {
-      const float v = -lk[q];
-      float out;
-      if (metric == GFY_L2) {
-        const float d2 = at + v;
-        out = __builtin_sqrtf(d2 > 0.f ? d2 : 0.f);
-      } else {
-        out = -v * at;
-      }
-      top_val[i * k + q] = out;
-      top_idx[i * k + q] = li[q] == kNoIndex ? -1 : li[q];
-    }
-  }
+  topk_finish<true>(part_key, part_idx, a_term, group_lo, group_hi, n, chunks, k, metric, top_val,
+                    top_idx);
 }
 
 }  // namespace
 
 int launch_topk_sweep_distinct(const TopkArgs& p, bool fold, hipStream_t s) {
-  if (p.k <= 4)
-    return fold ? launch_sweep<4, true, true, true>(p, s) : launch_sweep<4, false, true, true>(p, s);
-  if (p.k <= 8)
-    return fold ? launch_sweep<8, true, true, true>(p, s) : launch_sweep<8, false, true, true>(p, s);
-  return fold ? launch_sweep<16, true, true, true>(p, s) : launch_sweep<16, false, true, true>(p, s);
+  return launch_topk_sweep<true, true>(p, fold, s);
 }
 
 int launch_topk_finish_distinct(const TopkArgs& p, const float* a_term, int metric, float* top_val,

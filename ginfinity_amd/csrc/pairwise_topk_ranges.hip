@@ -8,9 +8,7 @@
 namespace gfy {
 
 int launch_topk_sweep_ranges(const TopkArgs& p, bool fold, hipStream_t s) {
-  if (p.k <= 4) return fold ? launch_sweep<4, true, true>(p, s) : launch_sweep<4, false, true>(p, s);
-  if (p.k <= 8) return fold ? launch_sweep<8, true, true>(p, s) : launch_sweep<8, false, true>(p, s);
-  return fold ? launch_sweep<16, true, true>(p, s) : launch_sweep<16, false, true>(p, s);
+  return launch_topk_sweep<true>(p, fold, s);
 }
 
 }  // namespace gfy

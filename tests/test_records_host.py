@@ -181,6 +181,52 @@ def test_an_oversize_record_is_refused_with_its_bytes():
         distance.plan_record_blocks([1, -1], 1, 100)
 
 
+# ---- workspaces ---------------------------------------------------------------------------------
+
+def _split_b(n, m, block_a):
+    """(blocks_a, chunks, chunk_rows) of a sweep of n a-rows in blocks of ``block_a`` against m
+    b-rows in 128-row tiles: at least 1,024 workgroups, of the next five chunk counts a later one
+    only where its grid ends in 1 % fewer sweeps over 256 CUs, at most one chunk per tile, and the
+    chunks evened out to whole tiles."""
+    blocks_a, tiles_b = -(-n // block_a), -(-m // 128)
+    least = -(-1024 // blocks_a)
+    best, chunks = 1e300, least
+    for c in range(least, least + 6):
+        sweeps = -(-blocks_a * c // 256) / c
+        if sweeps < best * 0.99:
+            best, chunks = sweeps, c
+    chunks = max(1, min(chunks, tiles_b))
+    tiles_per_chunk = -(-tiles_b // chunks)
+    return blocks_a, -(-tiles_b // tiles_per_chunk), tiles_per_chunk * 128
+
+
+def _workspace(n, m, *arrays):
+    """s and t of b padded to whole tiles, the a-side term, then ``arrays`` (bytes each): every
+    array rounded up to 256 bytes."""
+    padded = -(-m // 128) * 128 * 4
+    return sum(-(-size // 256) * 256 for size in (padded, padded, n * 4, *arrays))
+
+
+def test_workspace_sizes_follow_the_layout_rule():
+    """The three workspace functions and gfy_pairwise_record_chunks against the rule stated
+    above: 256 a-rows per workgroup for nearest, 128 for top-k and the records."""
+    lib = native.library()
+    for n, m in ((1, 1), (130, 257), (300, 700), (65_536, 4_607), (1_000_000, 1_000_000)):
+        chunks = _split_b(n, m, 256)[1]
+        assert lib.gfy_pairwise_workspace_bytes(n, m) == \
+            _workspace(n, m, chunks * n * 4, chunks * n * 4), (n, m)
+        chunks = _split_b(n, m, 128)[1]
+        assert lib.gfy_pairwise_record_chunks(n, m) == chunks, (n, m)
+        for k in (1, 4, 8, 16):
+            assert lib.gfy_pairwise_topk_workspace_bytes(n, m, k) == \
+                _workspace(n, m, chunks * n * k * 4, chunks * n * k * 4), (n, m, k)
+        for records_b in (1, 7):
+            assert lib.gfy_pairwise_record_workspace_bytes(n, m, 3, records_b) == \
+                _workspace(n, m, records_b * n * 4), (n, m, records_b)
+    assert _split_b(300, 700, 128) == (3, 6, 128) and _split_b(300, 700, 256) == (2, 6, 128)
+    assert _split_b(1_000_000, 1_000_000, 256)[:2] == (3907, 3)
+
+
 # ---- registers ----------------------------------------------------------------------------------
 
 def test_every_record_kernel_fits_the_register_file(tmp_path):

@@ -46,7 +46,7 @@ sys.path.insert(0, str(ROOT))
 from ginfinity_amd import distance, synthetic  # noqa: E402
 
 DENSE_ROWS = 4_096
-KERNEL_SOURCES = ("pairwise.hip", "pairwise_topk.hip", "pairwise_topk.inc",
+KERNEL_SOURCES = ("pairwise.hip", "pairwise_sweep.inc", "pairwise_topk.hip", "pairwise_topk.inc",
                   "pairwise_topk_ranges.hip", "pairwise_topk_distinct.hip", "gfy_common.h",
                   "gfy_api.hip")
 
