@@ -21,6 +21,7 @@ from .graph import Graph, GraphBuilder, GraphShard, partition_records
 from .shard_io import graph_metadata_path, load_graph_shard, save_graph_shard
 from .table import read_rna_table
 from .api import Ginfinity, ModelIntegrityError, default_alignment_parameters
+from . import align
 
 __version__ = "1.2.1+mi355x.1"
 
@@ -29,7 +30,7 @@ __all__ = [
     "NODE_ROLE_CONTEXT", "NODE_ROLE_CORE", "Graph", "GraphBuilder",
     "GraphCompatibilityError", "GraphShard", "GraphSpec",
     "GraphValidationError", "InputValidationError", "ModelIntegrityError",
-    "RNA", "default_alignment_parameters", "graph_metadata_path",
+    "RNA", "align", "default_alignment_parameters", "graph_metadata_path",
     "load_graph_shard", "partition_records", "read_rna_table",
     "save_graph_shard", "__version__",
 ]

@@ -6,7 +6,7 @@ caller gets an exception.  The product never routes around the kernels.
 from __future__ import annotations
 
 import ctypes
-from ctypes import (POINTER, Structure, c_char_p, c_int, c_int32, c_int64, c_size_t,
+from ctypes import (POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t,
                     c_uint32, c_void_p)
 import os
 from pathlib import Path
@@ -27,6 +27,7 @@ GFY_L2, GFY_COSINE = 0, 1
 GFY_PAIRWISE_TOPK_MAX = 16
 GFY_PAIRWISE_TOPK_DISTINCT_MAX = 16
 GFY_PAIRWISE_RECORDS_MAX = 2097120
+GFY_ALIGN_ROWS_MAX = 4096
 GFY_OPT_SEPARATE_HEAD = 2
 GFY_OPT_LAYER_KERNEL = 3
 GFY_OPT_STAGGER = 4
@@ -130,6 +131,10 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_pairwise_record_scores": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
                                            c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                            c_size_t, c_void_p]),
+    "gfy_align_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gfy_align_local": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -1,0 +1,187 @@
+"""Batched local alignment of record pairs on the device: the step behind ``record_scores``.
+
+``distance.record_scores`` ranks pairs of records; ``local_align`` aligns the pairs a caller
+picks from that ranking, without the embeddings leaving the device:
+
+    scores = distance.record_scores(rows, counts_a=counts, metric="cosine")
+    pairs = align.top_pairs(scores, 8, largest=True)
+    score, end = align.local_align(rows, counts_a=counts, pairs=pairs, gap_open=1.0, gap_extend=0.25)
+
+**This is not ``ginfinity-sw``.**  The reference delegates alignment to that external package,
+which is not in its tree; it holds the names of eight scoring parameters and no formula.  The
+semantics below are defined here and in include/gfy.h, as the whole distance path's are.
+Nothing here reproduces that package's scores, none of ``default_alignment_parameters()``'s
+entries maps onto an argument of ``local_align`` (that function stays a pass-through and is not
+wired in), and ``gap_open`` / ``gap_extend`` are ordinary arguments without a default.
+
+Definition.  A pair ``(q, r)`` aligns ``A`` = the ``Lq`` rows of record q of ``a`` with ``B`` =
+the ``Lr`` rows of record r of ``b``: Smith-Waterman with affine gaps (Gotoh), all in float32,
+every addition and subtraction one rounded operation, ``max`` exact:
+
+    C[i][j] = distance.pairwise(A, B, metric="cosine")[i, j]           (bit for bit)
+    s[i][j] = fl32(fl32(C[i][j] * match_scale) + match_shift)
+    E[i][j] = max(E[i][j-1] - gap_extend, H[i][j-1] - gap_open)
+    F[i][j] = max(F[i-1][j] - gap_extend, H[i-1][j] - gap_open)
+    H[i][j] = max(0, H[i-1][j-1] + s[i][j], E[i][j], F[i][j])
+
+with ``H = 0`` and ``E = F = -inf`` outside the matrix; ``gap_open`` is the cost of a gap's
+first position.  ``score = max H``; ``end = (i, j)`` is the first cell in the order (i
+ascending, then j ascending) with ``H == score``, 0-based inside the two records; a score of 0
+(no positive cell, a record of zero rows) gives ``end = (-1, -1)``, and only a zero keeps no
+promise of its sign.  Every cell is a fixed expression of its three predecessors, so a pair's
+result depends neither on the other pairs of the call nor on the run, bit for bit.
+
+Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIMUM_LENGTH_NT``),
+``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: traceback and start
+positions, banded or global alignment, a ``device="cpu"`` path, and any z-score or
+normalisation of the scores.  The cost is not measured.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+import torch
+
+from . import _native as native
+from .distance import _checked, _prepare, _record_ptr
+
+
+class AlignWorkspace:
+    """Scratch memory of ``local_align`` kept across calls, as ``distance.RecordWorkspace`` keeps
+    that of ``record_scores`` (the results are always new tensors)."""
+
+    def __init__(self) -> None:
+        self.scratch: torch.Tensor | None = None
+
+    def buffer(self, device, scratch_bytes: int) -> torch.Tensor:
+        if self.scratch is None or self.scratch.numel() < scratch_bytes or \
+                self.scratch.device != device:
+            self.scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=device)
+        return self.scratch
+
+
+def _checked_pairs(pairs, records_a: int, records_b: int) -> np.ndarray:
+    """``pairs`` as an int32 ``[P, 2]`` host array with every index inside its side's records."""
+    if isinstance(pairs, torch.Tensor):
+        pairs = pairs.detach().cpu().numpy()
+    pairs = np.asarray(pairs)
+    if pairs.size == 0 and pairs.ndim in (1, 2):
+        pairs = np.zeros((0, 2), dtype=np.int64)
+    if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
+        raise ValueError("pairs must be an integer array of shape (P, 2)")
+    pairs = pairs.astype(np.int64)
+    if pairs.shape[0] >= 2 ** 31:
+        raise ValueError("pairs must hold fewer than 2^31 pairs")
+    if pairs.shape[0] and (pairs.min() < 0 or pairs[:, 0].max() >= records_a
+                           or pairs[:, 1].max() >= records_b):
+        bad = int(np.flatnonzero((pairs[:, 0] < 0) | (pairs[:, 0] >= records_a)
+                                 | (pairs[:, 1] < 0) | (pairs[:, 1] >= records_b))[0])
+        raise ValueError(f"pair {bad} = ({int(pairs[bad, 0])}, {int(pairs[bad, 1])}) is out of "
+                         f"range: a has {records_a} records, b has {records_b}")
+    return np.ascontiguousarray(pairs.astype(np.int32))
+
+
+def _checked_parameter(value, name: str) -> float:
+    if value is None:
+        raise ValueError(f"{name} is required: it has no default")
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) \
+            or not math.isfinite(float(value)):
+        raise ValueError(f"{name} must be a finite number")
+    value = float(value)
+    if abs(value) > float(np.finfo(np.float32).max):
+        raise ValueError(f"{name} must be finite in float32")
+    return value
+
+
+def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None
+                ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Local alignment of the record pairs ``pairs``: ``(scores float32 [P], ends int32 [P, 2])``
+    on the device, exact, the ``Lq x Lr`` matrix of a pair never written (the definition is at
+    the head of this module; it is this project's own and not ``ginfinity-sw``'s).
+
+    ``a`` / ``b`` are fp16 ``[rows, 128]`` embeddings as ``distance.pairwise`` takes them,
+    ``counts_a`` / ``counts_b`` the row counts of their contiguous records.  With ``b`` omitted
+    ``a`` is aligned against itself and ``counts_b`` defaults to ``counts_a``; nothing is
+    excluded, ``(q, q)`` aligns a record with itself.  ``pairs`` is an integer ``[P, 2]`` array
+    (numpy or torch, on any device) of (record of ``a``, record of ``b``); ``top_pairs`` makes
+    one from ``distance.record_scores``.  The substitution score of two rows is
+    ``cosine * match_scale + match_shift`` (two rounded float32 operations); ``gap_open`` (the
+    cost of a gap's first position) and ``gap_extend`` are required, ``0 <= gap_extend <=
+    gap_open``.
+
+    Every argument error is a ``ValueError`` before a device is touched: a pair out of range, a
+    record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
+    finite or out of order.  ``P == 0`` returns empty tensors without a launch."""
+    gap_open = _checked_parameter(gap_open, "gap_open")
+    gap_extend = _checked_parameter(gap_extend, "gap_extend")
+    match_scale = _checked_parameter(match_scale, "match_scale")
+    match_shift = _checked_parameter(match_shift, "match_shift")
+    if not 0.0 <= gap_extend <= gap_open:
+        raise ValueError("0 <= gap_extend <= gap_open is required")
+    a = _checked(a)
+    if b is None:
+        counts_b = counts_a if counts_b is None else counts_b
+    else:
+        b = _checked(b)
+        if counts_b is None:
+            raise ValueError("counts_b is required with b: record counts of b's rows")
+    n, m = a.shape[0], a.shape[0] if b is None else b.shape[0]
+    ptr_a = _record_ptr(counts_a, n, "counts_a", "a")
+    ptr_b = _record_ptr(counts_b, m, "counts_b", "b")
+    pairs = _checked_pairs(pairs, ptr_a.size - 1, ptr_b.size - 1)
+    rows_a = np.diff(ptr_a)[pairs[:, 0]]
+    rows_b = np.diff(ptr_b)[pairs[:, 1]]
+    for side, rows, column in (("a", rows_a, 0), ("b", rows_b, 1)):
+        if rows.size and rows.max() > native.GFY_ALIGN_ROWS_MAX:
+            bad = int(np.argmax(rows > native.GFY_ALIGN_ROWS_MAX))
+            raise ValueError(f"pair {bad}: record {int(pairs[bad, column])} of {side} has "
+                             f"{int(rows[bad])} rows, more than {native.GFY_ALIGN_ROWS_MAX}")
+    count = pairs.shape[0]
+    a = _prepare(a, None)
+    b = a if b is None else _prepare(b, a.device)
+    with torch.cuda.device(a.device):
+        scores = torch.zeros(count, dtype=torch.float32, device=a.device)
+        ends = torch.full((count, 2), -1, dtype=torch.int32, device=a.device)
+        if count == 0 or n == 0 or m == 0:   # no pair, or no pair with a row on both sides
+            return scores, ends
+        lib = native.library()
+        need = lib.gfy_align_workspace_bytes(count, int(rows_b.max()))
+        scratch = (workspace or AlignWorkspace()).buffer(a.device, need)
+        ptr_a_dev = torch.from_numpy(ptr_a.astype(np.int32)).to(a.device)
+        ptr_b_dev = torch.from_numpy(ptr_b.astype(np.int32)).to(a.device)
+        pairs_dev = torch.from_numpy(pairs).to(a.device)
+        native.check(lib.gfy_align_local(
+            a.data_ptr(), n, ptr_a_dev.data_ptr(), ptr_a.size - 1, b.data_ptr(), m,
+            ptr_b_dev.data_ptr(), ptr_b.size - 1, pairs_dev.data_ptr(), count, match_scale,
+            match_shift, gap_open, gap_extend, scores.data_ptr(), ends.data_ptr(),
+            scratch.data_ptr(), scratch.numel(),
+            torch.cuda.current_stream(a.device).cuda_stream), "gfy_align_local")
+    return scores, ends
+
+
+def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
+    """The candidate pairs of a ``distance.record_scores`` matrix ``[Q, R]``: for every row q its
+    ``k`` best columns r, as an int32 ``[Q * min(k, R), 2]`` host array of ``[q, r]``, rows in
+    order and inside a row the best column first.  ``largest`` says which end is good (True for
+    cosine scores, False for L2).  Ties go to the lowest r; NaN (a record of zero rows) ranks
+    behind every number.  A pure function of its arguments: no device is needed."""
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("k must be a positive integer")
+    if not isinstance(largest, (bool, np.bool_)):
+        raise ValueError("largest must be True (large scores are good) or False")
+    if isinstance(scores, torch.Tensor):
+        scores = scores.detach().cpu().numpy()
+    scores = np.asarray(scores)
+    if scores.ndim != 2 or scores.dtype.kind != "f":
+        raise ValueError("scores must be a floating-point matrix [Q, R]")
+    missing = np.isnan(scores)
+    keys = np.where(missing, 0, -scores if largest else scores)
+    # by (NaN or not, key, column): lexsort is stable and takes its last key first
+    order = np.lexsort((keys, missing), axis=1)[:, :min(int(k), scores.shape[1])]
+    rows = np.repeat(np.arange(scores.shape[0]), order.shape[1])
+    return np.stack([rows, order.reshape(-1)], axis=1).astype(np.int32)
+
+
+__all__ = ["local_align", "AlignWorkspace", "top_pairs"]

@@ -1149,4 +1149,44 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
                                  out_scores, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t gfy_align_workspace_bytes(int64_t pairs, int64_t max_rows_b) {
+  return align_workspace_bytes(pairs < 1 ? 1 : pairs,
+                               max_rows_b < 0 ? 0 : max_rows_b > GFY_ALIGN_ROWS_MAX
+                                   ? GFY_ALIGN_ROWS_MAX : max_rows_b);
+}
+
+int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                    const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                    const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                    float gap_open, float gap_extend, float* out_score, int32_t* out_end,
+                    void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  const char* who = "gfy_align_local";
+  GFY_REQUIRE(a, GFY_ERR_INVALID, "%s: a is NULL", who);
+  GFY_REQUIRE(b, GFY_ERR_INVALID, "%s: b is NULL", who);
+  GFY_REQUIRE(ptr_a, GFY_ERR_INVALID, "%s: ptr_a is NULL", who);
+  GFY_REQUIRE(ptr_b, GFY_ERR_INVALID, "%s: ptr_b is NULL", who);
+  GFY_REQUIRE(pairs, GFY_ERR_INVALID, "%s: pairs is NULL", who);
+  GFY_REQUIRE(out_score, GFY_ERR_INVALID, "%s: out_score is NULL", who);
+  GFY_REQUIRE(out_end, GFY_ERR_INVALID, "%s: out_end is NULL", who);
+  GFY_REQUIRE(ws, GFY_ERR_INVALID, "%s: workspace is NULL", who);
+  GFY_REQUIRE(n > 0 && m > 0 && n < INT32_MAX && m < INT32_MAX, GFY_ERR_INVALID,
+              "%s: bad arguments: n = %lld, m = %lld", who, (long long)n, (long long)m);
+  GFY_REQUIRE(records_a > 0 && records_a < INT32_MAX && records_b > 0 && records_b < INT32_MAX,
+              GFY_ERR_INVALID, "%s: records_a = %lld, records_b = %lld outside 1..2^31 - 2", who,
+              (long long)records_a, (long long)records_b);
+  GFY_REQUIRE(P >= 1 && P <= INT32_MAX, GFY_ERR_INVALID, "%s: P = %lld outside 1..2^31 - 1", who,
+              (long long)P);
+  GFY_REQUIRE(std::isfinite(match_scale) && std::isfinite(match_shift) &&
+                  std::isfinite(gap_open) && std::isfinite(gap_extend),
+              GFY_ERR_INVALID, "%s: match_scale, match_shift, gap_open and gap_extend must be finite",
+              who);
+  GFY_REQUIRE(0.0f <= gap_extend && gap_extend <= gap_open, GFY_ERR_INVALID,
+              "%s: 0 <= gap_extend <= gap_open required, got gap_open = %g, gap_extend = %g", who,
+              (double)gap_open, (double)gap_extend);
+  return launch_align_local(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale,
+                            match_shift, gap_open, gap_extend, out_score, out_end, ws, ws_bytes,
+                            (hipStream_t)stream);
+}
+
 }  // extern "C"

@@ -53,17 +53,11 @@ __global__ __launch_bounds__(256) void k_row_terms(const f16* __restrict__ rows,
   const int64_t item = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t row = item >> 4;
   const int chunk = (int)(item & 15);
-  float ss = 0.f;
-  if (row < count) {
-    const f16x8 v = *reinterpret_cast<const f16x8*>(rows + row * 128 + chunk * 8);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) ss = __builtin_fmaf((float)v[j], (float)v[j], ss);
-  }
-#pragma unroll
-  for (int m = 1; m < 16; m <<= 1) ss += __shfl_xor(ss, m, 64);
+  f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (row < count) v = *reinterpret_cast<const f16x8*>(rows + row * 128 + chunk * 8);
+  const float ss = row_square_sum(v);
   if (row < count && chunk == 0) {
-    const float nrm = __builtin_sqrtf(ss);
-    const float inv = 1.0f / (nrm > 1e-12f ? nrm : 1e-12f);
+    const float inv = inverse_norm(ss);
     if (s_out) {
       s_out[row] = metric == GFY_L2 ? -2.0f : -inv;
       t_out[row] = metric == GFY_L2 ? (fold ? -0.5f * ss : ss) : 0.0f;

@@ -44,6 +44,24 @@ __device__ __forceinline__ float max16(const f32x16& g) {
   return high;
 }
 
+// |row|^2 the way every key's terms take it (k_row_terms, pairwise.hip; the local aligner's
+// rows, align_local.hip): 16 consecutive lanes hold the 16 pieces of a row, each adds its eight
+// squares in order and a butterfly adds the 16 partial sums, so that all 16 lanes hold the sum.
+__device__ __forceinline__ float row_square_sum(const f16x8& v) {
+  float ss = 0.f;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) ss = __builtin_fmaf((float)v[j], (float)v[j], ss);
+#pragma unroll
+  for (int m = 1; m < 16; m <<= 1) ss += __shfl_xor(ss, m, 64);
+  return ss;
+}
+
+// 1 / max(|row|, 1e-12) of cosine: -s_j of a b-row, the a_term of an a-row
+__device__ __forceinline__ float inverse_norm(float ss) {
+  const float nrm = __builtin_sqrtf(ss);
+  return 1.0f / (nrm > 1e-12f ? nrm : 1e-12f);
+}
+
 // What leaves every search for the pair with key `key` (key_ij = fma(dot_ij, s_j, t_j), head of
 // pairwise.hip): L2 sqrt(max(|a_i|^2 + key, 0)) with a_term = |a_i|^2, cosine -key / |a_i| with
 // a_term = 1 / |a_i|.

@@ -582,6 +582,57 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
                                const int32_t* ptr_b, int64_t records_b, float* out_scores,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Batched local alignment of record pairs: Smith-Waterman with affine gaps (Gotoh) over the
+ * cosine of the records' rows, the step behind the ranking of gfy_pairwise_record_scores.  The
+ * L_q x L_r matrix of a pair is never written to memory.
+ *   No reference symbol: the reference delegates alignment to an external package that is not in
+ *   its tree and holds parameter names without a formula.  The semantics are defined here; this
+ *   is NOT that package, reproduces none of its scores, and none of the reference's alignment
+ *   parameters maps onto an argument of this call.
+ *   Rows of a ([n][128] fp16) are grouped in records_a contiguous records by ptr_a, rows of b in
+ *   records_b by ptr_b (int32 running sums, device memory, as gfy_pairwise_record_scores takes
+ *   them).  pairs int32 [P][2], device memory: pair p = (q, r) aligns A = the L_q rows of record
+ *   q of a with B = the L_r rows of record r of b.
+ *   Cosine      C[i][j] is gfy_pairwise_dense(A, B, GFY_COSINE)[i][j] bit for bit (the same
+ *               multiply, key and value).
+ *   Substitution  s[i][j] = fl32(fl32(C[i][j] * match_scale) + match_shift): two rounded fp32
+ *               operations, never contracted.
+ *   Recurrences, all fp32, every + and - one rounded operation, max exact:
+ *               E[i][j] = max(E[i][j-1] - gap_extend, H[i][j-1] - gap_open)
+ *               F[i][j] = max(F[i-1][j] - gap_extend, H[i-1][j] - gap_open)
+ *               H[i][j] = max(0, H[i-1][j-1] + s[i][j], E[i][j], F[i][j])
+ *               H = 0 and E = F = -inf outside the matrix; gap_open is the cost of a gap's first
+ *               position.  A cell is a fixed expression of its three predecessors: the result
+ *               depends neither on the schedule, nor on the other pairs of the call, nor on the
+ *               run.
+ *   Result      out_score[p] = max H; out_end[p] = (i, j), 0-based inside the two records, the
+ *               first cell in the order (i ascending, then j ascending) with H == score.  A score
+ *               of 0 (no positive cell, a record of zero rows) gives end = (-1, -1); only a zero
+ *               keeps no promise of its sign.
+ *   Limits      a record has at most GFY_ALIGN_ROWS_MAX rows; 0 <= gap_extend <= gap_open, the
+ *               four parameters finite; 1 <= P < 2^31.  Rows holding inf / NaN give unspecified
+ *               values.  No traceback or start positions, no banded or global alignment, no
+ *               normalisation of scores.
+ *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), max_rows_b the longest b-record any
+ *               pair names: the last row of a 64-row strip of A, per wave in flight.
+ *   ptr_a, ptr_b and pairs are device arrays, which the kernel only compares and clips.  A pair
+ *   whose record index is out of range, or whose record is longer than GFY_ALIGN_ROWS_MAX, or
+ *   whose b-record is longer than the max_rows_b the workspace holds, gets score = NaN and end =
+ *   (-2, -2), and causes no access outside the caller's buffers.
+ *   A NULL pointer (named in gfy_last_error), n or m outside 1..2^31 - 2, a record count outside
+ *   1..2^31 - 2, P outside 1..2^31 - 1, a non-finite parameter and gap_extend outside
+ *   [0, gap_open] are GFY_ERR_INVALID, a workspace shorter than gfy_align_workspace_bytes(P, 0)
+ *   is GFY_ERR_WORKSPACE; all of it before any launch and without a device.
+ *   Cost: not measured.                                                                       */
+#define GFY_ALIGN_ROWS_MAX 4096
+size_t gfy_align_workspace_bytes(int64_t pairs, int64_t max_rows_b);
+int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                    const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                    const int32_t* pairs /* [P][2] device */, int64_t P,
+                    float match_scale, float match_shift, float gap_open, float gap_extend,
+                    float* out_score /* [P] */, int32_t* out_end /* [P][2] */,
+                    void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

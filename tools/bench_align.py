@@ -1,0 +1,150 @@
+"""Local-alignment measurement: ``align.local_align`` over ``--pairs`` pairs of records of 200 to
+600 rows of 128-d fp16 unit rows on one device, reported as pairs/s and cell updates/s (a cell
+update is one (i, j) of a pair's ``Lq x Lr`` dynamic program, the cosine included).
+
+``--warmup`` untimed runs, ``--repeats`` timed runs (HIP events around one call), min, median
+and max reported; the rates use the median.  No target is set: nobody had measured any part of
+this before the first run.  For scale only, a host numpy float32 dynamic program of the same
+recurrences (anti-diagonal by anti-diagonal, from cosines the device computed) is timed on
+``--host-pairs`` of the pairs.  Nothing else may run on the device.  The document names the run:
+host, UTC time, device, ROCm / torch versions, the commit (``--commit``, or ``git rev-parse
+HEAD`` where the tree is a checkout) and a SHA-256 of align_local.hip.  Writes one JSON document
+(default profiles/align_bench.json) and prints it.
+
+    python tools/bench_align.py --pairs 20000
+"""
+from __future__ import annotations
+
+import argparse
+import datetime
+import hashlib
+import json
+import platform
+import statistics
+import subprocess
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+from ginfinity_amd import align, distance, synthetic  # noqa: E402
+
+KERNEL_SOURCE = "align_local.hip"
+
+
+def _commit() -> str | None:
+    try:
+        done = subprocess.run(["git", "-C", str(ROOT), "rev-parse", "HEAD"], capture_output=True,
+                              text=True, timeout=10)
+    except (OSError, subprocess.SubprocessError):
+        return None
+    return done.stdout.strip() if done.returncode == 0 and done.stdout.strip() else None
+
+
+def _timed(call, repeats: int, warmup: int) -> list[float]:
+    for _ in range(warmup):
+        call()
+    torch.cuda.synchronize()
+    seconds = []
+    for _ in range(repeats):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        call()
+        e1.record()
+        torch.cuda.synchronize()
+        seconds.append(e0.elapsed_time(e1) * 1e-3)
+    return seconds
+
+
+def _span(seconds: list[float]) -> dict:
+    return {"min": min(seconds), "median": statistics.median(seconds), "max": max(seconds),
+            "runs": seconds}
+
+
+def _host_gotoh(S: np.ndarray, go: np.float32, ge: np.float32) -> np.float32:
+    """max H of the recurrences in numpy float32, one anti-diagonal at a time."""
+    lq, lr = S.shape
+    H = np.zeros((lq + 1, lr + 1), dtype=np.float32)
+    E = np.full((lq + 1, lr + 1), -np.inf, dtype=np.float32)
+    F = np.full((lq + 1, lr + 1), -np.inf, dtype=np.float32)
+    for d in range(lq + lr - 1):
+        i = np.arange(max(0, d - lr + 1), min(lq - 1, d) + 1) + 1
+        j = d + 2 - i
+        e = np.maximum(E[i, j - 1] - ge, H[i, j - 1] - go)
+        f = np.maximum(F[i - 1, j] - ge, H[i - 1, j] - go)
+        E[i, j], F[i, j] = e, f
+        H[i, j] = np.maximum(np.maximum(np.float32(0), H[i - 1, j - 1] + S[i - 1, j - 1]),
+                             np.maximum(e, f))
+    return H.max()
+
+
+def main() -> None:
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--pairs", type=int, default=20_000)
+    parser.add_argument("--records", type=int, default=2_000, help="records in the library")
+    parser.add_argument("--repeats", type=int, default=7)
+    parser.add_argument("--warmup", type=int, default=2)
+    parser.add_argument("--host-pairs", type=int, default=4,
+                        help="pairs of the host numpy DP timed for scale (0: none)")
+    parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
+    parser.add_argument("--out", default=str(ROOT / "profiles" / "align_bench.json"))
+    args = parser.parse_args()
+    if args.pairs < 1 or args.records < 1:
+        parser.error("--pairs, --records: positive")
+    rng = np.random.default_rng(0)
+    counts = rng.integers(200, 601, size=args.records)
+    ptr = np.concatenate(([0], np.cumsum(counts)))
+    rows = torch.from_numpy(synthetic.unit_rows(0, int(ptr[-1]))).cuda()
+    pairs = rng.integers(0, args.records, size=(args.pairs, 2)).astype(np.int32)
+    cells = int((counts[pairs[:, 0]].astype(np.int64) * counts[pairs[:, 1]]).sum())
+    parameters = dict(gap_open=1.0, gap_extend=0.25, match_scale=1.0, match_shift=-0.3)
+    keeper = align.AlignWorkspace()
+    pairs_dev = torch.from_numpy(pairs)
+    seconds = _timed(lambda: align.local_align(rows, counts_a=counts, pairs=pairs_dev,
+                                               workspace=keeper, **parameters),
+                     args.repeats, args.warmup)
+    mid = statistics.median(seconds)
+    source = ROOT / "ginfinity_amd" / "csrc" / KERNEL_SOURCE
+    result = {"metric": "local_align over pairs of 200- to 600-row records of 128-d fp16 embeddings",
+              "pairs": args.pairs, "records": args.records, "rows": int(ptr[-1]), "cells": cells,
+              "parameters": parameters, "host": platform.node(),
+              "utc": datetime.datetime.now(datetime.timezone.utc).isoformat(timespec="seconds"),
+              "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
+              "torch": torch.__version__, "commit": args.commit or _commit(),
+              "kernel_source": KERNEL_SOURCE,
+              "kernel_source_sha256": hashlib.sha256(source.read_bytes()).hexdigest(),
+              "command": "python tools/bench_align.py " + " ".join(sys.argv[1:]),
+              "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
+              "timed": "the whole call: host checks of the pair list, its upload, one launch",
+              "seconds": _span(seconds), "pairs_per_s": args.pairs / mid,
+              "cell_updates_per_s": cells / mid}
+    print(f"local_align: {mid:.4f} s for {args.pairs} pairs = {args.pairs / mid:.3e} pairs/s, "
+          f"{cells / mid:.3e} cell updates/s", file=sys.stderr, flush=True)
+    if args.host_pairs > 0:
+        some = pairs[:args.host_pairs]
+        host_seconds, host_cells = 0.0, 0
+        for q, r in some:
+            C = distance.pairwise(rows[ptr[q]:ptr[q + 1]], rows[ptr[r]:ptr[r + 1]],
+                                  metric="cosine").cpu().numpy()
+            S = (C * np.float32(parameters["match_scale"])) + np.float32(parameters["match_shift"])
+            start = time.perf_counter()
+            _host_gotoh(S, np.float32(parameters["gap_open"]), np.float32(parameters["gap_extend"]))
+            host_seconds += time.perf_counter() - start
+            host_cells += S.size
+        result["host_numpy_dp"] = {"pairs": int(len(some)), "cells": host_cells,
+                                   "seconds": host_seconds,
+                                   "cell_updates_per_s": host_cells / host_seconds,
+                                   "what": "numpy float32 anti-diagonal DP on one host thread, the "
+                                           "cosines given: for scale, not a competitor"}
+    text = json.dumps(result, indent=1)
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(text + "\n")
+    print(json.dumps(result))
+
+
+if __name__ == "__main__":
+    main()
