@@ -135,6 +135,11 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_align_local": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                                 c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_float,
                                 c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gfy_align_span_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gfy_align_local_span": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                     c_void_p, c_int64, c_void_p, c_int64, c_float, c_float,
+                                     c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
 }
 
 

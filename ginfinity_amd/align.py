@@ -31,10 +31,31 @@ ascending, then j ascending) with ``H == score``, 0-based inside the two records
 promise of its sign.  Every cell is a fixed expression of its three predecessors, so a pair's
 result depends neither on the other pairs of the call nor on the run, bit for bit.
 
+Start cells.  ``local_spans`` returns, next to score and end, the cell where each alignment
+starts.  Every E, F and H that is positive has an origin ``(i0, j0)``, the first matched cell of
+the path that produced it, carried through the same recurrences (the matrix is still never
+written):
+
+    H[i][j]   the origin of the first candidate, in the order diagonal, then E, then F, whose
+              value equals H[i][j]; the diagonal candidate ``H[i-1][j-1] + s[i][j]`` carries the
+              origin of ``H[i-1][j-1]`` if that value is > 0 and ``(i, j)`` itself otherwise (a
+              predecessor that is 0 of either sign or outside the matrix: the alignment starts
+              here)
+    E[i][j]   the origin of ``H[i][j-1]`` if ``H[i][j-1] - gap_open >= E[i][j-1] - gap_extend``
+              (opening wins a tie), else that of ``E[i][j-1]``
+    F[i][j]   the same rule with the row above
+
+A value <= 0 has no origin, and none is needed: a positive E or F descends from a positive H.
+``start`` is the origin of H at ``end``; a score of 0 gives ``(-1, -1)``.  An origin is a fixed
+function of the three predecessors, so a start is as independent of company and run as a score.
+It follows that ``start <= end`` in both coordinates, that ``s[start] == H[start] > 0``, and that
+the same recurrences run on the box ``start..end`` alone reach exactly ``score`` at the box's last
+cell, bit for bit: a later traceback only has to revisit that box.
+
 Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIMUM_LENGTH_NT``),
-``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: traceback and start
-positions, banded or global alignment, a ``device="cpu"`` path, and any z-score or
-normalisation of the scores.  The cost is not measured.
+``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: the aligned path
+itself (traceback), banded or global alignment, a ``device="cpu"`` path, and any z-score or
+normalisation of the scores.  Measured cost: DESIGN.md §4.
 """
 from __future__ import annotations
 
@@ -48,8 +69,9 @@ from .distance import _checked, _prepare, _record_ptr
 
 
 class AlignWorkspace:
-    """Scratch memory of ``local_align`` kept across calls, as ``distance.RecordWorkspace`` keeps
-    that of ``record_scores`` (the results are always new tensors)."""
+    """Scratch memory of ``local_align`` and ``local_spans`` kept across calls, as
+    ``distance.RecordWorkspace`` keeps that of ``record_scores`` (the results are always new
+    tensors)."""
 
     def __init__(self) -> None:
         self.scratch: torch.Tensor | None = None
@@ -94,26 +116,11 @@ def _checked_parameter(value, name: str) -> float:
     return value
 
 
-def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None
-                ) -> tuple[torch.Tensor, torch.Tensor]:
-    """Local alignment of the record pairs ``pairs``: ``(scores float32 [P], ends int32 [P, 2])``
-    on the device, exact, the ``Lq x Lr`` matrix of a pair never written (the definition is at
-    the head of this module; it is this project's own and not ``ginfinity-sw``'s).
-
-    ``a`` / ``b`` are fp16 ``[rows, 128]`` embeddings as ``distance.pairwise`` takes them,
-    ``counts_a`` / ``counts_b`` the row counts of their contiguous records.  With ``b`` omitted
-    ``a`` is aligned against itself and ``counts_b`` defaults to ``counts_a``; nothing is
-    excluded, ``(q, q)`` aligns a record with itself.  ``pairs`` is an integer ``[P, 2]`` array
-    (numpy or torch, on any device) of (record of ``a``, record of ``b``); ``top_pairs`` makes
-    one from ``distance.record_scores``.  The substitution score of two rows is
-    ``cosine * match_scale + match_shift`` (two rounded float32 operations); ``gap_open`` (the
-    cost of a gap's first position) and ``gap_extend`` are required, ``0 <= gap_extend <=
-    gap_open``.
-
-    Every argument error is a ``ValueError`` before a device is touched: a pair out of range, a
-    record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
-    finite or out of order.  ``P == 0`` returns empty tensors without a launch."""
+def _align(span: bool, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
+           match_shift, workspace):
+    """The checks and the one launch behind ``local_align`` (``span`` False: scores, ends) and
+    ``local_spans`` (True: scores, starts, ends).  Every argument error is raised before a device
+    is touched."""
     gap_open = _checked_parameter(gap_open, "gap_open")
     gap_extend = _checked_parameter(gap_extend, "gap_extend")
     match_scale = _checked_parameter(match_scale, "match_scale")
@@ -144,21 +151,65 @@ def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     with torch.cuda.device(a.device):
         scores = torch.zeros(count, dtype=torch.float32, device=a.device)
         ends = torch.full((count, 2), -1, dtype=torch.int32, device=a.device)
+        starts = torch.full((count, 2), -1, dtype=torch.int32, device=a.device) if span else None
         if count == 0 or n == 0 or m == 0:   # no pair, or no pair with a row on both sides
-            return scores, ends
+            return scores, starts, ends
         lib = native.library()
-        need = lib.gfy_align_workspace_bytes(count, int(rows_b.max()))
+        name = "gfy_align_local_span" if span else "gfy_align_local"
+        sizer = lib.gfy_align_span_workspace_bytes if span else lib.gfy_align_workspace_bytes
+        need = sizer(count, int(rows_b.max()))
         scratch = (workspace or AlignWorkspace()).buffer(a.device, need)
         ptr_a_dev = torch.from_numpy(ptr_a.astype(np.int32)).to(a.device)
         ptr_b_dev = torch.from_numpy(ptr_b.astype(np.int32)).to(a.device)
         pairs_dev = torch.from_numpy(pairs).to(a.device)
-        native.check(lib.gfy_align_local(
+        outputs = (scores.data_ptr(), starts.data_ptr(), ends.data_ptr()) if span else \
+            (scores.data_ptr(), ends.data_ptr())
+        native.check(getattr(lib, name)(
             a.data_ptr(), n, ptr_a_dev.data_ptr(), ptr_a.size - 1, b.data_ptr(), m,
             ptr_b_dev.data_ptr(), ptr_b.size - 1, pairs_dev.data_ptr(), count, match_scale,
-            match_shift, gap_open, gap_extend, scores.data_ptr(), ends.data_ptr(),
-            scratch.data_ptr(), scratch.numel(),
-            torch.cuda.current_stream(a.device).cuda_stream), "gfy_align_local")
+            match_shift, gap_open, gap_extend, *outputs, scratch.data_ptr(), scratch.numel(),
+            torch.cuda.current_stream(a.device).cuda_stream), name)
+    return scores, starts, ends
+
+
+def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None
+                ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Local alignment of the record pairs ``pairs``: ``(scores float32 [P], ends int32 [P, 2])``
+    on the device, exact, the ``Lq x Lr`` matrix of a pair never written (the definition is at
+    the head of this module; it is this project's own and not ``ginfinity-sw``'s).
+
+    ``a`` / ``b`` are fp16 ``[rows, 128]`` embeddings as ``distance.pairwise`` takes them,
+    ``counts_a`` / ``counts_b`` the row counts of their contiguous records.  With ``b`` omitted
+    ``a`` is aligned against itself and ``counts_b`` defaults to ``counts_a``; nothing is
+    excluded, ``(q, q)`` aligns a record with itself.  ``pairs`` is an integer ``[P, 2]`` array
+    (numpy or torch, on any device) of (record of ``a``, record of ``b``); ``top_pairs`` makes
+    one from ``distance.record_scores``.  The substitution score of two rows is
+    ``cosine * match_scale + match_shift`` (two rounded float32 operations); ``gap_open`` (the
+    cost of a gap's first position) and ``gap_extend`` are required, ``0 <= gap_extend <=
+    gap_open``.
+
+    Every argument error is a ``ValueError`` before a device is touched: a pair out of range, a
+    record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
+    finite or out of order.  ``P == 0`` returns empty tensors without a launch."""
+    scores, _, ends = _align(False, a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                             match_scale, match_shift, workspace)
     return scores, ends
+
+
+def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None
+                ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``local_align`` with the start cell of every alignment: ``(scores float32 [P], starts
+    int32 [P, 2], ends int32 [P, 2])`` on the device.  Rows ``starts[p, 0] .. ends[p, 0]`` of the
+    a-record and ``starts[p, 1] .. ends[p, 1]`` of the b-record are the stretch that takes part
+    (the origin rules are at the head of this module).  Scores and ends are those of
+    ``local_align`` bit for bit; a score of 0 gives a start of ``(-1, -1)``.
+
+    The arguments, their checks and the ``ValueError``s are those of ``local_align``; an
+    ``AlignWorkspace`` serves both functions (this one needs twice the bytes)."""
+    return _align(True, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
+                  match_shift, workspace)
 
 
 def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
@@ -184,4 +235,4 @@ def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
     return np.stack([rows, order.reshape(-1)], axis=1).astype(np.int32)
 
 
-__all__ = ["local_align", "AlignWorkspace", "top_pairs"]
+__all__ = ["local_align", "local_spans", "AlignWorkspace", "top_pairs"]

@@ -1,0 +1,367 @@
+// The one alignment loop of the library (semantics: include/gfy.h), shared by k_align_local
+// (align_local.hip, kSpan = false: score and end) and k_align_span (align_span.hip, kSpan = true:
+// score, start and end), as pairwise_topk.inc is shared by the top-k family.
+//
+// One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
+// wave takes pairs wave, wave + waves of the grid, ... until the list ends.
+//   * The wave walks the a-record in strips of 64 rows, lane = row, and sweeps the b-record with
+//     the usual skew: at step t lane l is at column t - l.  H and F of the row above come from
+//     lane l - 1 (one wave shift each), H of the diagonal is last step's H from above, E and H
+//     of the left neighbour are the lane's own registers.  Every cell is the fixed expression of
+//     include/gfy.h of its three predecessors, so nothing depends on the schedule.
+//   * The substitution scores come 32 columns at a time: the 32 b-rows go to LDS in the swizzled
+//     layout of the sweep, sweep_multiply (pairwise_sweep.inc, the one multiply of the library)
+//     forms the 64 x 32 products against the strip's fragments, which stay in registers, and the
+//     epilogue turns them into the dense kernel's cosine (same key, same pair_value), scales and
+//     shifts it with two rounded operations and stores it BY ANTI-DIAGONAL: cell (l, j) at
+//     [(l + j) % 128][l], a ring of 128 diagonals of 64 lanes (32 KB).  A step reads one diagonal:
+//     64 consecutive words, no bank conflict.  Before step t = 32 kb the ring holds diagonals
+//     t .. t + 62 of earlier columns, the new columns add up to t + 94, and the quarter behind
+//     them (t + 96 .. t + 127, spent by the last 32 steps) stages the b-rows.
+//   * The strip's last row goes to the workspace as lane 63 forms it and comes back to lane 0 of
+//     the next strip 32 columns at a time, one load ahead, two buffers in turn: (H, F) per column,
+//     8 bytes, and with kSpan (H, F, origin of H, origin of F), 16 bytes in one store and one load.
+//   * Each lane keeps its best (H, i, j) with a strict >, which is the lowest (i, j) of the lane's
+//     rows; one butterfly at the end orders by (score descending, i ascending, j ascending).
+//   * kSpan: every positive H, E and F has an origin, the first matched cell of the path behind
+//     it, one word (i0 << 12) | j0.  A lane keeps the origins of h, e, f and diag and that of its
+//     best cell; the two values that cross lanes each step take theirs along, and so does the
+//     butterfly.  An origin is SELECTED where its value is formed, by comparing the very operands
+//     of the max — the max expressions themselves are those of kSpan = false, so scores and ends
+//     are the same bits.  With kSpan = false none of it exists.
+// ptr_a, ptr_b and pairs are device arrays: they are compared and clipped, a pair outside them or
+// longer than the limits gets NaN and (-2, -2), and nothing outside the caller's buffers is read.
+#pragma once
+#include <type_traits>
+
+#include "gfy_common.h"
+#include "pairwise_sweep.inc"
+
+namespace gfy {
+namespace {
+
+constexpr int kAlignWaves = 4;                 // pairs in flight per workgroup
+constexpr int kAlignThreads = 64 * kAlignWaves;
+constexpr int kStrip = 64;                     // a-rows per strip: lane = row
+constexpr int kSub = 32;                       // b-rows per multiply
+constexpr int kRingBytes = 128 * kStrip * 4;   // 128 anti-diagonals
+constexpr int kWaveLds = kRingBytes + kStrip * 4 + kSub * 4;   // ring, 1/|a| of the strip, s of the b-rows
+constexpr int kAlignLds = kAlignWaves * kWaveLds;
+constexpr int kAlignGroupsMax = 256;           // one per compute unit (its LDS holds one): the waves loop
+constexpr int kOriginBits = 12;                // an origin is (i0 << 12) | j0
+static_assert(kRingBytes == kBuffers * (kSub * 256), "a quarter of the ring stages 32 b-rows");
+static_assert(kAlignLds <= 160 * 1024, "the LDS of a compute unit");
+static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an origin fit its word");
+
+struct AlignArgs {
+  const f16* a;
+  const f16* b;
+  const int32_t* ptr_a;
+  const int32_t* ptr_b;
+  const int32_t* pairs;   // [P][2]
+  int64_t n, m, P;
+  int records_a, records_b;
+  float match_scale, match_shift, gap_open, gap_extend;
+  float* out_score;       // [P]
+  int32_t* out_end;       // [P][2]
+  void* carry;            // [waves of the grid][2][cap] entries of a strip's last row
+  int cap;                // columns a carry buffer holds
+};
+
+// a carry entry: (H, F) of a column, and with kSpan their origins behind them
+template <bool kSpan>
+using AlignCarry = std::conditional_t<kSpan, u32x4, float2>;
+
+// what one wave writes is read by its other lanes: LDS executes a wave's instructions in order,
+// so only the compiler has to be told
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+}
+
+__device__ __forceinline__ float lane_value(float x, int lane /* wave-uniform */) {
+  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), lane));
+}
+
+// record `index` of running sums `ptr` over `rows` rows, clipped into them
+__device__ __forceinline__ void record_rows(const int32_t* ptr, int index, int64_t rows,
+                                            int64_t& lo, int64_t& hi) {
+  lo = ptr[index];
+  hi = ptr[index + 1];
+  lo = lo < 0 ? 0 : lo > rows ? rows : lo;
+  hi = hi < lo ? lo : hi > rows ? rows : hi;
+}
+
+// out_start ([P][2]) is written with kSpan alone
+template <bool kSpan>
+__device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start) {
+  using Carry = AlignCarry<kSpan>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = lane & 31, hq = lane >> 5;
+  char* ring = smem + wave * kWaveLds;
+  float* ring_f = reinterpret_cast<float*>(ring);
+  float* a_inv = reinterpret_cast<float*>(ring + kRingBytes);   // [kStrip]
+  float* b_s = a_inv + kStrip;                                  // [kSub]
+  const int64_t slot = (int64_t)blockIdx.x * kAlignWaves + wave;
+  const int64_t slots = (int64_t)gridDim.x * kAlignWaves;
+  Carry* carry = reinterpret_cast<Carry*>(p.carry) + slot * 2 * p.cap;
+  const float go = p.gap_open, ge = p.gap_extend;
+  const float minus_inf = -__builtin_inff();
+
+  for (int64_t pair = slot; pair < p.P; pair += slots) {
+    const int q = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair]);
+    const int rec = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair + 1]);
+    bool ok = (uint32_t)q < (uint32_t)p.records_a && (uint32_t)rec < (uint32_t)p.records_b;
+    int64_t a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;
+    if (ok) {
+      record_rows(p.ptr_a, q, p.n, a_lo, a_hi);
+      record_rows(p.ptr_b, rec, p.m, b_lo, b_hi);
+    }
+    ok = ok && a_hi - a_lo <= GFY_ALIGN_ROWS_MAX && b_hi - b_lo <= GFY_ALIGN_ROWS_MAX &&
+         b_hi - b_lo <= p.cap;
+    const int lq = __builtin_amdgcn_readfirstlane(ok ? (int)(a_hi - a_lo) : 0);
+    const int lr = __builtin_amdgcn_readfirstlane(ok ? (int)(b_hi - b_lo) : 0);
+    const f16* rows_a = p.a + a_lo * 128;
+    const f16* rows_b = p.b + b_lo * 128;
+
+    float best = 0.f;   // strict >: only a positive cell is ever kept
+    int best_i = -1, best_j = -1;
+    uint32_t best_o = 0;   // kSpan: the origin of the best cell
+
+    // 32 b-rows from column c0 on as this lane's eight 16-byte pieces: piece lane + 64 x is
+    // chunk lane & 15 of row (lane >> 4) + 4 x — a row on 16 consecutive lanes (row_square_sum)
+    auto load_b = [&](f16x8 (&v)[8], int c0) __attribute__((always_inline)) {
+#pragma unroll
+      for (int x = 0; x < 8; ++x) {
+        const int col = c0 + (lane >> 4) + 4 * x;
+        v[x] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        if (col < lr) v[x] = *reinterpret_cast<const f16x8*>(rows_b + (int64_t)col * 128 + (lane & 15) * 8);
+      }
+    };
+
+    const int strips = lq > 0 && lr > 0 ? (lq + kStrip - 1) / kStrip : 0;
+    for (int strip = 0; strip < strips; ++strip) {
+      const int i0 = strip * kStrip;
+      const int rows = lq - i0 < kStrip ? lq - i0 : kStrip;
+      const bool onward = strip + 1 < strips;   // lane 63's row feeds another strip
+      const Carry* carry_in = carry + (size_t)((strip + 1) & 1) * p.cap;
+      Carry* carry_out = carry + (size_t)(strip & 1) * p.cap;
+
+      // the strip's rows through the ring's first half (free: no column is in flight) into the
+      // MFMA fragments, and 1 / |a_i| next to them
+#pragma unroll 4
+      for (int x = 0; x < 16; ++x) {
+        const int row = (lane >> 4) + 4 * x, ch = lane & 15;
+        f16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (row < rows) v = *reinterpret_cast<const f16x8*>(rows_a + (int64_t)(i0 + row) * 128 + ch * 8);
+        const float ss = row_square_sum(v);
+        *reinterpret_cast<f16x8*>(ring + off256(row, ch)) = v;
+        if (ch == 0) a_inv[row] = inverse_norm(ss);
+      }
+      wave_sync();
+      f16x8 af[2][8];
+#pragma unroll
+      for (int at = 0; at < 2; ++at)
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks)
+          af[at][ks] = *reinterpret_cast<const f16x8*>(ring + off256(32 * at + r, 2 * ks + hq));
+      const float a_term[2] = {a_inv[r], a_inv[32 + r]};
+      wave_sync();
+
+      float h = 0.f, e = minus_inf, f = minus_inf;   // this lane's last cell
+      float diag = 0.f;                              // H of the row above, one column back
+      uint32_t o_h = 0, o_e = 0, o_f = 0, o_diag = 0;   // kSpan: their origins
+      f16x8 b_next[8];
+      load_b(b_next, 0);
+      // the carry entries of the row above the strip for columns c0 + lane, lanes 0..31
+      auto load_carry = [&](int c0) __attribute__((always_inline)) {
+        Carry v;
+        if constexpr (kSpan) v = Carry{__float_as_uint(0.f), __float_as_uint(minus_inf), 0u, 0u};
+        else v = make_float2(0.f, minus_inf);
+        if (strip > 0 && lane < kSub && c0 + lane < lr) v = carry_in[c0 + lane];
+        return v;
+      };
+      Carry carry_next = load_carry(0);
+
+      const int steps = lr + rows - 1;
+      for (int t0 = 0; t0 < steps; t0 += kSub) {
+        if (t0 < lr) {   // columns t0 .. t0 + 31 join the ring
+          char* stage = ring + (((t0 >> 5) + 3) & 3) * (kSub * 256);
+#pragma unroll
+          for (int x = 0; x < 8; ++x) {
+            const int row = (lane >> 4) + 4 * x, ch = lane & 15;
+            const float ss = row_square_sum(b_next[x]);
+            *reinterpret_cast<f16x8*>(stage + off256(row, ch)) = b_next[x];
+            if (ch == 0) b_s[row] = -inverse_norm(ss);   // s_j of k_row_terms
+          }
+          wave_sync();
+          f32x16 acc[2];
+          sweep_multiply<2, false>(acc, af, stage, 0, 0, r, hq);
+          if (t0 + kSub < lr) load_b(b_next, t0 + kSub);
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            const int jl = 4 * hq + 8 * g;   // 4 consecutive b-rows
+            const f32x4 sv = *reinterpret_cast<const f32x4*>(b_s + jl);
+#pragma unroll
+            for (int at = 0; at < 2; ++at)
+#pragma unroll
+              for (int i = 0; i < 4; ++i) {
+                const float key = __builtin_fmaf(acc[at][4 * g + i], sv[i], 0.0f);
+                const float cosine = pair_value(key, a_term[at], GFY_COSINE);
+                const float score = __fadd_rn(__fmul_rn(cosine, p.match_scale), p.match_shift);
+                const int row = 32 * at + r;
+                ring_f[((t0 + jl + i + row) & 127) * kStrip + row] = score;
+              }
+          }
+          wave_sync();
+        }
+        const Carry from_above = carry_next;
+        carry_next = load_carry(t0 + kSub);
+        const int t_end = t0 + kSub < steps ? t0 + kSub : steps;
+        for (int t = t0; t < t_end; ++t) {
+          const int j = t - lane;
+          float up_h = __shfl_up(h, 1, 64), up_f = __shfl_up(f, 1, 64);
+          float above_h, above_f;
+          if constexpr (kSpan) {
+            above_h = __uint_as_float(__builtin_amdgcn_readlane(from_above.x, t - t0));
+            above_f = __uint_as_float(__builtin_amdgcn_readlane(from_above.y, t - t0));
+          } else {
+            above_h = lane_value(from_above.x, t - t0);
+            above_f = lane_value(from_above.y, t - t0);
+          }
+          if (lane == 0) up_h = above_h, up_f = above_f;
+          const float s = ring_f[(t & 127) * kStrip + lane];
+          const bool live = (uint32_t)j < (uint32_t)lr && lane < rows;
+          const float e_ext = e - ge, e_open = h - go;
+          const float f_ext = up_f - ge, f_open = up_h - go;
+          const float match = diag + s;
+          const float e_new = __builtin_fmaxf(e_ext, e_open);
+          const float f_new = __builtin_fmaxf(f_ext, f_open);
+          const float h_new = __builtin_fmaxf(__builtin_fmaxf(0.f, match),
+                                              __builtin_fmaxf(e_new, f_new));
+          uint32_t o_new = 0;
+          if constexpr (kSpan) {
+            uint32_t up_oh = (uint32_t)__shfl_up((int)o_h, 1, 64);
+            uint32_t up_of = (uint32_t)__shfl_up((int)o_f, 1, 64);
+            const uint32_t above_oh = __builtin_amdgcn_readlane(from_above.z, t - t0);
+            const uint32_t above_of = __builtin_amdgcn_readlane(from_above.w, t - t0);
+            if (lane == 0) up_oh = above_oh, up_of = above_of;
+            // opening wins a tie; diagonal, then E, then F; a path starts where its diagonal
+            // predecessor is not positive
+            const uint32_t here = ((uint32_t)(i0 + lane) << kOriginBits) | (uint32_t)j;
+            const uint32_t oe_new = e_open >= e_ext ? o_h : o_e;
+            const uint32_t of_new = f_open >= f_ext ? up_oh : up_of;
+            o_new = h_new == match ? (diag > 0.f ? o_diag : here) : h_new == e_new ? oe_new : of_new;
+            o_e = live ? oe_new : o_e;
+            o_f = live ? of_new : o_f;
+            o_h = live ? o_new : o_h;
+            o_diag = live ? up_oh : o_diag;
+          }
+          e = live ? e_new : e;
+          f = live ? f_new : f;
+          h = live ? h_new : h;
+          diag = live ? up_h : diag;
+          const bool better = live && h_new > best;
+          best = better ? h_new : best;
+          best_i = better ? i0 + lane : best_i;
+          best_j = better ? j : best_j;
+          if constexpr (kSpan) best_o = better ? o_new : best_o;
+          if (onward && lane == kStrip - 1 && live) {
+            if constexpr (kSpan)
+              carry_out[j] = Carry{__float_as_uint(h_new), __float_as_uint(f_new), o_h, o_f};
+            else
+              carry_out[j] = make_float2(h_new, f_new);
+          }
+        }
+      }
+      // the next strip reads what lane 63 stored (and restages the ring)
+      __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+      wave_sync();
+    }
+
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) {
+      const float ob = __shfl_xor(best, mask, 64);
+      const int oi = __shfl_xor(best_i, mask, 64), oj = __shfl_xor(best_j, mask, 64);
+      const bool take = ob > best || (ob == best && (oi < best_i || (oi == best_i && oj < best_j)));
+      if constexpr (kSpan) {
+        const uint32_t oo = (uint32_t)__shfl_xor((int)best_o, mask, 64);
+        best_o = take ? oo : best_o;
+      }
+      best = take ? ob : best;
+      best_i = take ? oi : best_i;
+      best_j = take ? oj : best_j;
+    }
+    if (lane == 0) {
+      const bool none = !(best > 0.f);
+      p.out_score[pair] = ok ? (none ? 0.f : best) : __builtin_nanf("");
+      p.out_end[2 * pair] = ok ? (none ? -1 : best_i) : -2;
+      p.out_end[2 * pair + 1] = ok ? (none ? -1 : best_j) : -2;
+      if constexpr (kSpan) {
+        out_start[2 * pair] = ok ? (none ? -1 : (int)(best_o >> kOriginBits)) : -2;
+        out_start[2 * pair + 1] = ok ? (none ? -1 : (int)(best_o & ((1u << kOriginBits) - 1))) : -2;
+      }
+    }
+  }
+}
+
+int align_groups(int64_t pairs) {
+  const int64_t groups = (pairs + kAlignWaves - 1) / kAlignWaves;
+  return (int)(groups < 1 ? 1 : groups > kAlignGroupsMax ? kAlignGroupsMax : groups);
+}
+
+// two carry buffers of max_rows_b entries per wave of the grid
+template <bool kSpan>
+size_t align_carry_bytes(int64_t pairs, int64_t max_rows_b) {
+  const size_t waves = (size_t)align_groups(pairs) * kAlignWaves;
+  return align_up(waves * 2 * (size_t)max_rows_b * sizeof(AlignCarry<kSpan>) + 1, 256);
+}
+
+// the launch both kernels share: the workspace check, the LDS opt-in (once per device and
+// kernel) and the arguments; `launch(groups, p)` starts the kernel
+template <bool kSpan, typename Launch>
+int align_launch(const char* who, const void* kernel, const void* a, int64_t n,
+                 const int32_t* ptr_a, int64_t records_a, const void* b, int64_t m,
+                 const int32_t* ptr_b, int64_t records_b, const int32_t* pairs, int64_t P,
+                 float match_scale, float match_shift, float gap_open, float gap_extend,
+                 float* out_score, int32_t* out_end, void* ws, size_t ws_bytes, Launch&& launch) {
+  GFY_REQUIRE(ws_bytes >= align_carry_bytes<kSpan>(P, 0), GFY_ERR_WORKSPACE,
+              "%s: workspace %zu < required %zu", who, ws_bytes, align_carry_bytes<kSpan>(P, 0));
+  const int groups = align_groups(P);
+  const size_t columns =
+      ws_bytes / ((size_t)groups * kAlignWaves * 2 * sizeof(AlignCarry<kSpan>));
+  static PerDeviceOnce opt_in;
+  if (const int rc = opt_in.run([kernel]() -> int {
+        GFY_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                          kAlignLds));
+        return GFY_OK;
+      }))
+    return rc;
+  AlignArgs p{};
+  p.a = (const f16*)a;
+  p.b = (const f16*)b;
+  p.ptr_a = ptr_a;
+  p.ptr_b = ptr_b;
+  p.pairs = pairs;
+  p.n = n;
+  p.m = m;
+  p.P = P;
+  p.records_a = (int)records_a;
+  p.records_b = (int)records_b;
+  p.match_scale = match_scale;
+  p.match_shift = match_shift;
+  p.gap_open = gap_open;
+  p.gap_extend = gap_extend;
+  p.out_score = out_score;
+  p.out_end = out_end;
+  p.carry = ws;
+  p.cap = (int)(columns < GFY_ALIGN_ROWS_MAX ? columns : GFY_ALIGN_ROWS_MAX);
+  launch(groups, p);
+  GFY_CHECK_HIP(hipGetLastError());
+  return GFY_OK;
+}
+
+}  // namespace
+}  // namespace gfy

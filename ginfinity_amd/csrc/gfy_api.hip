@@ -1149,25 +1149,21 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
                                  out_scores, ws, ws_bytes, (hipStream_t)stream);
 }
 
-size_t gfy_align_workspace_bytes(int64_t pairs, int64_t max_rows_b) {
-  return align_workspace_bytes(pairs < 1 ? 1 : pairs,
-                               max_rows_b < 0 ? 0 : max_rows_b > GFY_ALIGN_ROWS_MAX
-                                   ? GFY_ALIGN_ROWS_MAX : max_rows_b);
-}
-
-int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
-                    const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
-                    const int32_t* pairs, int64_t P, float match_scale, float match_shift,
-                    float gap_open, float gap_extend, float* out_score, int32_t* out_end,
-                    void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  const char* who = "gfy_align_local";
+// the argument rules gfy_align_local and gfy_align_local_span share; out_start is checked by the
+// span call alone (between out_score and out_end, the order of its arguments)
+static int check_align_call(const char* who, const void* a, int64_t n, const int32_t* ptr_a,
+                            int64_t records_a, const void* b, int64_t m, const int32_t* ptr_b,
+                            int64_t records_b, const int32_t* pairs, int64_t P, float match_scale,
+                            float match_shift, float gap_open, float gap_extend,
+                            const float* out_score, const int32_t* out_start, bool with_start,
+                            const int32_t* out_end, const void* ws) {
   GFY_REQUIRE(a, GFY_ERR_INVALID, "%s: a is NULL", who);
   GFY_REQUIRE(b, GFY_ERR_INVALID, "%s: b is NULL", who);
   GFY_REQUIRE(ptr_a, GFY_ERR_INVALID, "%s: ptr_a is NULL", who);
   GFY_REQUIRE(ptr_b, GFY_ERR_INVALID, "%s: ptr_b is NULL", who);
   GFY_REQUIRE(pairs, GFY_ERR_INVALID, "%s: pairs is NULL", who);
   GFY_REQUIRE(out_score, GFY_ERR_INVALID, "%s: out_score is NULL", who);
+  GFY_REQUIRE(!with_start || out_start, GFY_ERR_INVALID, "%s: out_start is NULL", who);
   GFY_REQUIRE(out_end, GFY_ERR_INVALID, "%s: out_end is NULL", who);
   GFY_REQUIRE(ws, GFY_ERR_INVALID, "%s: workspace is NULL", who);
   GFY_REQUIRE(n > 0 && m > 0 && n < INT32_MAX && m < INT32_MAX, GFY_ERR_INVALID,
@@ -1184,9 +1180,49 @@ int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
   GFY_REQUIRE(0.0f <= gap_extend && gap_extend <= gap_open, GFY_ERR_INVALID,
               "%s: 0 <= gap_extend <= gap_open required, got gap_open = %g, gap_extend = %g", who,
               (double)gap_open, (double)gap_extend);
+  return GFY_OK;
+}
+
+static int64_t clipped_align_rows(int64_t max_rows_b) {
+  return max_rows_b < 0 ? 0 : max_rows_b > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : max_rows_b;
+}
+
+size_t gfy_align_workspace_bytes(int64_t pairs, int64_t max_rows_b) {
+  return align_workspace_bytes(pairs < 1 ? 1 : pairs, clipped_align_rows(max_rows_b));
+}
+
+size_t gfy_align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b) {
+  return align_span_workspace_bytes(pairs < 1 ? 1 : pairs, clipped_align_rows(max_rows_b));
+}
+
+int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                    const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                    const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                    float gap_open, float gap_extend, float* out_score, int32_t* out_end,
+                    void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (const int rc = check_align_call("gfy_align_local", a, n, ptr_a, records_a, b, m, ptr_b,
+                                      records_b, pairs, P, match_scale, match_shift, gap_open,
+                                      gap_extend, out_score, nullptr, false, out_end, ws))
+    return rc;
   return launch_align_local(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale,
                             match_shift, gap_open, gap_extend, out_score, out_end, ws, ws_bytes,
                             (hipStream_t)stream);
+}
+
+int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                         float gap_open, float gap_extend, float* out_score, int32_t* out_start,
+                         int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  if (const int rc = check_align_call("gfy_align_local_span", a, n, ptr_a, records_a, b, m, ptr_b,
+                                      records_b, pairs, P, match_scale, match_shift, gap_open,
+                                      gap_extend, out_score, out_start, true, out_end, ws))
+    return rc;
+  return launch_align_local_span(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P,
+                                 match_scale, match_shift, gap_open, gap_extend, out_score,
+                                 out_start, out_end, ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

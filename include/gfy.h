@@ -611,8 +611,8 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
  *               keeps no promise of its sign.
  *   Limits      a record has at most GFY_ALIGN_ROWS_MAX rows; 0 <= gap_extend <= gap_open, the
  *               four parameters finite; 1 <= P < 2^31.  Rows holding inf / NaN give unspecified
- *               values.  No traceback or start positions, no banded or global alignment, no
- *               normalisation of scores.
+ *               values.  No traceback (gfy_align_local_span gives the start cell), no banded or
+ *               global alignment, no normalisation of scores.
  *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), max_rows_b the longest b-record any
  *               pair names: the last row of a 64-row strip of A, per wave in flight.
  *   ptr_a, ptr_b and pairs are device arrays, which the kernel only compares and clips.  A pair
@@ -632,6 +632,45 @@ int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
                     float match_scale, float match_shift, float gap_open, float gap_extend,
                     float* out_score /* [P] */, int32_t* out_end /* [P][2] */,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* gfy_align_local with the START cell of every alignment: the stretch start..end of both records
+ * is what takes part.  C, s, E, F, H, out_score and out_end are those of gfy_align_local, bit for
+ * bit; the origin of the best path is carried through the same recurrences, so the L_q x L_r
+ * matrix is still never written.
+ *   Origins     every E, F and H that is > 0 has an origin (i0, j0), the first matched cell of
+ *               the path that produced it:
+ *               H[i][j]  the origin of the first candidate, in the order diagonal, then E, then
+ *                        F, whose value equals H[i][j].  The diagonal candidate H[i-1][j-1] +
+ *                        s[i][j] carries the origin of H[i-1][j-1] if that value is > 0, and
+ *                        (i, j) itself otherwise (a predecessor that is 0 of either sign, or
+ *                        outside the matrix: the alignment starts here).
+ *               E[i][j]  the origin of H[i][j-1] if H[i][j-1] - gap_open >= E[i][j-1] -
+ *                        gap_extend (opening wins a tie), else that of E[i][j-1].
+ *               F[i][j]  the same rule with the row above.
+ *               A value <= 0 has no origin; what is carried for it is unspecified and never
+ *               reaches a positive H, since a positive E or F descends from a positive H.
+ *   Result      out_start[p] = the origin of H at out_end[p]; (-1, -1) with a score of 0, (-2, -2)
+ *               for a pair that is refused, as out_end.  An origin is a fixed function of the
+ *               three predecessors: a pair's start depends neither on the other pairs of the call
+ *               nor on the run, bit for bit.
+ *   It follows  start <= end in both coordinates; s[start] == H[start] > 0; and the same
+ *               recurrences run on the box start..end alone reach, at the box's last cell,
+ *               exactly out_score, bit for bit (rounded addition and max are monotone and the
+ *               path's own operations are unchanged).  A later traceback only has to revisit
+ *               that box.
+ *   Workspace   gfy_align_span_workspace_bytes(pairs, max_rows_b): a strip's last row carries
+ *               (H, F, origin of H, origin of F), 16 bytes per column, twice gfy_align_local's.
+ *   Arguments, clipping of what the device arrays hold and error codes are those of
+ *   gfy_align_local; a NULL out_start is GFY_ERR_INVALID and named.
+ *   No traceback, no banded or global alignment, no normalisation of scores.                  */
+size_t gfy_align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
+int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs /* [P][2] device */, int64_t P,
+                         float match_scale, float match_shift, float gap_open, float gap_extend,
+                         float* out_score /* [P] */, int32_t* out_start /* [P][2] */,
+                         int32_t* out_end /* [P][2] */,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

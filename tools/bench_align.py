@@ -11,7 +11,13 @@ host, UTC time, device, ROCm / torch versions, the commit (``--commit``, or ``gi
 HEAD`` where the tree is a checkout) and a SHA-256 of align_local.hip.  Writes one JSON document
 (default profiles/align_bench.json) and prints it.
 
+``--spans`` times ``align.local_spans`` (score, start and end) after ``local_align`` in the same
+run, on the same pairs and with the same warm-up and repeats, and adds ``spans_seconds``,
+``spans_cell_updates_per_s``, ``spans_over_local_align`` (the ratio of the two medians) and the
+SHA-256 of the span kernel's sources; without the flag nothing changes.
+
     python tools/bench_align.py --pairs 20000
+    python tools/bench_align.py --pairs 20000 --spans
 """
 from __future__ import annotations
 
@@ -34,6 +40,7 @@ sys.path.insert(0, str(ROOT))
 from ginfinity_amd import align, distance, synthetic  # noqa: E402
 
 KERNEL_SOURCE = "align_local.hip"
+SPAN_SOURCES = ("align_local.inc", "align_span.hip")     # --spans: the shared body and its kernel
 
 
 def _commit() -> str | None:
@@ -90,6 +97,8 @@ def main() -> None:
     parser.add_argument("--warmup", type=int, default=2)
     parser.add_argument("--host-pairs", type=int, default=4,
                         help="pairs of the host numpy DP timed for scale (0: none)")
+    parser.add_argument("--spans", action="store_true",
+                        help="time align.local_spans as well, after local_align")
     parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
     parser.add_argument("--out", default=str(ROOT / "profiles" / "align_bench.json"))
     args = parser.parse_args()
@@ -124,6 +133,19 @@ def main() -> None:
               "cell_updates_per_s": cells / mid}
     print(f"local_align: {mid:.4f} s for {args.pairs} pairs = {args.pairs / mid:.3e} pairs/s, "
           f"{cells / mid:.3e} cell updates/s", file=sys.stderr, flush=True)
+    if args.spans:
+        span_seconds = _timed(lambda: align.local_spans(rows, counts_a=counts, pairs=pairs_dev,
+                                                        workspace=keeper, **parameters),
+                              args.repeats, args.warmup)
+        span_mid = statistics.median(span_seconds)
+        result["spans_seconds"] = _span(span_seconds)
+        result["spans_cell_updates_per_s"] = cells / span_mid
+        result["spans_over_local_align"] = span_mid / mid
+        result["spans_source_sha256"] = {
+            name: hashlib.sha256((source.parent / name).read_bytes()).hexdigest()
+            for name in SPAN_SOURCES}
+        print(f"local_spans: {span_mid:.4f} s = {cells / span_mid:.3e} cell updates/s, "
+              f"{span_mid / mid:.3f} x local_align", file=sys.stderr, flush=True)
     if args.host_pairs > 0:
         some = pairs[:args.host_pairs]
         host_seconds, host_cells = 0.0, 0

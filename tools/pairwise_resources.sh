@@ -3,7 +3,8 @@
 #   bash tools/pairwise_resources.sh [extra hipcc flags]
 #   GFY_SOURCE=pairwise_topk.hip bash tools/pairwise_resources.sh     # the top-k kernels
 #   GFY_SOURCE=pairwise_topk_ranges.hip bash tools/pairwise_resources.sh   # ... with per-row ranges
-#   GFY_SOURCE=align_local.hip bash tools/pairwise_resources.sh       # the local aligner (288 VGPRs, no scratch, no barrier)
+#   GFY_SOURCE=align_local.hip bash tools/pairwise_resources.sh       # the local aligner (no scratch, no barrier)
+#   GFY_SOURCE=align_span.hip bash tools/pairwise_resources.sh        # ... with start cells
 # Per kernel: registers, spills, scratch, and how many MFMA, LDS-DMA, 16-byte LDS read and barrier
 # instructions its code holds (the figures a refactor of the sweep must leave alone).
 # The assembly is left in $GFY_ASM_OUT (default /tmp/<source stem>.s, i.e. /tmp/pairwise.s).
