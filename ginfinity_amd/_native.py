@@ -140,6 +140,11 @@ SIGNATURES: dict[str, tuple] = {
                                      c_void_p, c_int64, c_void_p, c_int64, c_float, c_float,
                                      c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),
+    "gfy_align_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gfy_align_trace": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                                c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_float,
+                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -50,16 +50,39 @@ A value <= 0 has no origin, and none is needed: a positive E or F descends from 
 function of the three predecessors, so a start is as independent of company and run as a score.
 It follows that ``start <= end`` in both coordinates, that ``s[start] == H[start] > 0``, and that
 the same recurrences run on the box ``start..end`` alone reach exactly ``score`` at the box's last
-cell, bit for bit: a later traceback only has to revisit that box.
+cell, bit for bit: the traceback only has to revisit that box.
+
+The aligned path.  ``local_paths`` returns, next to score, start and end, the path itself: the
+walk back from ``end`` by the origin rules above, nothing new.  A state is one of H, E or F at a
+cell, and the walk starts in H at ``end``:
+
+    H at (i, j)   if ``H == H[i-1][j-1] + s[i][j]``: op ``0`` (row i of A matched with row j of B);
+                  then, if ``H[i-1][j-1] > 0``, on in H at (i-1, j-1), otherwise stop (this cell
+                  is ``start``).  If H is not the diagonal candidate but ``H == E[i][j]``: E at
+                  the same cell.  Otherwise F at the same cell.
+    E at (i, j)   op ``1`` (row j of B faces a gap); on at (i, j-1), in H if ``H[i][j-1] -
+                  gap_open >= E[i][j-1] - gap_extend`` (opening wins a tie), otherwise in E
+    F at (i, j)   op ``2`` (row i of A faces a gap); on at (i-1, j) by the same rule with the
+                  row above
+
+The ops are reported in forward order, ``start`` to ``end``.  The first and the last op are
+``0``; the ops ``0`` and ``2`` number ``end_i - start_i + 1``, the ops ``0`` and ``1`` ``end_j -
+start_j + 1``; a score of 0 has an empty path.  Re-scoring the ops (``h = 0``; op 0: ``h = fl32(h
++ s[i][j])``; the first op of a run of equal gap ops ``g = fl32(h - gap_open)``, each further one
+``g = fl32(g - gap_extend)``, and ``h = g`` after the run) gives ``score`` bit for bit.  The
+device walks the box ``start..end`` alone, which gives the same ops as the full matrix
+(include/gfy.h has the argument), and keeps 4 bits per cell of the box in scratch memory: the
+only thing proportional to ``Lq x Lr`` that is ever written.
 
 Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIMUM_LENGTH_NT``),
-``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: the aligned path
-itself (traceback), banded or global alignment, a ``device="cpu"`` path, and any z-score or
-normalisation of the scores.  Measured cost: DESIGN.md §4.
+``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: banded or global
+alignment, a ``device="cpu"`` path, and any z-score or normalisation of the scores.  Measured
+cost: DESIGN.md §4.
 """
 from __future__ import annotations
 
 import math
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -69,8 +92,8 @@ from .distance import _checked, _prepare, _record_ptr
 
 
 class AlignWorkspace:
-    """Scratch memory of ``local_align`` and ``local_spans`` kept across calls, as
-    ``distance.RecordWorkspace`` keeps that of ``record_scores`` (the results are always new
+    """Scratch memory of ``local_align``, ``local_spans`` and ``local_paths`` kept across calls,
+    as ``distance.RecordWorkspace`` keeps that of ``record_scores`` (the results are always new
     tensors)."""
 
     def __init__(self) -> None:
@@ -116,11 +139,32 @@ def _checked_parameter(value, name: str) -> float:
     return value
 
 
+class _Call(NamedTuple):
+    """A checked call: the rows on the device, the records and pairs on both sides."""
+    a: torch.Tensor
+    b: torch.Tensor
+    ptr_a: np.ndarray
+    ptr_b: np.ndarray
+    pairs: np.ndarray
+    rows_b: np.ndarray
+    parameters: tuple          # match_scale, match_shift, gap_open, gap_extend
+    ptr_a_dev: torch.Tensor | None = None
+    ptr_b_dev: torch.Tensor | None = None
+    pairs_dev: torch.Tensor | None = None
+
+    def arguments(self) -> tuple:
+        """What every alignment call of the C ABI starts with."""
+        return (self.a.data_ptr(), self.a.shape[0], self.ptr_a_dev.data_ptr(), self.ptr_a.size - 1,
+                self.b.data_ptr(), self.b.shape[0], self.ptr_b_dev.data_ptr(), self.ptr_b.size - 1,
+                self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters)
+
+
 def _align(span: bool, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
            match_shift, workspace):
     """The checks and the one launch behind ``local_align`` (``span`` False: scores, ends) and
     ``local_spans`` (True: scores, starts, ends).  Every argument error is raised before a device
-    is touched."""
+    is touched.  The fourth result is the checked call with its device arrays, for
+    ``local_paths`` (None where nothing was launched)."""
     gap_open = _checked_parameter(gap_open, "gap_open")
     gap_extend = _checked_parameter(gap_extend, "gap_extend")
     match_scale = _checked_parameter(match_scale, "match_scale")
@@ -153,23 +197,23 @@ def _align(span: bool, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, ma
         ends = torch.full((count, 2), -1, dtype=torch.int32, device=a.device)
         starts = torch.full((count, 2), -1, dtype=torch.int32, device=a.device) if span else None
         if count == 0 or n == 0 or m == 0:   # no pair, or no pair with a row on both sides
-            return scores, starts, ends
+            return scores, starts, ends, None
         lib = native.library()
         name = "gfy_align_local_span" if span else "gfy_align_local"
         sizer = lib.gfy_align_span_workspace_bytes if span else lib.gfy_align_workspace_bytes
         need = sizer(count, int(rows_b.max()))
         scratch = (workspace or AlignWorkspace()).buffer(a.device, need)
-        ptr_a_dev = torch.from_numpy(ptr_a.astype(np.int32)).to(a.device)
-        ptr_b_dev = torch.from_numpy(ptr_b.astype(np.int32)).to(a.device)
-        pairs_dev = torch.from_numpy(pairs).to(a.device)
+        call = _Call(a, b, ptr_a, ptr_b, pairs, rows_b,
+                     (match_scale, match_shift, gap_open, gap_extend),
+                     torch.from_numpy(ptr_a.astype(np.int32)).to(a.device),
+                     torch.from_numpy(ptr_b.astype(np.int32)).to(a.device),
+                     torch.from_numpy(pairs).to(a.device))
         outputs = (scores.data_ptr(), starts.data_ptr(), ends.data_ptr()) if span else \
             (scores.data_ptr(), ends.data_ptr())
         native.check(getattr(lib, name)(
-            a.data_ptr(), n, ptr_a_dev.data_ptr(), ptr_a.size - 1, b.data_ptr(), m,
-            ptr_b_dev.data_ptr(), ptr_b.size - 1, pairs_dev.data_ptr(), count, match_scale,
-            match_shift, gap_open, gap_extend, *outputs, scratch.data_ptr(), scratch.numel(),
+            *call.arguments(), *outputs, scratch.data_ptr(), scratch.numel(),
             torch.cuda.current_stream(a.device).cuda_stream), name)
-    return scores, starts, ends
+    return scores, starts, ends, call
 
 
 def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -192,8 +236,8 @@ def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     Every argument error is a ``ValueError`` before a device is touched: a pair out of range, a
     record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
     finite or out of order.  ``P == 0`` returns empty tensors without a launch."""
-    scores, _, ends = _align(False, a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                             match_scale, match_shift, workspace)
+    scores, _, ends, _ = _align(False, a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                match_scale, match_shift, workspace)
     return scores, ends
 
 
@@ -209,7 +253,101 @@ def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     The arguments, their checks and the ``ValueError``s are those of ``local_align``; an
     ``AlignWorkspace`` serves both functions (this one needs twice the bytes)."""
     return _align(True, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-                  match_shift, workspace)
+                  match_shift, workspace)[:3]
+
+
+class AlignedPaths(NamedTuple):
+    """What ``local_paths`` returns, all on the device: pair p's path is
+    ``ops[offsets[p]:offsets[p + 1]]``."""
+    scores: torch.Tensor    # float32 [P]
+    starts: torch.Tensor    # int32 [P, 2]
+    ends: torch.Tensor      # int32 [P, 2]
+    ops: torch.Tensor       # uint8 [offsets[P]]: 0 match, 1 gap facing a row of b, 2 facing one of a
+    offsets: torch.Tensor   # int64 [P + 1]
+
+
+def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None,
+                max_workspace_bytes: int = 2 << 30) -> AlignedPaths:
+    """``local_spans`` with the aligned path of every pair: ``AlignedPaths(scores, starts, ends,
+    ops, offsets)`` on the device.  ``ops`` (uint8, all pairs one after the other) holds each
+    path in forward order, ``start`` to ``end``: ``0`` a row of the a-record matched with a row of
+    the b-record, ``1`` a row of the b-record facing a gap, ``2`` a row of the a-record facing a
+    gap (the walk is at the head of this module); ``offsets`` (int64 ``[P + 1]``) says where a
+    pair's ops lie, and ``path_cells`` turns them into row pairs.  Scores, starts and ends are
+    those of ``local_spans`` bit for bit; a score of 0 has an empty path.
+
+    Two launches with a copy to the host between them: the ``local_spans`` launch, then
+    ``starts`` and ``ends`` (``P x 4`` integers) come to the host — which waits for the device —
+    to size each pair's slot and the largest box, then the trace launch on the boxes.  The trace
+    keeps 4 bits per cell of a box per wave in flight (8 MB for a 4096 x 4096 box); it is given
+    ``min(what all waves need, max_workspace_bytes)`` bytes and fewer waves share the work where
+    that is less.  The default, 2 GiB, is a choice: a quarter of what the widest launch needs in
+    the worst case, and still a wave per compute unit.  A ``max_workspace_bytes`` below one wave's
+    need for the largest box of the call is refused by the library (``NativeLibraryError``).
+
+    The other arguments, their checks and the ``ValueError``s are those of ``local_spans``; an
+    ``AlignWorkspace`` serves all three functions.  ``P == 0``, or a call with no rows, returns
+    empty tensors without a launch."""
+    if isinstance(max_workspace_bytes, bool) or \
+            not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 1:
+        raise ValueError("max_workspace_bytes must be a positive integer")
+    scores, starts, ends, call = _align(True, a, b, counts_a, counts_b, pairs, gap_open,
+                                        gap_extend, match_scale, match_shift, workspace)
+    device, count = scores.device, scores.shape[0]
+    with torch.cuda.device(device):
+        box = (ends - starts + 1).cpu().numpy().astype(np.int64)    # waits for the span launch
+        box[starts.cpu().numpy()[:, 0] < 0] = 0                     # nothing aligned: no box
+        slots = np.maximum(box.sum(axis=1) - 1, 0)                  # rows + cols - 1 ops at most
+        slot_ptr = np.concatenate(([0], np.cumsum(slots)))
+        if call is None or slot_ptr[-1] == 0:                       # every path is empty
+            return AlignedPaths(scores, starts, ends,
+                                torch.zeros(0, dtype=torch.uint8, device=device),
+                                torch.zeros(count + 1, dtype=torch.int64, device=device))
+        lib = native.library()
+        box_rows, box_cols = int(box[:, 0].max()), int(box[:, 1].max())
+        need = min(lib.gfy_align_trace_workspace_bytes(count, box_rows, box_cols),
+                   int(max_workspace_bytes))
+        scratch = (workspace or AlignWorkspace()).buffer(device, need)
+        slot_ptr_dev = torch.from_numpy(slot_ptr).to(device)
+        slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
+        lengths = torch.zeros(count, dtype=torch.int32, device=device)
+        native.check(lib.gfy_align_trace(
+            *call.arguments(), starts.data_ptr(), ends.data_ptr(), slot_ptr_dev.data_ptr(),
+            slot_ops.data_ptr(), lengths.data_ptr(), box_rows, box_cols, scratch.data_ptr(), need,
+            torch.cuda.current_stream(device).cuda_stream), "gfy_align_trace")
+        # compaction, not the hot path: the front of every slot, one after the other
+        lengths = lengths.to(torch.int64)
+        if bool((lengths < 0).any()):
+            raise native.NativeLibraryError("gfy_align_trace refused a box of gfy_align_local_span")
+        offsets = torch.cat([lengths.new_zeros(1), torch.cumsum(lengths, 0)])
+        owner = torch.repeat_interleave(torch.arange(count, device=device),
+                                        torch.from_numpy(slots).to(device))
+        within = torch.arange(slot_ops.shape[0], device=device) - slot_ptr_dev[owner]
+        return AlignedPaths(scores, starts, ends, slot_ops[within < lengths[owner]], offsets)
+
+
+def path_cells(ops, start) -> np.ndarray:
+    """The rows a path pairs up: int32 ``[len, 2]`` of (row of the a-record, row of the b-record)
+    for the ops of one pair (``ops[offsets[p]:offsets[p + 1]]`` of ``local_paths``) from its
+    ``start``, with ``-1`` on the gap side (op ``1``: ``(-1, j)``, op ``2``: ``(i, -1)``).  A pure
+    function of its arguments: no device is needed."""
+    if isinstance(ops, torch.Tensor):
+        ops = ops.detach().cpu().numpy()
+    ops = np.asarray(ops)
+    if ops.size == 0 and ops.ndim == 1:
+        return np.zeros((0, 2), dtype=np.int32)
+    if ops.ndim != 1 or ops.dtype.kind not in "iu" or ops.min() < 0 or ops.max() > 2:
+        raise ValueError("ops must be a one-dimensional integer array of 0, 1 and 2")
+    if isinstance(start, torch.Tensor):
+        start = start.detach().cpu().numpy()
+    start = np.asarray(start)
+    if start.shape != (2,) or start.dtype.kind not in "iu" or start.min() < 0:
+        raise ValueError("start must be a cell (i, j) with both coordinates >= 0")
+    in_a, in_b = ops != 1, ops != 2
+    cells = np.stack([np.where(in_a, int(start[0]) - 1 + np.cumsum(in_a), -1),
+                      np.where(in_b, int(start[1]) - 1 + np.cumsum(in_b), -1)], axis=1)
+    return cells.astype(np.int32)
 
 
 def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
@@ -235,4 +373,5 @@ def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
     return np.stack([rows, order.reshape(-1)], axis=1).astype(np.int32)
 
 
-__all__ = ["local_align", "local_spans", "AlignWorkspace", "top_pairs"]
+__all__ = ["local_align", "local_spans", "local_paths", "path_cells", "AlignedPaths",
+           "AlignWorkspace", "top_pairs"]

@@ -1,6 +1,7 @@
 // The one alignment loop of the library (semantics: include/gfy.h), shared by k_align_local
-// (align_local.hip, kSpan = false: score and end) and k_align_span (align_span.hip, kSpan = true:
-// score, start and end), as pairwise_topk.inc is shared by the top-k family.
+// (align_local.hip, kSpan = false: score and end), k_align_span (align_span.hip, kSpan = true:
+// score, start and end) and k_align_trace (align_trace.hip, kTrace = true: the aligned path of a
+// given box), as pairwise_topk.inc is shared by the top-k family.
 //
 // One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
 // wave takes pairs wave, wave + waves of the grid, ... until the list ends.
@@ -29,6 +30,19 @@
 //     butterfly.  An origin is SELECTED where its value is formed, by comparing the very operands
 //     of the max — the max expressions themselves are those of kSpan = false, so scores and ends
 //     are the same bits.  With kSpan = false none of it exists.
+//   * kTrace (without kSpan): the pair's records are replaced by the box start..end the caller
+//     names (a-rows from start_i, b-rows from start_j, lq and lr the box's sizes; read from device
+//     arrays, compared and clipped like the records), and every cell leaves 4 direction bits,
+//     selected like the origins from the operands of the max: which candidate H took (0 starts
+//     here, 1 diagonal continuing, 2 E, 3 F), bit 2 E opened, bit 3 F opened.  A lane packs the 8
+//     consecutive columns of its row into a word and stores it when it fills or the row ends:
+//     [box rows][ceil(box cols / 8)] words, row-major, in the wave's region of the workspace (the
+//     only thing proportional to Lq x Lr the library ever writes, and the box alone).  After the
+//     last strip (behind the fence the carry hand-over uses) the wave walks back from the box's
+//     last cell, uniformly: the 64 lanes load the words of the diagonal behind the current cell
+//     at once, so a run of matches costs one load per 64 ops, a gap position one load each.  The
+//     ops go to the ring (free by then) in reverse, one byte each, and the lanes copy them
+//     forward into the pair's slot.  With kTrace = false none of it exists.
 // ptr_a, ptr_b and pairs are device arrays: they are compared and clipped, a pair outside them or
 // longer than the limits gets NaN and (-2, -2), and nothing outside the caller's buffers is read.
 #pragma once
@@ -68,6 +82,19 @@ struct AlignArgs {
   int cap;                // columns a carry buffer holds
 };
 
+// what k_align_trace takes next to AlignArgs (whose out_score / out_end it leaves alone, and whose
+// carry is the whole workspace: per wave two carry buffers of cap entries, then the region)
+struct TraceArgs {
+  const int32_t* starts;   // [P][2]
+  const int32_t* ends;     // [P][2]
+  const int64_t* op_ptr;   // [P + 1]: pair p owns out_ops[op_ptr[p] .. op_ptr[p + 1])
+  uint8_t* out_ops;
+  int32_t* out_len;        // [P]
+  int64_t waves;           // waves the workspace serves; the others return at once
+  int64_t wave_bytes;      // workspace of one wave
+  int64_t region_words;    // direction words a wave's region holds
+};
+
 // a carry entry: (H, F) of a column, and with kSpan their origins behind them
 template <bool kSpan>
 using AlignCarry = std::conditional_t<kSpan, u32x4, float2>;
@@ -92,9 +119,11 @@ __device__ __forceinline__ void record_rows(const int32_t* ptr, int index, int64
   hi = hi < lo ? lo : hi > rows ? rows : hi;
 }
 
-// out_start ([P][2]) is written with kSpan alone
-template <bool kSpan>
-__device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start) {
+// out_start ([P][2]) is written with kSpan alone, trace is read with kTrace alone
+template <bool kSpan, bool kTrace = false>
+__device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start,
+                                            const TraceArgs* trace = nullptr) {
+  static_assert(!(kSpan && kTrace), "the trace runs on the plain (H, F) carry");
   using Carry = AlignCarry<kSpan>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -105,8 +134,16 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
   float* a_inv = reinterpret_cast<float*>(ring + kRingBytes);   // [kStrip]
   float* b_s = a_inv + kStrip;                                  // [kSub]
   const int64_t slot = (int64_t)blockIdx.x * kAlignWaves + wave;
-  const int64_t slots = (int64_t)gridDim.x * kAlignWaves;
+  int64_t slots = (int64_t)gridDim.x * kAlignWaves;
   Carry* carry = reinterpret_cast<Carry*>(p.carry) + slot * 2 * p.cap;
+  uint32_t* dir = nullptr;   // kTrace: the wave's direction words
+  if constexpr (kTrace) {
+    if (slot >= trace->waves) return;
+    slots = trace->waves;
+    char* mine = reinterpret_cast<char*>(p.carry) + slot * trace->wave_bytes;
+    carry = reinterpret_cast<Carry*>(mine);
+    dir = reinterpret_cast<uint32_t*>(mine + (size_t)2 * p.cap * sizeof(Carry));
+  }
   const float go = p.gap_open, ge = p.gap_extend;
   const float minus_inf = -__builtin_inff();
 
@@ -120,7 +157,29 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       record_rows(p.ptr_b, rec, p.m, b_lo, b_hi);
     }
     ok = ok && a_hi - a_lo <= GFY_ALIGN_ROWS_MAX && b_hi - b_lo <= GFY_ALIGN_ROWS_MAX &&
-         b_hi - b_lo <= p.cap;
+         (kTrace || b_hi - b_lo <= p.cap);
+    int64_t op_lo = 0;   // kTrace: where the pair's slot starts
+    if constexpr (kTrace) {
+      // the box inside the records: only a box that lies in them, fits the wave's region and
+      // whose path fits the slot is followed; (-1, -1) is the empty alignment
+      const int si = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair]);
+      const int sj = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair + 1]);
+      const int ei = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair]);
+      const int ej = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair + 1]);
+      op_lo = trace->op_ptr[pair];
+      const int64_t op_hi = trace->op_ptr[pair + 1];
+      const bool none = si == -1 && sj == -1;
+      bool box = ok && !none && si >= 0 && sj >= 0 && si <= ei && sj <= ej && ei < a_hi - a_lo &&
+                 ej < b_hi - b_lo;
+      const int64_t box_rows = box ? ei - si + 1 : 0, box_cols = box ? ej - sj + 1 : 0;
+      box = box && box_cols <= p.cap && box_rows * ((box_cols + 7) >> 3) <= trace->region_words &&
+            op_lo >= 0 && op_hi - op_lo >= box_rows + box_cols - 1;
+      ok = ok && (none || box);
+      a_lo += box ? si : 0;
+      b_lo += box ? sj : 0;
+      a_hi = a_lo + (box ? box_rows : 0);
+      b_hi = b_lo + (box ? box_cols : 0);
+    }
     const int lq = __builtin_amdgcn_readfirstlane(ok ? (int)(a_hi - a_lo) : 0);
     const int lr = __builtin_amdgcn_readfirstlane(ok ? (int)(b_hi - b_lo) : 0);
     const f16* rows_a = p.a + a_lo * 128;
@@ -129,6 +188,8 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
     float best = 0.f;   // strict >: only a positive cell is ever kept
     int best_i = -1, best_j = -1;
     uint32_t best_o = 0;   // kSpan: the origin of the best cell
+    const int dir_pitch = (lr + 7) >> 3;   // kTrace: words of a row of the box
+    float h_last = 0.f;                    // kTrace: a lane's H when its strip ended
 
     // 32 b-rows from column c0 on as this lane's eight 16-byte pieces: piece lane + 64 x is
     // chunk lane & 15 of row (lane >> 4) + 4 x — a row on 16 consecutive lanes (row_square_sum)
@@ -173,6 +234,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       float h = 0.f, e = minus_inf, f = minus_inf;   // this lane's last cell
       float diag = 0.f;                              // H of the row above, one column back
       uint32_t o_h = 0, o_e = 0, o_f = 0, o_diag = 0;   // kSpan: their origins
+      uint32_t dir_word = 0;                            // kTrace: the row's 8 columns in the making
       f16x8 b_next[8];
       load_b(b_next, 0);
       // the carry entries of the row above the strip for columns c0 + lane, lanes 0..31
@@ -259,6 +321,17 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
             o_h = live ? o_new : o_h;
             o_diag = live ? up_oh : o_diag;
           }
+          if constexpr (kTrace) {
+            // the same selections as kSpan's, kept as bits: diagonal, then E, then F; opening
+            // wins a tie
+            const uint32_t how = h_new == match ? (diag > 0.f ? 1u : 0u) : h_new == e_new ? 2u : 3u;
+            const uint32_t bits = how | (e_open >= e_ext ? 4u : 0u) | (f_open >= f_ext ? 8u : 0u);
+            if (live) {
+              dir_word = (j & 7) == 0 ? bits : dir_word | (bits << (4 * (j & 7)));
+              if ((j & 7) == 7 || j == lr - 1)
+                dir[(size_t)(i0 + lane) * dir_pitch + (j >> 3)] = dir_word;
+            }
+          }
           e = live ? e_new : e;
           f = live ? f_new : f;
           h = live ? h_new : h;
@@ -276,9 +349,59 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           }
         }
       }
-      // the next strip reads what lane 63 stored (and restages the ring)
+      if constexpr (kTrace) h_last = h;
+      // the next strip reads what lane 63 stored (and restages the ring); kTrace: the walk reads
+      // the direction words the lanes stored
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
       wave_sync();
+    }
+
+    if constexpr (kTrace) {
+      int length = 0;
+      // H of the box's last cell is the last H of the lane that owns its row
+      if (strips > 0 && lane_value(h_last, (lq - 1) & (kStrip - 1)) > 0.f) {
+        uint8_t* reversed = reinterpret_cast<uint8_t*>(ring);   // <= 8191 ops of a byte
+        const int limit = lq + lr - 1;
+        int i = lq - 1, j = lr - 1, state = 0;   // 0 in H, 1 in E, 2 in F
+        int anchor_i = -1, anchor_j = -1;        // lane l holds the word of cell anchor - (l, l)
+        uint32_t window = 0;
+        while (length < limit && i >= 0 && j >= 0) {
+          int k = anchor_i - i;
+          if ((uint32_t)k >= 64u || anchor_j - j != k) {
+            anchor_i = i, anchor_j = j, k = 0;
+            const int wi = i - lane, wj = j - lane;
+            window = 0;
+            if (wi >= 0 && wj >= 0)
+              window = __hip_atomic_load(dir + (size_t)wi * dir_pitch + (wj >> 3), __ATOMIC_RELAXED,
+                                         __HIP_MEMORY_SCOPE_WORKGROUP);
+          }
+          const uint32_t bits = ((uint32_t)__builtin_amdgcn_readlane((int)window, k) >> (4 * (j & 7))) & 15u;
+          int op;
+          bool last = false;
+          if (state == 0) {
+            const uint32_t how = bits & 3u;
+            if (how >= 2u) {   // H is E's or F's value: the same cell in that state
+              state = (int)how - 1;
+              continue;
+            }
+            op = 0, last = how == 0u;
+            --i, --j;
+          } else if (state == 1) {
+            op = 1, state = bits & 4u ? 0 : 1;
+            --j;
+          } else {
+            op = 2, state = bits & 8u ? 0 : 2;
+            --i;
+          }
+          if (lane == 0) reversed[length] = (uint8_t)op;
+          ++length;
+          if (last) break;
+        }
+        wave_sync();
+        for (int x = lane; x < length; x += 64) trace->out_ops[op_lo + x] = reversed[length - 1 - x];
+        wave_sync();   // the next pair restages the ring
+      }
+      if (lane == 0) trace->out_len[pair] = ok ? length : -2;
     }
 
 #pragma unroll
@@ -294,7 +417,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       best_i = take ? oi : best_i;
       best_j = take ? oj : best_j;
     }
-    if (lane == 0) {
+    if (!kTrace && lane == 0) {
       const bool none = !(best > 0.f);
       p.out_score[pair] = ok ? (none ? 0.f : best) : __builtin_nanf("");
       p.out_end[2 * pair] = ok ? (none ? -1 : best_i) : -2;

@@ -1149,8 +1149,9 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
                                  out_scores, ws, ws_bytes, (hipStream_t)stream);
 }
 
-// the argument rules gfy_align_local and gfy_align_local_span share; out_start is checked by the
-// span call alone (between out_score and out_end, the order of its arguments)
+// the argument rules gfy_align_local, gfy_align_local_span and gfy_align_trace share; out_start is
+// checked by the span call alone (between out_score and out_end, the order of its arguments), and
+// the trace call passes its out_ops and out_len where the others pass out_score and out_end
 static int check_align_call(const char* who, const void* a, int64_t n, const int32_t* ptr_a,
                             int64_t records_a, const void* b, int64_t m, const int32_t* ptr_b,
                             int64_t records_b, const int32_t* pairs, int64_t P, float match_scale,
@@ -1223,6 +1224,39 @@ int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t
   return launch_align_local_span(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P,
                                  match_scale, match_shift, gap_open, gap_extend, out_score,
                                  out_start, out_end, ws, ws_bytes, (hipStream_t)stream);
+}
+
+size_t gfy_align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols) {
+  return align_trace_workspace_bytes(pairs < 1 ? 1 : pairs, clipped_align_rows(max_box_rows),
+                                     clipped_align_rows(max_box_cols));
+}
+
+int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                    const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                    const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                    float gap_open, float gap_extend, const int32_t* starts, const int32_t* ends,
+                    const int64_t* op_ptr, uint8_t* out_ops, int32_t* out_len,
+                    int64_t max_box_rows, int64_t max_box_cols, void* ws, size_t ws_bytes,
+                    void* stream) {
+  clear_error();
+  GFY_REQUIRE(starts, GFY_ERR_INVALID, "gfy_align_trace: starts is NULL");
+  GFY_REQUIRE(ends, GFY_ERR_INVALID, "gfy_align_trace: ends is NULL");
+  GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_trace: op_ptr is NULL");
+  GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_trace: out_ops is NULL");
+  GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_trace: out_len is NULL");
+  // out_ops and out_len are named above: the shared check sees them as given
+  if (const int rc = check_align_call("gfy_align_trace", a, n, ptr_a, records_a, b, m, ptr_b,
+                                      records_b, pairs, P, match_scale, match_shift, gap_open,
+                                      gap_extend, reinterpret_cast<const float*>(out_ops), nullptr,
+                                      false, out_len, ws))
+    return rc;
+  GFY_REQUIRE(max_box_rows >= 0 && max_box_cols >= 0, GFY_ERR_INVALID,
+              "gfy_align_trace: max_box_rows = %lld, max_box_cols = %lld are negative",
+              (long long)max_box_rows, (long long)max_box_cols);
+  return launch_align_trace(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale,
+                            match_shift, gap_open, gap_extend, starts, ends, op_ptr, out_ops,
+                            out_len, clipped_align_rows(max_box_rows),
+                            clipped_align_rows(max_box_cols), ws, ws_bytes, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -390,6 +390,15 @@ int launch_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int6
                             int32_t* out_start, int32_t* out_end, void* ws, size_t ws_bytes,
                             hipStream_t s);
 size_t align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
+// align_trace.hip: the aligned path of the box start..end of every pair
+int launch_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                       const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                       const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                       float gap_open, float gap_extend, const int32_t* starts,
+                       const int32_t* ends, const int64_t* op_ptr, uint8_t* out_ops,
+                       int32_t* out_len, int64_t max_box_rows, int64_t max_box_cols, void* ws,
+                       size_t ws_bytes, hipStream_t s);
+size_t align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS

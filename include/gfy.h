@@ -611,8 +611,8 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
  *               keeps no promise of its sign.
  *   Limits      a record has at most GFY_ALIGN_ROWS_MAX rows; 0 <= gap_extend <= gap_open, the
  *               four parameters finite; 1 <= P < 2^31.  Rows holding inf / NaN give unspecified
- *               values.  No traceback (gfy_align_local_span gives the start cell), no banded or
- *               global alignment, no normalisation of scores.
+ *               values.  The start cell is gfy_align_local_span's and the aligned path
+ *               gfy_align_trace's; no banded or global alignment, no normalisation of scores.
  *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), max_rows_b the longest b-record any
  *               pair names: the last row of a 64-row strip of A, per wave in flight.
  *   ptr_a, ptr_b and pairs are device arrays, which the kernel only compares and clips.  A pair
@@ -656,13 +656,14 @@ int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
  *   It follows  start <= end in both coordinates; s[start] == H[start] > 0; and the same
  *               recurrences run on the box start..end alone reach, at the box's last cell,
  *               exactly out_score, bit for bit (rounded addition and max are monotone and the
- *               path's own operations are unchanged).  A later traceback only has to revisit
+ *               path's own operations are unchanged).  gfy_align_trace only has to revisit
  *               that box.
  *   Workspace   gfy_align_span_workspace_bytes(pairs, max_rows_b): a strip's last row carries
  *               (H, F, origin of H, origin of F), 16 bytes per column, twice gfy_align_local's.
  *   Arguments, clipping of what the device arrays hold and error codes are those of
  *   gfy_align_local; a NULL out_start is GFY_ERR_INVALID and named.
- *   No traceback, no banded or global alignment, no normalisation of scores.                  */
+ *   The aligned path itself is gfy_align_trace's; no banded or global alignment, no
+ *   normalisation of scores.                                                                  */
 size_t gfy_align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
 int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
@@ -671,6 +672,74 @@ int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t
                          float* out_score /* [P] */, int32_t* out_start /* [P][2] */,
                          int32_t* out_end /* [P][2] */,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* The aligned PATH of every pair: the walk back from out_end by the origin rules of
+ * gfy_align_local_span, nothing new.  starts and ends (int32 [P][2], device memory) are what that
+ * call returned for the same a, b, pairs and parameters.
+ *   Walk        a state is H, E or F at a cell; the walk starts in H at end.
+ *               H at (i, j)  if H == H[i-1][j-1] + s[i][j]: op 0 (row i of A matched with row j of
+ *                            B); then, if H[i-1][j-1] > 0, on in H at (i-1, j-1), else stop (this
+ *                            cell is start).  Else if H == E[i][j]: E at the same cell.  Else F at
+ *                            the same cell.
+ *               E at (i, j)  op 1 (row j of B faces a gap); on at (i, j-1), in H if H[i][j-1] -
+ *                            gap_open >= E[i][j-1] - gap_extend (opening wins a tie), else in E.
+ *               F at (i, j)  op 2 (row i of A faces a gap); on at (i-1, j) by the same rule with
+ *                            the row above.
+ *   Result      out_ops[op_ptr[p] ..]: the ops in FORWARD order, start to end, out_len[p] of them,
+ *               one byte each.  The first and the last op are 0; the ops 0 and 2 number end_i -
+ *               start_i + 1, the ops 0 and 1 end_j - start_j + 1; out_len <= rows + cols - 1 of
+ *               the box.  A start of (-1, -1) (a score of 0) has out_len = 0.  Re-scoring the ops
+ *               (h = 0; op 0: h = fl32(h + s[i][j]); the first op of a run of equal gap ops: g =
+ *               fl32(h - gap_open), each further one g = fl32(g - gap_extend); after the run h =
+ *               g) gives out_score bit for bit: a run that re-opens inside needs gap_open ==
+ *               gap_extend, and then both readings round alike.
+ *   The box     the kernel runs the recurrences on the box start..end ALONE (a-rows from start_i,
+ *               b-rows from start_j), keeps 4 direction bits per cell and walks them.  That walk
+ *               equals the walk on the full matrix.  By induction from start along the chosen
+ *               path, every cell ON the path has the same H, E or F in both: its value is that
+ *               of a candidate whose predecessor lies on the path and is equal by hypothesis (for
+ *               start itself the predecessor is the 0 outside the box); every other candidate is
+ *               formed in the box from values that are <= the full matrix's (rounded + and max
+ *               are monotone, and what the box lacks counts as 0 or -inf, never more than what
+ *               the matrix holds there), so it can only become smaller and the maximum stays.
+ *               Every tie rule prefers the candidate on the path: a candidate that lost to it in
+ *               the full matrix, strictly or by the rule, still loses when it shrinks.  So every
+ *               direction bit the walk reads is the same, and so are the ops.
+ *   The call also serves any box inside the two records: its result is then the walk of the
+ *   recurrences on that box from the box's last cell (out_len = 0 where H there is not > 0).
+ *   The walk emits at most rows + cols - 1 ops and stops on leaving the box.
+ *   Slots       op_ptr int64 [P + 1], device memory: pair p owns out_ops[op_ptr[p] ..
+ *               op_ptr[p + 1]), at least rows + cols - 1 bytes of it; the ops fill its front, the
+ *               rest is left as it was.
+ *   Workspace   gfy_align_trace_workspace_bytes(pairs, max_box_rows, max_box_cols): per wave of
+ *               the full grid two carry buffers of max_box_cols entries and a region of max_box_rows
+ *               x ceil(max_box_cols / 8) direction words (8 MB at 4096 x 4096) — the first thing
+ *               proportional to L_q x L_r this library writes, for the box only.  The call takes
+ *               the same max_box_rows and max_box_cols (they say how the workspace is cut; they
+ *               come from starts and ends, which the caller has to read back to size the slots
+ *               anyway).  Any workspace that holds one wave's part is accepted: as many waves as
+ *               fit are used and take the pairs in turn, the others return at once.  A smaller
+ *               one is GFY_ERR_WORKSPACE.
+ *   Refused     out_len[p] = -2 and nothing written to the slot: a record index out of range or a
+ *               record longer than GFY_ALIGN_ROWS_MAX (as gfy_align_local), a box not inside its
+ *               records (start > end, end past the record, a negative start other than (-1, -1)),
+ *               a box of more columns than max_box_cols or of more direction words than a wave's
+ *               region, a slot shorter than rows + cols - 1.  starts, ends and the records are
+ *               compared and clipped, never followed unchecked.
+ *   Arguments and error codes are those of gfy_align_local, with out_ops and out_len in place of
+ *   out_score and out_end; NULL starts, ends, op_ptr, out_ops or out_len is GFY_ERR_INVALID and
+ *   named, and so is a negative max_box_rows or max_box_cols; all before any launch and without a
+ *   device.
+ *   Cost: DESIGN.md §4.                                                                       */
+size_t gfy_align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols);
+int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                    const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                    const int32_t* pairs /* [P][2] device */, int64_t P,
+                    float match_scale, float match_shift, float gap_open, float gap_extend,
+                    const int32_t* starts /* [P][2] */, const int32_t* ends /* [P][2] */,
+                    const int64_t* op_ptr /* [P + 1] */, uint8_t* out_ops, int32_t* out_len /* [P] */,
+                    int64_t max_box_rows, int64_t max_box_cols,
+                    void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,8 +16,17 @@ run, on the same pairs and with the same warm-up and repeats, and adds ``spans_s
 ``spans_cell_updates_per_s``, ``spans_over_local_align`` (the ratio of the two medians) and the
 SHA-256 of the span kernel's sources; without the flag nothing changes.
 
+``--paths`` times ``align.local_paths`` (score, start, end and the aligned path: the span launch,
+the copy of starts and ends to the host, the trace launch on the boxes and the compaction) next
+to ``align.local_spans`` on the same pairs, and adds ``paths`` to the document: both medians,
+their ratio, the ops and the box cells of the run.  Random records share nothing, so their
+alignments are a few cells long and the trace has next to nothing to do; the same two calls
+are therefore timed a second time on every record paired with ITSELF (``paths_self``), where the
+box is the whole matrix and the path its whole diagonal: the most a trace can be asked for.
+
     python tools/bench_align.py --pairs 20000
     python tools/bench_align.py --pairs 20000 --spans
+    python tools/bench_align.py --pairs 20000 --paths
 """
 from __future__ import annotations
 
@@ -41,6 +50,7 @@ from ginfinity_amd import align, distance, synthetic  # noqa: E402
 
 KERNEL_SOURCE = "align_local.hip"
 SPAN_SOURCES = ("align_local.inc", "align_span.hip")     # --spans: the shared body and its kernel
+PATH_SOURCES = ("align_local.inc", "align_span.hip", "align_trace.hip")   # --paths
 
 
 def _commit() -> str | None:
@@ -72,6 +82,27 @@ def _span(seconds: list[float]) -> dict:
             "runs": seconds}
 
 
+def _paths_against_spans(rows, counts, pairs, keeper, parameters, repeats, warmup) -> dict:
+    """``local_spans`` and ``local_paths`` on the same pairs, one after the other."""
+    pairs_dev = torch.from_numpy(pairs)
+    spans = _timed(lambda: align.local_spans(rows, counts_a=counts, pairs=pairs_dev,
+                                             workspace=keeper, **parameters), repeats, warmup)
+    paths = _timed(lambda: align.local_paths(rows, counts_a=counts, pairs=pairs_dev,
+                                             workspace=keeper, **parameters), repeats, warmup)
+    result = align.local_paths(rows, counts_a=counts, pairs=pairs_dev, workspace=keeper,
+                               **parameters)
+    box = (result.ends - result.starts + 1).cpu().numpy().astype(np.int64)
+    box[result.starts.cpu().numpy()[:, 0] < 0] = 0
+    span_mid, path_mid = statistics.median(spans), statistics.median(paths)
+    return {"pairs": int(pairs.shape[0]),
+            "cells": int((counts[pairs[:, 0]].astype(np.int64) * counts[pairs[:, 1]]).sum()),
+            "box_cells": int((box[:, 0] * box[:, 1]).sum()), "ops": int(result.ops.shape[0]),
+            "spans_seconds": _span(spans), "paths_seconds": _span(paths),
+            "paths_over_local_spans": path_mid / span_mid,
+            "timed": "local_paths whole: the span launch, starts and ends to the host, the trace "
+                     "launch, the compaction"}
+
+
 def _host_gotoh(S: np.ndarray, go: np.float32, ge: np.float32) -> np.float32:
     """max H of the recurrences in numpy float32, one anti-diagonal at a time."""
     lq, lr = S.shape
@@ -99,6 +130,9 @@ def main() -> None:
                         help="pairs of the host numpy DP timed for scale (0: none)")
     parser.add_argument("--spans", action="store_true",
                         help="time align.local_spans as well, after local_align")
+    parser.add_argument("--paths", action="store_true",
+                        help="time align.local_paths next to align.local_spans, on the pairs and "
+                             "on every record with itself")
     parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
     parser.add_argument("--out", default=str(ROOT / "profiles" / "align_bench.json"))
     args = parser.parse_args()
@@ -146,6 +180,21 @@ def main() -> None:
             for name in SPAN_SOURCES}
         print(f"local_spans: {span_mid:.4f} s = {cells / span_mid:.3e} cell updates/s, "
               f"{span_mid / mid:.3f} x local_align", file=sys.stderr, flush=True)
+    if args.paths:
+        result["paths"] = _paths_against_spans(rows, counts, pairs, keeper, parameters,
+                                               args.repeats, args.warmup)
+        own = np.repeat(np.arange(args.records, dtype=np.int32)[:, None], 2, axis=1)
+        result["paths_self"] = _paths_against_spans(rows, counts, own, keeper, parameters,
+                                                    args.repeats, args.warmup)
+        result["paths_source_sha256"] = {
+            name: hashlib.sha256((source.parent / name).read_bytes()).hexdigest()
+            for name in PATH_SOURCES}
+        for name in ("paths", "paths_self"):
+            part = result[name]
+            print(f"{name}: local_spans {part['spans_seconds']['median']:.4f} s, local_paths "
+                  f"{part['paths_seconds']['median']:.4f} s = {part['paths_over_local_spans']:.3f} x, "
+                  f"{part['ops']} ops, {part['box_cells']} box cells of {part['cells']}",
+                  file=sys.stderr, flush=True)
     if args.host_pairs > 0:
         some = pairs[:args.host_pairs]
         host_seconds, host_cells = 0.0, 0
