@@ -44,6 +44,10 @@ class GfyShard(Structure):
                 ("node_ptr", c_void_p), ("edge_ptr", c_void_p), ("n_records", c_int64)]
 
 
+#: what every alignment call starts with: a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P,
+#: match_scale, match_shift, gap_open, gap_extend
+_ALIGN_CALL = [c_void_p, c_int64] * 5 + [c_float] * 4
+
 #: every symbol include/gfy.h declares: (restype, argtypes)
 SIGNATURES: dict[str, tuple] = {
     "gfy_last_error": (c_char_p, []),
@@ -132,19 +136,13 @@ SIGNATURES: dict[str, tuple] = {
                                            c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                            c_size_t, c_void_p]),
     "gfy_align_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "gfy_align_local": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_float,
-                                c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "gfy_align_local": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gfy_align_span_workspace_bytes": (c_size_t, [c_int64, c_int64]),
-    "gfy_align_local_span": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
-                                     c_void_p, c_int64, c_void_p, c_int64, c_float, c_float,
-                                     c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+    "gfy_align_local_span": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_size_t, c_void_p]),
     "gfy_align_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
-    "gfy_align_trace": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
-                                c_int64, c_void_p, c_int64, c_float, c_float, c_float, c_float,
-                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
-                                c_void_p, c_size_t, c_void_p]),
+    "gfy_align_trace": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
 }
 
 

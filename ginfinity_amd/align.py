@@ -88,7 +88,7 @@ import numpy as np
 import torch
 
 from . import _native as native
-from .distance import _checked, _prepare, _record_ptr
+from .distance import _checked, _grown, _prepare, _record_ptr
 
 
 class AlignWorkspace:
@@ -100,9 +100,7 @@ class AlignWorkspace:
         self.scratch: torch.Tensor | None = None
 
     def buffer(self, device, scratch_bytes: int) -> torch.Tensor:
-        if self.scratch is None or self.scratch.numel() < scratch_bytes or \
-                self.scratch.device != device:
-            self.scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=device)
+        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
         return self.scratch
 
 
@@ -140,7 +138,8 @@ def _checked_parameter(value, name: str) -> float:
 
 
 class _Call(NamedTuple):
-    """A checked call: the rows on the device, the records and pairs on both sides."""
+    """A checked call: the rows (``b`` is ``a`` where it was omitted), the records and pairs on
+    both sides; ``on_device`` adds the device arrays."""
     a: torch.Tensor
     b: torch.Tensor
     ptr_a: np.ndarray
@@ -152,6 +151,23 @@ class _Call(NamedTuple):
     ptr_b_dev: torch.Tensor | None = None
     pairs_dev: torch.Tensor | None = None
 
+    @property
+    def empty(self) -> bool:
+        """No pair, or no pair with a row on both sides: nothing is launched."""
+        return self.pairs.shape[0] == 0 or self.a.shape[0] == 0 or self.b.shape[0] == 0
+
+    def on_device(self) -> "_Call":
+        """The call with its rows on the device and, unless it is empty, its arrays next to
+        them."""
+        a = _prepare(self.a, None)
+        b = a if self.b is self.a else _prepare(self.b, a.device)
+        if self.empty:
+            return self._replace(a=a, b=b)
+        return self._replace(a=a, b=b,
+                             ptr_a_dev=torch.from_numpy(self.ptr_a.astype(np.int32)).to(a.device),
+                             ptr_b_dev=torch.from_numpy(self.ptr_b.astype(np.int32)).to(a.device),
+                             pairs_dev=torch.from_numpy(self.pairs).to(a.device))
+
     def arguments(self) -> tuple:
         """What every alignment call of the C ABI starts with."""
         return (self.a.data_ptr(), self.a.shape[0], self.ptr_a_dev.data_ptr(), self.ptr_a.size - 1,
@@ -159,12 +175,10 @@ class _Call(NamedTuple):
                 self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters)
 
 
-def _align(span: bool, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-           match_shift, workspace):
-    """The checks and the one launch behind ``local_align`` (``span`` False: scores, ends) and
-    ``local_spans`` (True: scores, starts, ends).  Every argument error is raised before a device
-    is touched.  The fourth result is the checked call with its device arrays, for
-    ``local_paths`` (None where nothing was launched)."""
+def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
+                  match_shift) -> _Call:
+    """Every check of ``local_align``, ``local_spans`` and ``local_paths``: the call, or the
+    ``ValueError``.  No device is touched."""
     gap_open = _checked_parameter(gap_open, "gap_open")
     gap_extend = _checked_parameter(gap_extend, "gap_extend")
     match_scale = _checked_parameter(match_scale, "match_scale")
@@ -173,14 +187,13 @@ def _align(span: bool, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, ma
         raise ValueError("0 <= gap_extend <= gap_open is required")
     a = _checked(a)
     if b is None:
-        counts_b = counts_a if counts_b is None else counts_b
+        b, counts_b = a, counts_a if counts_b is None else counts_b
     else:
         b = _checked(b)
         if counts_b is None:
             raise ValueError("counts_b is required with b: record counts of b's rows")
-    n, m = a.shape[0], a.shape[0] if b is None else b.shape[0]
-    ptr_a = _record_ptr(counts_a, n, "counts_a", "a")
-    ptr_b = _record_ptr(counts_b, m, "counts_b", "b")
+    ptr_a = _record_ptr(counts_a, a.shape[0], "counts_a", "a")
+    ptr_b = _record_ptr(counts_b, b.shape[0], "counts_b", "b")
     pairs = _checked_pairs(pairs, ptr_a.size - 1, ptr_b.size - 1)
     rows_a = np.diff(ptr_a)[pairs[:, 0]]
     rows_b = np.diff(ptr_b)[pairs[:, 1]]
@@ -189,31 +202,30 @@ def _align(span: bool, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, ma
             bad = int(np.argmax(rows > native.GFY_ALIGN_ROWS_MAX))
             raise ValueError(f"pair {bad}: record {int(pairs[bad, column])} of {side} has "
                              f"{int(rows[bad])} rows, more than {native.GFY_ALIGN_ROWS_MAX}")
-    count = pairs.shape[0]
-    a = _prepare(a, None)
-    b = a if b is None else _prepare(b, a.device)
-    with torch.cuda.device(a.device):
-        scores = torch.zeros(count, dtype=torch.float32, device=a.device)
-        ends = torch.full((count, 2), -1, dtype=torch.int32, device=a.device)
-        starts = torch.full((count, 2), -1, dtype=torch.int32, device=a.device) if span else None
-        if count == 0 or n == 0 or m == 0:   # no pair, or no pair with a row on both sides
-            return scores, starts, ends, None
-        lib = native.library()
-        name = "gfy_align_local_span" if span else "gfy_align_local"
-        sizer = lib.gfy_align_span_workspace_bytes if span else lib.gfy_align_workspace_bytes
-        need = sizer(count, int(rows_b.max()))
-        scratch = (workspace or AlignWorkspace()).buffer(a.device, need)
-        call = _Call(a, b, ptr_a, ptr_b, pairs, rows_b,
-                     (match_scale, match_shift, gap_open, gap_extend),
-                     torch.from_numpy(ptr_a.astype(np.int32)).to(a.device),
-                     torch.from_numpy(ptr_b.astype(np.int32)).to(a.device),
-                     torch.from_numpy(pairs).to(a.device))
-        outputs = (scores.data_ptr(), starts.data_ptr(), ends.data_ptr()) if span else \
-            (scores.data_ptr(), ends.data_ptr())
-        native.check(getattr(lib, name)(
-            *call.arguments(), *outputs, scratch.data_ptr(), scratch.numel(),
-            torch.cuda.current_stream(a.device).cuda_stream), name)
-    return scores, starts, ends, call
+    return _Call(a, b, ptr_a, ptr_b, pairs, rows_b,
+                 (match_scale, match_shift, gap_open, gap_extend))
+
+
+def _launch(call: _Call, span: bool, workspace) -> tuple:
+    """The one launch behind ``local_align`` (``span`` False: ``(scores, ends)``) and
+    ``local_spans`` (True: ``(scores, starts, ends)``) of a call that is ``on_device``; an
+    empty call gives its results without one."""
+    device, count = call.a.device, call.pairs.shape[0]
+    with torch.cuda.device(device):
+        scores = torch.zeros(count, dtype=torch.float32, device=device)
+        ends = torch.full((count, 2), -1, dtype=torch.int32, device=device)
+        starts = torch.full((count, 2), -1, dtype=torch.int32, device=device) if span else None
+        outputs = (scores, starts, ends) if span else (scores, ends)
+        if not call.empty:
+            lib = native.library()
+            name = "gfy_align_local_span" if span else "gfy_align_local"
+            sizer = lib.gfy_align_span_workspace_bytes if span else lib.gfy_align_workspace_bytes
+            need = sizer(count, int(call.rows_b.max()))
+            scratch = (workspace or AlignWorkspace()).buffer(device, need)
+            native.check(getattr(lib, name)(
+                *call.arguments(), *(out.data_ptr() for out in outputs), scratch.data_ptr(),
+                scratch.numel(), torch.cuda.current_stream(device).cuda_stream), name)
+    return outputs
 
 
 def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -236,9 +248,8 @@ def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     Every argument error is a ``ValueError`` before a device is touched: a pair out of range, a
     record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
     finite or out of order.  ``P == 0`` returns empty tensors without a launch."""
-    scores, _, ends, _ = _align(False, a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                match_scale, match_shift, workspace)
-    return scores, ends
+    return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                 match_scale, match_shift).on_device(), False, workspace)
 
 
 def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -252,8 +263,8 @@ def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
 
     The arguments, their checks and the ``ValueError``s are those of ``local_align``; an
     ``AlignWorkspace`` serves both functions (this one needs twice the bytes)."""
-    return _align(True, a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-                  match_shift, workspace)[:3]
+    return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                 match_scale, match_shift).on_device(), True, workspace)
 
 
 class AlignedPaths(NamedTuple):
@@ -292,15 +303,16 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     if isinstance(max_workspace_bytes, bool) or \
             not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 1:
         raise ValueError("max_workspace_bytes must be a positive integer")
-    scores, starts, ends, call = _align(True, a, b, counts_a, counts_b, pairs, gap_open,
-                                        gap_extend, match_scale, match_shift, workspace)
+    call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
+                         match_shift).on_device()
+    scores, starts, ends = _launch(call, True, workspace)
     device, count = scores.device, scores.shape[0]
     with torch.cuda.device(device):
         box = (ends - starts + 1).cpu().numpy().astype(np.int64)    # waits for the span launch
         box[starts.cpu().numpy()[:, 0] < 0] = 0                     # nothing aligned: no box
         slots = np.maximum(box.sum(axis=1) - 1, 0)                  # rows + cols - 1 ops at most
         slot_ptr = np.concatenate(([0], np.cumsum(slots)))
-        if call is None or slot_ptr[-1] == 0:                       # every path is empty
+        if call.empty or slot_ptr[-1] == 0:                         # every path is empty
             return AlignedPaths(scores, starts, ends,
                                 torch.zeros(0, dtype=torch.uint8, device=device),
                                 torch.zeros(count + 1, dtype=torch.int64, device=device))

@@ -21,17 +21,10 @@ size_t align_workspace_bytes(int64_t pairs, int64_t max_rows_b) {
   return align_carry_bytes<false>(pairs, max_rows_b);
 }
 
-int launch_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
-                       const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
-                       const int32_t* pairs, int64_t P, float match_scale, float match_shift,
-                       float gap_open, float gap_extend, float* out_score, int32_t* out_end,
-                       void* ws, size_t ws_bytes, hipStream_t s) {
-  return align_launch<false>(
-      "gfy_align_local", reinterpret_cast<const void*>(k_align_local), a, n, ptr_a, records_a, b,
-      m, ptr_b, records_b, pairs, P, match_scale, match_shift, gap_open, gap_extend, out_score,
-      out_end, ws, ws_bytes, [s](int groups, const AlignArgs& p) {
-        k_align_local<<<groups, kAlignThreads, kAlignLds, s>>>(p);
-      });
+int launch_align_local(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s) {
+  AlignArgs p = call;
+  if (const int rc = align_take_carry<false>("gfy_align_local", &p, ws, ws_bytes)) return rc;
+  return align_launch<k_align_local>(p, align_groups(p.P), s);
 }
 
 }  // namespace gfy

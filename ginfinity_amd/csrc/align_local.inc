@@ -67,33 +67,7 @@ static_assert(kRingBytes == kBuffers * (kSub * 256), "a quarter of the ring stag
 static_assert(kAlignLds <= 160 * 1024, "the LDS of a compute unit");
 static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an origin fit its word");
 
-struct AlignArgs {
-  const f16* a;
-  const f16* b;
-  const int32_t* ptr_a;
-  const int32_t* ptr_b;
-  const int32_t* pairs;   // [P][2]
-  int64_t n, m, P;
-  int records_a, records_b;
-  float match_scale, match_shift, gap_open, gap_extend;
-  float* out_score;       // [P]
-  int32_t* out_end;       // [P][2]
-  void* carry;            // [waves of the grid][2][cap] entries of a strip's last row
-  int cap;                // columns a carry buffer holds
-};
-
-// what k_align_trace takes next to AlignArgs (whose out_score / out_end it leaves alone, and whose
-// carry is the whole workspace: per wave two carry buffers of cap entries, then the region)
-struct TraceArgs {
-  const int32_t* starts;   // [P][2]
-  const int32_t* ends;     // [P][2]
-  const int64_t* op_ptr;   // [P + 1]: pair p owns out_ops[op_ptr[p] .. op_ptr[p + 1])
-  uint8_t* out_ops;
-  int32_t* out_len;        // [P]
-  int64_t waves;           // waves the workspace serves; the others return at once
-  int64_t wave_bytes;      // workspace of one wave
-  int64_t region_words;    // direction words a wave's region holds
-};
+// (AlignArgs and TraceArgs, the kernels' arguments: gfy_common.h)
 
 // a carry entry: (H, F) of a column, and with kSpan their origins behind them
 template <bool kSpan>
@@ -442,46 +416,32 @@ size_t align_carry_bytes(int64_t pairs, int64_t max_rows_b) {
   return align_up(waves * 2 * (size_t)max_rows_b * sizeof(AlignCarry<kSpan>) + 1, 256);
 }
 
-// the launch both kernels share: the workspace check, the LDS opt-in (once per device and
-// kernel) and the arguments; `launch(groups, p)` starts the kernel
-template <bool kSpan, typename Launch>
-int align_launch(const char* who, const void* kernel, const void* a, int64_t n,
-                 const int32_t* ptr_a, int64_t records_a, const void* b, int64_t m,
-                 const int32_t* ptr_b, int64_t records_b, const int32_t* pairs, int64_t P,
-                 float match_scale, float match_shift, float gap_open, float gap_extend,
-                 float* out_score, int32_t* out_end, void* ws, size_t ws_bytes, Launch&& launch) {
-  GFY_REQUIRE(ws_bytes >= align_carry_bytes<kSpan>(P, 0), GFY_ERR_WORKSPACE,
-              "%s: workspace %zu < required %zu", who, ws_bytes, align_carry_bytes<kSpan>(P, 0));
-  const int groups = align_groups(P);
+// the carry of a score or span call in the caller's workspace: the check, then `carry` and `cap`
+// of `p`, the launcher's copy of the call
+template <bool kSpan>
+int align_take_carry(const char* who, AlignArgs* p, void* ws, size_t ws_bytes) {
+  GFY_REQUIRE(ws_bytes >= align_carry_bytes<kSpan>(p->P, 0), GFY_ERR_WORKSPACE,
+              "%s: workspace %zu < required %zu", who, ws_bytes,
+              align_carry_bytes<kSpan>(p->P, 0));
   const size_t columns =
-      ws_bytes / ((size_t)groups * kAlignWaves * 2 * sizeof(AlignCarry<kSpan>));
+      ws_bytes / ((size_t)align_groups(p->P) * kAlignWaves * 2 * sizeof(AlignCarry<kSpan>));
+  p->carry = ws;
+  p->cap = (int)(columns < GFY_ALIGN_ROWS_MAX ? columns : GFY_ALIGN_ROWS_MAX);
+  return GFY_OK;
+}
+
+// kKernel<<<groups, kAlignThreads, kAlignLds>>>(p): the opt-in to that much dynamic LDS once per
+// device and kernel, as launch_sweep (pairwise_sweep.inc) does it
+template <auto kKernel, class Args>
+int align_launch(const Args& p, int groups, hipStream_t s) {
   static PerDeviceOnce opt_in;
-  if (const int rc = opt_in.run([kernel]() -> int {
-        GFY_CHECK_HIP(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          kAlignLds));
+  if (const int rc = opt_in.run([]() -> int {
+        GFY_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, kAlignLds));
         return GFY_OK;
       }))
     return rc;
-  AlignArgs p{};
-  p.a = (const f16*)a;
-  p.b = (const f16*)b;
-  p.ptr_a = ptr_a;
-  p.ptr_b = ptr_b;
-  p.pairs = pairs;
-  p.n = n;
-  p.m = m;
-  p.P = P;
-  p.records_a = (int)records_a;
-  p.records_b = (int)records_b;
-  p.match_scale = match_scale;
-  p.match_shift = match_shift;
-  p.gap_open = gap_open;
-  p.gap_extend = gap_extend;
-  p.out_score = out_score;
-  p.out_end = out_end;
-  p.carry = ws;
-  p.cap = (int)(columns < GFY_ALIGN_ROWS_MAX ? columns : GFY_ALIGN_ROWS_MAX);
-  launch(groups, p);
+  kKernel<<<groups, kAlignThreads, kAlignLds, s>>>(p);
   GFY_CHECK_HIP(hipGetLastError());
   return GFY_OK;
 }

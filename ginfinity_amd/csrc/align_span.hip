@@ -23,18 +23,12 @@ size_t align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b) {
   return align_carry_bytes<true>(pairs, max_rows_b);
 }
 
-int launch_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
-                            const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
-                            const int32_t* pairs, int64_t P, float match_scale, float match_shift,
-                            float gap_open, float gap_extend, float* out_score,
-                            int32_t* out_start, int32_t* out_end, void* ws, size_t ws_bytes,
+int launch_align_local_span(const AlignArgs& call, int32_t* out_start, void* ws, size_t ws_bytes,
                             hipStream_t s) {
-  return align_launch<true>(
-      "gfy_align_local_span", reinterpret_cast<const void*>(k_align_span), a, n, ptr_a, records_a,
-      b, m, ptr_b, records_b, pairs, P, match_scale, match_shift, gap_open, gap_extend, out_score,
-      out_end, ws, ws_bytes, [s, out_start](int groups, const AlignArgs& p) {
-        k_align_span<<<groups, kAlignThreads, kAlignLds, s>>>(SpanArgs{p, out_start});
-      });
+  SpanArgs p{call, out_start};
+  if (const int rc = align_take_carry<true>("gfy_align_local_span", &p.align, ws, ws_bytes))
+    return rc;
+  return align_launch<k_align_span>(p, align_groups(call.P), s);
 }
 
 }  // namespace gfy

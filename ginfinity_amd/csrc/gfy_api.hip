@@ -10,6 +10,7 @@
 // Compiled with -ffp-contract=off: alpha/shift must round after every step.
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -990,16 +991,38 @@ size_t gfy_pairwise_workspace_bytes(int64_t n, int64_t m) {
   return pairwise_workspace_bytes(n < 1 ? 1 : n, m < 1 ? 1 : m);
 }
 
+// the checks the nearest and top-k calls share, in the style of check_record_call below; `who`
+// names the call in the message
+static int check_pairwise_call(const char* who, const void* a, int64_t n, const void* b, int64_t m,
+                               int metric, const void* out_val, const void* out_idx,
+                               const void* ws) {
+  GFY_REQUIRE(a && b && out_val && out_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
+              GFY_ERR_INVALID, "%s: bad arguments", who);
+  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID, "%s: unknown metric %d",
+              who, metric);
+  return GFY_OK;
+}
+
+static int check_topk_k(const char* who, int k, int most) {
+  GFY_REQUIRE(k >= 1 && k <= most, GFY_ERR_INVALID, "%s: k = %d outside 1..%d", who, k, most);
+  return GFY_OK;
+}
+
+static int check_pairwise_window(const char* who, int64_t window_first, int64_t n, int64_t m) {
+  GFY_REQUIRE(window_first >= 0 && window_first + m <= n, GFY_ERR_INVALID,
+              "%s: b must be rows [%lld, %lld) of the %lld rows of a", who, (long long)window_first,
+              (long long)(window_first + m), (long long)n);
+  return GFY_OK;
+}
+
 int gfy_pairwise_nearest(const void* a, int64_t n, const void* b, int64_t m,
                          int metric, int64_t exclude_offset, float* best_val,
                          int32_t* best_idx, void* ws, size_t ws_bytes,
                          void* stream) {
   clear_error();
-  GFY_REQUIRE(a && b && best_val && best_idx && ws && n > 0 && m > 0 &&
-                  m < INT32_MAX,
-              GFY_ERR_INVALID, "gfy_pairwise_nearest: bad arguments");
-  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
-              "gfy_pairwise_nearest: unknown metric %d", metric);
+  if (const int rc = check_pairwise_call("gfy_pairwise_nearest", a, n, b, m, metric, best_val,
+                                         best_idx, ws))
+    return rc;
   return launch_pairwise_nearest(a, n, b, m, metric, exclude_offset, exclude_offset >= 0 ? 1 : 0,
                                  best_val, best_idx, ws, ws_bytes, (hipStream_t)stream);
 }
@@ -1007,14 +1030,11 @@ int gfy_pairwise_nearest(const void* a, int64_t n, const void* b, int64_t m,
 int gfy_pairwise_nearest_window(const void* a, int64_t n, const void* b, int64_t m, int metric,
                                 int64_t window_first, float* best_val, int32_t* best_idx,
                                 void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "gfy_pairwise_nearest_window";
   clear_error();
-  GFY_REQUIRE(a && b && best_val && best_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
-              GFY_ERR_INVALID, "gfy_pairwise_nearest_window: bad arguments");
-  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
-              "gfy_pairwise_nearest_window: unknown metric %d", metric);
-  GFY_REQUIRE(window_first >= 0 && window_first + m <= n, GFY_ERR_INVALID,
-              "gfy_pairwise_nearest_window: b must be rows [%lld, %lld) of the %lld rows of a",
-              (long long)window_first, (long long)(window_first + m), (long long)n);
+  if (const int rc = check_pairwise_call(who, a, n, b, m, metric, best_val, best_idx, ws))
+    return rc;
+  if (const int rc = check_pairwise_window(who, window_first, n, m)) return rc;
   return launch_pairwise_nearest(a, n, b, m, metric, -window_first, 1, best_val, best_idx, ws,
                                  ws_bytes, (hipStream_t)stream);
 }
@@ -1027,13 +1047,10 @@ size_t gfy_pairwise_topk_workspace_bytes(int64_t n, int64_t m, int k) {
 int gfy_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
                       int64_t exclude_offset, float* top_val, int32_t* top_idx, void* ws,
                       size_t ws_bytes, void* stream) {
+  const char* who = "gfy_pairwise_topk";
   clear_error();
-  GFY_REQUIRE(a && b && top_val && top_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
-              GFY_ERR_INVALID, "gfy_pairwise_topk: bad arguments");
-  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
-              "gfy_pairwise_topk: unknown metric %d", metric);
-  GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_MAX, GFY_ERR_INVALID,
-              "gfy_pairwise_topk: k = %d outside 1..%d", k, GFY_PAIRWISE_TOPK_MAX);
+  if (const int rc = check_pairwise_call(who, a, n, b, m, metric, top_val, top_idx, ws)) return rc;
+  if (const int rc = check_topk_k(who, k, GFY_PAIRWISE_TOPK_MAX)) return rc;
   return launch_pairwise_topk(a, n, b, m, metric, k, exclude_offset, exclude_offset >= 0 ? 1 : 0,
                               nullptr, nullptr, nullptr, nullptr, top_val, top_idx, ws, ws_bytes,
                               (hipStream_t)stream);
@@ -1042,16 +1059,11 @@ int gfy_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int me
 int gfy_pairwise_topk_window(const void* a, int64_t n, const void* b, int64_t m, int metric,
                              int k, int64_t window_first, float* top_val, int32_t* top_idx,
                              void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "gfy_pairwise_topk_window";
   clear_error();
-  GFY_REQUIRE(a && b && top_val && top_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
-              GFY_ERR_INVALID, "gfy_pairwise_topk_window: bad arguments");
-  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_window: unknown metric %d", metric);
-  GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_MAX, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_window: k = %d outside 1..%d", k, GFY_PAIRWISE_TOPK_MAX);
-  GFY_REQUIRE(window_first >= 0 && window_first + m <= n, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_window: b must be rows [%lld, %lld) of the %lld rows of a",
-              (long long)window_first, (long long)(window_first + m), (long long)n);
+  if (const int rc = check_pairwise_call(who, a, n, b, m, metric, top_val, top_idx, ws)) return rc;
+  if (const int rc = check_topk_k(who, k, GFY_PAIRWISE_TOPK_MAX)) return rc;
+  if (const int rc = check_pairwise_window(who, window_first, n, m)) return rc;
   return launch_pairwise_topk(a, n, b, m, metric, k, -window_first, 1, nullptr, nullptr, nullptr,
                               nullptr, top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
 }
@@ -1059,15 +1071,11 @@ int gfy_pairwise_topk_window(const void* a, int64_t n, const void* b, int64_t m,
 int gfy_pairwise_topk_ranges(const void* a, int64_t n, const void* b, int64_t m, int metric, int k,
                              const int32_t* skip_lo, const int32_t* skip_hi, float* top_val,
                              int32_t* top_idx, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "gfy_pairwise_topk_ranges";
   clear_error();
-  GFY_REQUIRE(a && b && top_val && top_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
-              GFY_ERR_INVALID, "gfy_pairwise_topk_ranges: bad arguments");
-  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_ranges: unknown metric %d", metric);
-  GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_MAX, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_ranges: k = %d outside 1..%d", k, GFY_PAIRWISE_TOPK_MAX);
-  GFY_REQUIRE(skip_lo && skip_hi, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_ranges: skip_lo or skip_hi is NULL");
+  if (const int rc = check_pairwise_call(who, a, n, b, m, metric, top_val, top_idx, ws)) return rc;
+  if (const int rc = check_topk_k(who, k, GFY_PAIRWISE_TOPK_MAX)) return rc;
+  GFY_REQUIRE(skip_lo && skip_hi, GFY_ERR_INVALID, "%s: skip_lo or skip_hi is NULL", who);
   return launch_pairwise_topk(a, n, b, m, metric, k, 0, 0, skip_lo, skip_hi, nullptr, nullptr,
                               top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
 }
@@ -1076,18 +1084,12 @@ int gfy_pairwise_topk_distinct(const void* a, int64_t n, const void* b, int64_t 
                                const int32_t* skip_lo, const int32_t* skip_hi,
                                const int32_t* group_lo, const int32_t* group_hi, float* top_val,
                                int32_t* top_idx, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "gfy_pairwise_topk_distinct";
   clear_error();
-  GFY_REQUIRE(a && b && top_val && top_idx && ws && n > 0 && m > 0 && m < INT32_MAX,
-              GFY_ERR_INVALID, "gfy_pairwise_topk_distinct: bad arguments");
-  GFY_REQUIRE(metric == GFY_L2 || metric == GFY_COSINE, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_distinct: unknown metric %d", metric);
-  GFY_REQUIRE(k >= 1 && k <= GFY_PAIRWISE_TOPK_DISTINCT_MAX, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_distinct: k = %d outside 1..%d", k,
-              GFY_PAIRWISE_TOPK_DISTINCT_MAX);
-  GFY_REQUIRE(skip_lo && skip_hi, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_distinct: skip_lo or skip_hi is NULL");
-  GFY_REQUIRE(group_lo && group_hi, GFY_ERR_INVALID,
-              "gfy_pairwise_topk_distinct: group_lo or group_hi is NULL");
+  if (const int rc = check_pairwise_call(who, a, n, b, m, metric, top_val, top_idx, ws)) return rc;
+  if (const int rc = check_topk_k(who, k, GFY_PAIRWISE_TOPK_DISTINCT_MAX)) return rc;
+  GFY_REQUIRE(skip_lo && skip_hi, GFY_ERR_INVALID, "%s: skip_lo or skip_hi is NULL", who);
+  GFY_REQUIRE(group_lo && group_hi, GFY_ERR_INVALID, "%s: group_lo or group_hi is NULL", who);
   return launch_pairwise_topk(a, n, b, m, metric, k, 0, 0, skip_lo, skip_hi, group_lo, group_hi,
                               top_val, top_idx, ws, ws_bytes, (hipStream_t)stream);
 }
@@ -1149,38 +1151,71 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
                                  out_scores, ws, ws_bytes, (hipStream_t)stream);
 }
 
-// the argument rules gfy_align_local, gfy_align_local_span and gfy_align_trace share; out_start is
-// checked by the span call alone (between out_score and out_end, the order of its arguments), and
-// the trace call passes its out_ops and out_len where the others pass out_score and out_end
-static int check_align_call(const char* who, const void* a, int64_t n, const int32_t* ptr_a,
-                            int64_t records_a, const void* b, int64_t m, const int32_t* ptr_b,
-                            int64_t records_b, const int32_t* pairs, int64_t P, float match_scale,
-                            float match_shift, float gap_open, float gap_extend,
-                            const float* out_score, const int32_t* out_start, bool with_start,
-                            const int32_t* out_end, const void* ws) {
-  GFY_REQUIRE(a, GFY_ERR_INVALID, "%s: a is NULL", who);
-  GFY_REQUIRE(b, GFY_ERR_INVALID, "%s: b is NULL", who);
-  GFY_REQUIRE(ptr_a, GFY_ERR_INVALID, "%s: ptr_a is NULL", who);
-  GFY_REQUIRE(ptr_b, GFY_ERR_INVALID, "%s: ptr_b is NULL", who);
-  GFY_REQUIRE(pairs, GFY_ERR_INVALID, "%s: pairs is NULL", who);
-  GFY_REQUIRE(out_score, GFY_ERR_INVALID, "%s: out_score is NULL", who);
-  GFY_REQUIRE(!with_start || out_start, GFY_ERR_INVALID, "%s: out_start is NULL", who);
-  GFY_REQUIRE(out_end, GFY_ERR_INVALID, "%s: out_end is NULL", who);
+// The 14 values every alignment call of the ABI starts with, in the order of include/gfy.h, and
+// an output pointer with the name a refusal gives it.
+struct AlignAbi {
+  const void* a;
+  int64_t n;
+  const int32_t* ptr_a;
+  int64_t records_a;
+  const void* b;
+  int64_t m;
+  const int32_t* ptr_b;
+  int64_t records_b;
+  const int32_t* pairs;
+  int64_t P;
+  float match_scale, match_shift, gap_open, gap_extend;
+};
+struct NamedOutput {
+  const void* pointer;
+  const char* name;
+};
+
+// The argument rules gfy_align_local, gfy_align_local_span and gfy_align_trace share, in one
+// order (the outputs in the order given), and the call record the launchers take: `call` gets
+// every field that comes from the 14 values; the outputs are the entry point's, carry and cap the
+// launcher's.
+static int checked_align_call(const char* who, const AlignAbi& v,
+                              std::initializer_list<NamedOutput> outputs, const void* ws,
+                              AlignArgs* call) {
+  GFY_REQUIRE(v.a, GFY_ERR_INVALID, "%s: a is NULL", who);
+  GFY_REQUIRE(v.b, GFY_ERR_INVALID, "%s: b is NULL", who);
+  GFY_REQUIRE(v.ptr_a, GFY_ERR_INVALID, "%s: ptr_a is NULL", who);
+  GFY_REQUIRE(v.ptr_b, GFY_ERR_INVALID, "%s: ptr_b is NULL", who);
+  GFY_REQUIRE(v.pairs, GFY_ERR_INVALID, "%s: pairs is NULL", who);
+  for (const NamedOutput& out : outputs)
+    GFY_REQUIRE(out.pointer, GFY_ERR_INVALID, "%s: %s is NULL", who, out.name);
   GFY_REQUIRE(ws, GFY_ERR_INVALID, "%s: workspace is NULL", who);
-  GFY_REQUIRE(n > 0 && m > 0 && n < INT32_MAX && m < INT32_MAX, GFY_ERR_INVALID,
-              "%s: bad arguments: n = %lld, m = %lld", who, (long long)n, (long long)m);
-  GFY_REQUIRE(records_a > 0 && records_a < INT32_MAX && records_b > 0 && records_b < INT32_MAX,
+  GFY_REQUIRE(v.n > 0 && v.m > 0 && v.n < INT32_MAX && v.m < INT32_MAX, GFY_ERR_INVALID,
+              "%s: bad arguments: n = %lld, m = %lld", who, (long long)v.n, (long long)v.m);
+  GFY_REQUIRE(v.records_a > 0 && v.records_a < INT32_MAX && v.records_b > 0 &&
+                  v.records_b < INT32_MAX,
               GFY_ERR_INVALID, "%s: records_a = %lld, records_b = %lld outside 1..2^31 - 2", who,
-              (long long)records_a, (long long)records_b);
-  GFY_REQUIRE(P >= 1 && P <= INT32_MAX, GFY_ERR_INVALID, "%s: P = %lld outside 1..2^31 - 1", who,
-              (long long)P);
-  GFY_REQUIRE(std::isfinite(match_scale) && std::isfinite(match_shift) &&
-                  std::isfinite(gap_open) && std::isfinite(gap_extend),
+              (long long)v.records_a, (long long)v.records_b);
+  GFY_REQUIRE(v.P >= 1 && v.P <= INT32_MAX, GFY_ERR_INVALID, "%s: P = %lld outside 1..2^31 - 1",
+              who, (long long)v.P);
+  GFY_REQUIRE(std::isfinite(v.match_scale) && std::isfinite(v.match_shift) &&
+                  std::isfinite(v.gap_open) && std::isfinite(v.gap_extend),
               GFY_ERR_INVALID, "%s: match_scale, match_shift, gap_open and gap_extend must be finite",
               who);
-  GFY_REQUIRE(0.0f <= gap_extend && gap_extend <= gap_open, GFY_ERR_INVALID,
+  GFY_REQUIRE(0.0f <= v.gap_extend && v.gap_extend <= v.gap_open, GFY_ERR_INVALID,
               "%s: 0 <= gap_extend <= gap_open required, got gap_open = %g, gap_extend = %g", who,
-              (double)gap_open, (double)gap_extend);
+              (double)v.gap_open, (double)v.gap_extend);
+  *call = AlignArgs{};
+  call->a = (const f16*)v.a;
+  call->b = (const f16*)v.b;
+  call->ptr_a = v.ptr_a;
+  call->ptr_b = v.ptr_b;
+  call->pairs = v.pairs;
+  call->n = v.n;
+  call->m = v.m;
+  call->P = v.P;
+  call->records_a = (int)v.records_a;
+  call->records_b = (int)v.records_b;
+  call->match_scale = v.match_scale;
+  call->match_shift = v.match_shift;
+  call->gap_open = v.gap_open;
+  call->gap_extend = v.gap_extend;
   return GFY_OK;
 }
 
@@ -1202,13 +1237,16 @@ int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
                     float gap_open, float gap_extend, float* out_score, int32_t* out_end,
                     void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  if (const int rc = check_align_call("gfy_align_local", a, n, ptr_a, records_a, b, m, ptr_b,
-                                      records_b, pairs, P, match_scale, match_shift, gap_open,
-                                      gap_extend, out_score, nullptr, false, out_end, ws))
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_local",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
     return rc;
-  return launch_align_local(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale,
-                            match_shift, gap_open, gap_extend, out_score, out_end, ws, ws_bytes,
-                            (hipStream_t)stream);
+  call.out_score = out_score;
+  call.out_end = out_end;
+  return launch_align_local(call, ws, ws_bytes, (hipStream_t)stream);
 }
 
 int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1217,13 +1255,16 @@ int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t
                          float gap_open, float gap_extend, float* out_score, int32_t* out_start,
                          int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
   clear_error();
-  if (const int rc = check_align_call("gfy_align_local_span", a, n, ptr_a, records_a, b, m, ptr_b,
-                                      records_b, pairs, P, match_scale, match_shift, gap_open,
-                                      gap_extend, out_score, out_start, true, out_end, ws))
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_local_span",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{out_score, "out_score"}, {out_start, "out_start"}, {out_end, "out_end"}}, ws, &call))
     return rc;
-  return launch_align_local_span(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P,
-                                 match_scale, match_shift, gap_open, gap_extend, out_score,
-                                 out_start, out_end, ws, ws_bytes, (hipStream_t)stream);
+  call.out_score = out_score;
+  call.out_end = out_end;
+  return launch_align_local_span(call, out_start, ws, ws_bytes, (hipStream_t)stream);
 }
 
 size_t gfy_align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols) {
@@ -1244,18 +1285,23 @@ int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
   GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_trace: op_ptr is NULL");
   GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_trace: out_ops is NULL");
   GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_trace: out_len is NULL");
-  // out_ops and out_len are named above: the shared check sees them as given
-  if (const int rc = check_align_call("gfy_align_trace", a, n, ptr_a, records_a, b, m, ptr_b,
-                                      records_b, pairs, P, match_scale, match_shift, gap_open,
-                                      gap_extend, reinterpret_cast<const float*>(out_ops), nullptr,
-                                      false, out_len, ws))
+  AlignArgs call;   // the five pointers are named above: no output is left to the shared check
+  if (const int rc = checked_align_call(
+          "gfy_align_trace",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {}, ws, &call))
     return rc;
   GFY_REQUIRE(max_box_rows >= 0 && max_box_cols >= 0, GFY_ERR_INVALID,
               "gfy_align_trace: max_box_rows = %lld, max_box_cols = %lld are negative",
               (long long)max_box_rows, (long long)max_box_cols);
-  return launch_align_trace(a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale,
-                            match_shift, gap_open, gap_extend, starts, ends, op_ptr, out_ops,
-                            out_len, clipped_align_rows(max_box_rows),
+  TraceArgs trace{};
+  trace.starts = starts;
+  trace.ends = ends;
+  trace.op_ptr = op_ptr;
+  trace.out_ops = out_ops;
+  trace.out_len = out_len;
+  return launch_align_trace(call, trace, clipped_align_rows(max_box_rows),
                             clipped_align_rows(max_box_cols), ws, ws_bytes, (hipStream_t)stream);
 }
 

@@ -375,29 +375,47 @@ int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, 
                             hipStream_t s);
 size_t pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_b);
 int pairwise_record_chunks(int64_t n, int64_t m);
+// One alignment call (align_local.inc): what the three entry points of gfy_api.hip check and
+// fill, the launchers complete (carry, cap) and the kernels read as their argument.
+struct AlignArgs {
+  const f16* a;
+  const f16* b;
+  const int32_t* ptr_a;
+  const int32_t* ptr_b;
+  const int32_t* pairs;   // [P][2]
+  int64_t n, m, P;
+  int records_a, records_b;
+  float match_scale, match_shift, gap_open, gap_extend;
+  float* out_score;       // [P]
+  int32_t* out_end;       // [P][2]
+  void* carry;            // [waves of the grid][2][cap] entries of a strip's last row
+  int cap;                // columns a carry buffer holds
+};
+
+// what k_align_trace takes next to AlignArgs (whose out_score / out_end it leaves alone, and whose
+// carry is the whole workspace: per wave two carry buffers of cap entries, then the region)
+struct TraceArgs {
+  const int32_t* starts;   // [P][2]
+  const int32_t* ends;     // [P][2]
+  const int64_t* op_ptr;   // [P + 1]: pair p owns out_ops[op_ptr[p] .. op_ptr[p + 1])
+  uint8_t* out_ops;
+  int32_t* out_len;        // [P]
+  int64_t waves;           // waves the workspace serves; the others return at once
+  int64_t wave_bytes;      // workspace of one wave
+  int64_t region_words;    // direction words a wave's region holds
+};
+
 // align_local.hip
-int launch_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
-                       const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
-                       const int32_t* pairs, int64_t P, float match_scale, float match_shift,
-                       float gap_open, float gap_extend, float* out_score, int32_t* out_end,
-                       void* ws, size_t ws_bytes, hipStream_t s);
+int launch_align_local(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
 size_t align_workspace_bytes(int64_t pairs, int64_t max_rows_b);
 // align_span.hip: the same with the start cell of every alignment
-int launch_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
-                            const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
-                            const int32_t* pairs, int64_t P, float match_scale, float match_shift,
-                            float gap_open, float gap_extend, float* out_score,
-                            int32_t* out_start, int32_t* out_end, void* ws, size_t ws_bytes,
+int launch_align_local_span(const AlignArgs& call, int32_t* out_start, void* ws, size_t ws_bytes,
                             hipStream_t s);
 size_t align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
-// align_trace.hip: the aligned path of the box start..end of every pair
-int launch_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
-                       const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
-                       const int32_t* pairs, int64_t P, float match_scale, float match_shift,
-                       float gap_open, float gap_extend, const int32_t* starts,
-                       const int32_t* ends, const int64_t* op_ptr, uint8_t* out_ops,
-                       int32_t* out_len, int64_t max_box_rows, int64_t max_box_cols, void* ws,
-                       size_t ws_bytes, hipStream_t s);
+// align_trace.hip: the aligned path of the box start..end of every pair; `trace` carries the
+// caller's five pointers, the rest of it is set here
+int launch_align_trace(const AlignArgs& call, const TraceArgs& trace, int64_t max_box_rows,
+                       int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
 size_t align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------

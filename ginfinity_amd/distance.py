@@ -88,6 +88,14 @@ def pairwise(a, b=None, *, metric: str = "l2") -> torch.Tensor:
     return out
 
 
+def _grown(kept: torch.Tensor | None, device, count: int, dtype) -> torch.Tensor:
+    """The grow rule of every workspace: ``kept`` where it lives on ``device`` and holds ``count``
+    elements, a new tensor of ``max(count, 1)`` otherwise."""
+    if kept is None or kept.numel() < count or kept.device != device:
+        return torch.empty(max(count, 1), dtype=dtype, device=device)
+    return kept
+
+
 class NearestWorkspace:
     """Scratch memory and result arrays of ``nearest`` kept across calls (the chunked
     cross-shard search calls it once per rank's piece and chunk: allocating per call costs
@@ -99,12 +107,9 @@ class NearestWorkspace:
         self.indices: torch.Tensor | None = None
 
     def buffers(self, device, rows: int, scratch_bytes: int):
-        if self.scratch is None or self.scratch.numel() < scratch_bytes or \
-                self.scratch.device != device:
-            self.scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=device)
-        if self.values is None or self.values.numel() < rows or self.values.device != device:
-            self.values = torch.empty(max(rows, 1), dtype=torch.float32, device=device)
-            self.indices = torch.empty(max(rows, 1), dtype=torch.int32, device=device)
+        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
+        self.values = _grown(self.values, device, rows, torch.float32)
+        self.indices = _grown(self.indices, device, rows, torch.int32)
         return self.scratch, self.values[:rows], self.indices[:rows]
 
 
@@ -191,6 +196,13 @@ def _checked_ranges(n: int, b_rows: int | None, exclude_ranges, exclude_records,
     return tuple(bounds)
 
 
+def _results(values, indices, scratch) -> tuple:
+    """What a ``nearest`` / ``topk`` call of the C ABI ends with: the two results, the scratch
+    memory and its size, the current stream of their device."""
+    return (values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
+            torch.cuda.current_stream(values.device).cuda_stream)
+
+
 def nearest(a, b=None, *, metric: str = "l2", exclude_self: bool = False,
             exclude_offset: int | None = None, window_first: int | None = None,
             exclude_ranges=None, exclude_records=None,
@@ -233,17 +245,13 @@ def nearest(a, b=None, *, metric: str = "l2", exclude_self: bool = False,
             scratch = torch.empty(need, dtype=torch.uint8, device=a.device)
         else:
             scratch, values, indices = workspace.buffers(a.device, n, need)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
         if window_first is None:
-            native.check(lib.gfy_pairwise_nearest(
-                a.data_ptr(), n, b.data_ptr(), m, _metric(metric),
-                int(exclude_offset), values.data_ptr(), indices.data_ptr(),
-                scratch.data_ptr(), scratch.numel(), stream), "gfy_pairwise_nearest")
+            name, middle = "gfy_pairwise_nearest", (int(exclude_offset),)
         else:
-            native.check(lib.gfy_pairwise_nearest_window(
-                a.data_ptr(), n, b.data_ptr(), m, _metric(metric), int(window_first),
-                values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                stream), "gfy_pairwise_nearest_window")
+            name, middle = "gfy_pairwise_nearest_window", (int(window_first),)
+        native.check(getattr(lib, name)(
+            a.data_ptr(), n, b.data_ptr(), m, _metric(metric), *middle,
+            *_results(values, indices, scratch)), name)
     return values, indices
 
 
@@ -257,12 +265,9 @@ class TopKWorkspace:
         self.indices: torch.Tensor | None = None
 
     def buffers(self, device, rows: int, k: int, scratch_bytes: int):
-        if self.scratch is None or self.scratch.numel() < scratch_bytes or \
-                self.scratch.device != device:
-            self.scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=device)
-        if self.values is None or self.values.numel() < rows * k or self.values.device != device:
-            self.values = torch.empty(max(rows * k, 1), dtype=torch.float32, device=device)
-            self.indices = torch.empty(max(rows * k, 1), dtype=torch.int32, device=device)
+        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
+        self.values = _grown(self.values, device, rows * k, torch.float32)
+        self.indices = _grown(self.indices, device, rows * k, torch.int32)
         return (self.scratch, self.values[:rows * k].view(rows, k),
                 self.indices[:rows * k].view(rows, k))
 
@@ -363,30 +368,20 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
             scratch = torch.empty(need, dtype=torch.uint8, device=a.device)
         else:
             scratch, values, indices = workspace.buffers(a.device, n, k, need)
-        stream = torch.cuda.current_stream(a.device).cuda_stream
         if n == 0:
             return values, indices
         if groups is not None:
-            native.check(lib.gfy_pairwise_topk_distinct(
-                a.data_ptr(), n, b.data_ptr(), m, code, k, ranges[0].data_ptr(),
-                ranges[1].data_ptr(), groups[0].data_ptr(), groups[1].data_ptr(),
-                values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                stream), "gfy_pairwise_topk_distinct")
+            name = "gfy_pairwise_topk_distinct"
+            middle = tuple(bound.data_ptr() for bound in (*ranges, *groups))
         elif ranges is not None:
-            native.check(lib.gfy_pairwise_topk_ranges(
-                a.data_ptr(), n, b.data_ptr(), m, code, k, ranges[0].data_ptr(),
-                ranges[1].data_ptr(), values.data_ptr(), indices.data_ptr(), scratch.data_ptr(),
-                scratch.numel(), stream), "gfy_pairwise_topk_ranges")
+            name, middle = "gfy_pairwise_topk_ranges", tuple(bound.data_ptr() for bound in ranges)
         elif window_first is None:
-            native.check(lib.gfy_pairwise_topk(
-                a.data_ptr(), n, b.data_ptr(), m, code, k, int(exclude_offset),
-                values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                stream), "gfy_pairwise_topk")
+            name, middle = "gfy_pairwise_topk", (int(exclude_offset),)
         else:
-            native.check(lib.gfy_pairwise_topk_window(
-                a.data_ptr(), n, b.data_ptr(), m, code, k, int(window_first),
-                values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
-                stream), "gfy_pairwise_topk_window")
+            name, middle = "gfy_pairwise_topk_window", (int(window_first),)
+        native.check(getattr(lib, name)(
+            a.data_ptr(), n, b.data_ptr(), m, code, k, *middle,
+            *_results(values, indices, scratch)), name)
     return values, indices
 
 
@@ -398,9 +393,7 @@ class RecordWorkspace:
         self.scratch: torch.Tensor | None = None
 
     def buffer(self, device, scratch_bytes: int) -> torch.Tensor:
-        if self.scratch is None or self.scratch.numel() < scratch_bytes or \
-                self.scratch.device != device:
-            self.scratch = torch.empty(max(scratch_bytes, 1), dtype=torch.uint8, device=device)
+        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
         return self.scratch
 
 
