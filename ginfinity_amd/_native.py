@@ -143,6 +143,12 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_align_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "gfy_align_trace": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+    "gfy_align_global": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
+    "gfy_align_global_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gfy_align_global_trace": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t,
+                                       c_void_p]),
 }
 
 

@@ -74,10 +74,50 @@ device walks the box ``start..end`` alone, which gives the same ops as the full 
 (include/gfy.h has the argument), and keeps 4 bits per cell of the box in scratch memory: the
 only thing proportional to ``Lq x Lr`` that is ever written.
 
+Global and query-in-target alignment.  ``global_align`` and ``global_paths`` answer two other
+questions with the same recurrences, substitution scores and parameters.  ``within=False`` is
+global alignment (Needleman-Wunsch with affine gaps): how similar are two whole records — both
+take part end to end, and unrelated flanks are charged for.  ``within=True`` is query-in-target
+("fit") alignment: where does all of the a-record lie inside the b-record — the b-record's rows
+in front of and behind the alignment are free, so a window cannot take part with a piece of
+itself as it may in a local alignment:
+
+    E[i][j] = max(E[i][j-1] - gap_extend, H[i][j-1] - gap_open)
+    F[i][j] = max(F[i-1][j] - gap_extend, H[i-1][j] - gap_open)
+    H[i][j] = max(H[i-1][j-1] + s[i][j], E[i][j], F[i][j])              (no 0 candidate)
+
+The borders are the same recurrences carried onto row -1 and column -1, so a border is an
+iterated sum and not a closed form.  ``H[-1][-1] = 0``.  Left border, both modes: ``F[i][-1] =
+max(F[i-1][-1] - gap_extend, H[i-1][-1] - gap_open)``, ``H[i][-1] = F[i][-1]``, ``E[i][-1] =
+-inf``, with ``F[-1][-1] = -inf``; that is ``H[0][-1] = fl32(0 - gap_open)`` and ``H[i][-1] =
+fl32(H[i-1][-1] - gap_extend)``.  Top border, global: the mirror image, ``H[-1][j] = E[-1][j]``
+iterated along j and ``F[-1][j] = -inf``.  Top border, ``within``: ``H[-1][j] = 0`` and ``E[-1][j]
+= F[-1][j] = -inf`` for every j.
+
+Global: ``score = H[Lq-1][Lr-1]`` and ``end = (Lq-1, Lr-1)``.  ``within``: ``score = max_j
+H[Lq-1][j]`` over ``0 <= j < Lr`` and ``end = (Lq-1, j)`` for the first such j.  Scores may be
+negative.  A pair with a record of zero rows on either side is "nothing to align": score 0, end
+``(-1, -1)`` and an empty path, as in the local mode (not the cost of a gap).  Because every
+operation is monotone in its inputs and the modes differ only in the candidates they add,
+``global score <= within score <= local score`` holds exactly, in float32 comparison, for any
+pair and parameters.
+
+The path of these modes is the walk back from ``end``, starting in H, by the tie rules above (in
+H the diagonal first, then E, then F; in E and F opening wins a tie), with the same ops in
+forward order.  There is no "starts here" rule: the walk ends on a border.  At ``(-1, -1)`` it
+stops; at ``(i, -1)`` it emits ``i + 1`` ops ``2`` (the left border is a charged gap); at ``(-1,
+j)`` global emits ``j + 1`` ops ``1`` and ``within`` stops (those rows are free).  A path has at
+most ``Lq + Lr`` ops, one more than the local bound.  ``start`` is (first row of A consumed, first
+row of B consumed): ``start_i`` is always 0, ``start_j`` is 0 for global and ``end_j + 1 - #(ops
+!= 2)`` for ``within``, which is ``end_j + 1`` when no row of B is consumed; ``path_cells(ops,
+start)`` gives the cells.  Re-scoring the ops by the rule above gives ``score`` bit for bit,
+which is why the borders are iterated.
+
 Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIMUM_LENGTH_NT``),
-``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: banded or global
-alignment, a ``device="cpu"`` path, and any z-score or normalisation of the scores.  Measured
-cost: DESIGN.md §4.
+``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: banded alignment, a
+span-only kernel for the global and ``within`` modes, free ends on the a-side, a
+``device="cpu"`` path, and any z-score or normalisation of the scores.  Measured cost: DESIGN.md
+§4.
 """
 from __future__ import annotations
 
@@ -92,8 +132,8 @@ from .distance import _checked, _grown, _prepare, _record_ptr
 
 
 class AlignWorkspace:
-    """Scratch memory of ``local_align``, ``local_spans`` and ``local_paths`` kept across calls,
-    as ``distance.RecordWorkspace`` keeps that of ``record_scores`` (the results are always new
+    """Scratch memory of ``local_align``, ``local_spans``, ``local_paths``, ``global_align`` and
+    ``global_paths`` kept across calls, as ``distance.RecordWorkspace`` keeps that of ``record_scores`` (the results are always new
     tensors)."""
 
     def __init__(self) -> None:
@@ -177,8 +217,8 @@ class _Call(NamedTuple):
 
 def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
                   match_shift) -> _Call:
-    """Every check of ``local_align``, ``local_spans`` and ``local_paths``: the call, or the
-    ``ValueError``.  No device is touched."""
+    """Every check the alignment functions share: the call, or the ``ValueError``.  No device is
+    touched."""
     gap_open = _checked_parameter(gap_open, "gap_open")
     gap_extend = _checked_parameter(gap_extend, "gap_extend")
     match_scale = _checked_parameter(match_scale, "match_scale")
@@ -300,9 +340,7 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     The other arguments, their checks and the ``ValueError``s are those of ``local_spans``; an
     ``AlignWorkspace`` serves all three functions.  ``P == 0``, or a call with no rows, returns
     empty tensors without a launch."""
-    if isinstance(max_workspace_bytes, bool) or \
-            not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 1:
-        raise ValueError("max_workspace_bytes must be a positive integer")
+    max_workspace_bytes = _checked_cap(max_workspace_bytes)
     call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
                          match_shift).on_device()
     scores, starts, ends = _launch(call, True, workspace)
@@ -319,7 +357,7 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
         lib = native.library()
         box_rows, box_cols = int(box[:, 0].max()), int(box[:, 1].max())
         need = min(lib.gfy_align_trace_workspace_bytes(count, box_rows, box_cols),
-                   int(max_workspace_bytes))
+                   max_workspace_bytes)
         scratch = (workspace or AlignWorkspace()).buffer(device, need)
         slot_ptr_dev = torch.from_numpy(slot_ptr).to(device)
         slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
@@ -328,15 +366,127 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
             *call.arguments(), starts.data_ptr(), ends.data_ptr(), slot_ptr_dev.data_ptr(),
             slot_ops.data_ptr(), lengths.data_ptr(), box_rows, box_cols, scratch.data_ptr(), need,
             torch.cuda.current_stream(device).cuda_stream), "gfy_align_trace")
-        # compaction, not the hot path: the front of every slot, one after the other
-        lengths = lengths.to(torch.int64)
         if bool((lengths < 0).any()):
             raise native.NativeLibraryError("gfy_align_trace refused a box of gfy_align_local_span")
-        offsets = torch.cat([lengths.new_zeros(1), torch.cumsum(lengths, 0)])
-        owner = torch.repeat_interleave(torch.arange(count, device=device),
-                                        torch.from_numpy(slots).to(device))
-        within = torch.arange(slot_ops.shape[0], device=device) - slot_ptr_dev[owner]
-        return AlignedPaths(scores, starts, ends, slot_ops[within < lengths[owner]], offsets)
+        return AlignedPaths(scores, starts, ends,
+                            *_compacted(slot_ops, slot_ptr_dev, slots, lengths))
+
+
+def _compacted(slot_ops, slot_ptr_dev, slots: np.ndarray, lengths) -> tuple:
+    """``(ops, offsets)`` of traced slots: the front ``lengths[p]`` of every slot, one after the
+    other.  Not the hot path."""
+    device, count = slot_ops.device, lengths.shape[0]
+    lengths = lengths.to(torch.int64)
+    offsets = torch.cat([lengths.new_zeros(1), torch.cumsum(lengths, 0)])
+    owner = torch.repeat_interleave(torch.arange(count, device=device),
+                                    torch.from_numpy(slots).to(device))
+    inside = torch.arange(slot_ops.shape[0], device=device) - slot_ptr_dev[owner]
+    return slot_ops[inside < lengths[owner]], offsets
+
+
+def _checked_within(within) -> bool:
+    if not isinstance(within, (bool, np.bool_)):
+        raise ValueError("within must be True (query-in-target) or False (global)")
+    return bool(within)
+
+
+def _checked_cap(max_workspace_bytes) -> int:
+    if isinstance(max_workspace_bytes, bool) or \
+            not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 1:
+        raise ValueError("max_workspace_bytes must be a positive integer")
+    return int(max_workspace_bytes)
+
+
+def _launch_global(call: _Call, within: bool, workspace) -> tuple:
+    """The launch behind ``global_align``: ``(scores, ends)`` of a call that is ``on_device``; an
+    empty call gives its results without one."""
+    device, count = call.a.device, call.pairs.shape[0]
+    with torch.cuda.device(device):
+        scores = torch.zeros(count, dtype=torch.float32, device=device)
+        ends = torch.full((count, 2), -1, dtype=torch.int32, device=device)
+        if not call.empty:
+            lib = native.library()
+            need = lib.gfy_align_workspace_bytes(count, int(call.rows_b.max()))
+            scratch = (workspace or AlignWorkspace()).buffer(device, need)
+            native.check(lib.gfy_align_global(
+                *call.arguments(), int(within), scores.data_ptr(), ends.data_ptr(),
+                scratch.data_ptr(), scratch.numel(),
+                torch.cuda.current_stream(device).cuda_stream), "gfy_align_global")
+    return scores, ends
+
+
+def global_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                 match_scale=1.0, match_shift=0.0, within: bool = False,
+                 workspace: AlignWorkspace | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Global (``within=False``) or query-in-target (``within=True``) alignment of the record
+    pairs ``pairs``: ``(scores float32 [P], ends int32 [P, 2])`` on the device, exact, the ``Lq x
+    Lr`` matrix of a pair never written (the definition is at the head of this module).  Global:
+    both records take part end to end and ``end`` is ``(Lq - 1, Lr - 1)``.  ``within``: all of the
+    a-record is aligned inside the b-record, whose rows in front of and behind the alignment are
+    free; ``end`` is ``(Lq - 1, j)`` for the first best j.  Scores may be negative; a pair with a
+    record of zero rows on either side has nothing to align and gives 0 and ``(-1, -1)``.
+    ``global <= within <= local_align`` holds for the scores of any pair, exactly.
+
+    The other arguments, their checks and the ``ValueError``s are those of ``local_align``;
+    ``within`` must be a bool.  An ``AlignWorkspace`` serves this function too."""
+    within = _checked_within(within)
+    return _launch_global(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                        match_scale, match_shift).on_device(), within, workspace)
+
+
+def global_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                 match_scale=1.0, match_shift=0.0, within: bool = False,
+                 workspace: AlignWorkspace | None = None,
+                 max_workspace_bytes: int = 2 << 30) -> AlignedPaths:
+    """``global_align`` with the aligned path of every pair: ``AlignedPaths(scores, starts, ends,
+    ops, offsets)`` on the device, ops and offsets as ``local_paths`` returns them.  The path
+    takes in every row of the a-record, and of the b-record every row (global) or rows ``start_j
+    .. end_j`` (``within``); the border it ends on is part of it (the walk is at the head of this
+    module), so a path has up to ``Lq + Lr`` ops and may consist of gaps alone.  ``starts[p]`` is
+    ``(0, 0)`` for global and ``(0, start_j)`` for ``within``, where ``start_j = end_j + 1`` if no
+    row of the b-record is consumed; ``path_cells(ops, start)`` gives the cells.  Scores and ends
+    are those of ``global_align`` bit for bit; a pair with nothing to align has start and end
+    ``(-1, -1)`` and an empty path.
+
+    Two launches and no copy to the host between them: every slot (``Lq + Lr`` ops) and the
+    largest box are known from the counts, and the trace launch reads the ends of the first one
+    on the device.  The workspace of the trace and ``max_workspace_bytes`` are those of
+    ``local_paths``, the boxes being the records' own sizes.
+
+    The other arguments, their checks and the ``ValueError``s are those of ``global_align``."""
+    within = _checked_within(within)
+    cap = _checked_cap(max_workspace_bytes)
+    call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
+                         match_shift).on_device()
+    scores, ends = _launch_global(call, within, workspace)
+    device, count = scores.device, scores.shape[0]
+    with torch.cuda.device(device):
+        starts = torch.full((count, 2), -1, dtype=torch.int32, device=device)
+        rows_a = np.diff(call.ptr_a)[call.pairs[:, 0]].astype(np.int64)
+        rows_b = call.rows_b.astype(np.int64)
+        slots = np.where((rows_a > 0) & (rows_b > 0), rows_a + rows_b, 0)   # Lq + Lr ops at most
+        slot_ptr = np.concatenate(([0], np.cumsum(slots)))
+        if call.empty or slot_ptr[-1] == 0:                         # every path is empty
+            return AlignedPaths(scores, starts, ends,
+                                torch.zeros(0, dtype=torch.uint8, device=device),
+                                torch.zeros(count + 1, dtype=torch.int64, device=device))
+        lib = native.library()
+        most_a, most_b = int(rows_a.max()), int(rows_b.max())
+        need = min(lib.gfy_align_global_trace_workspace_bytes(count, most_a, most_b), cap)
+        scratch = (workspace or AlignWorkspace()).buffer(device, need)
+        slot_ptr_dev = torch.from_numpy(slot_ptr).to(device)
+        slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
+        lengths = torch.zeros(count, dtype=torch.int32, device=device)
+        native.check(lib.gfy_align_global_trace(
+            *call.arguments(), int(within), ends.data_ptr(), slot_ptr_dev.data_ptr(),
+            slot_ops.data_ptr(), lengths.data_ptr(), starts.data_ptr(), most_a, most_b,
+            scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
+            "gfy_align_global_trace")
+        if bool((lengths < 0).any()):
+            raise native.NativeLibraryError(
+                "gfy_align_global_trace refused an end of gfy_align_global")
+        return AlignedPaths(scores, starts, ends,
+                            *_compacted(slot_ops, slot_ptr_dev, slots, lengths))
 
 
 def path_cells(ops, start) -> np.ndarray:
@@ -385,5 +535,5 @@ def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
     return np.stack([rows, order.reshape(-1)], axis=1).astype(np.int32)
 
 
-__all__ = ["local_align", "local_spans", "local_paths", "path_cells", "AlignedPaths",
-           "AlignWorkspace", "top_pairs"]
+__all__ = ["local_align", "local_spans", "local_paths", "global_align", "global_paths",
+           "path_cells", "AlignedPaths", "AlignWorkspace", "top_pairs"]

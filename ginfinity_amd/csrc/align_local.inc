@@ -43,6 +43,17 @@
 //     at once, so a run of matches costs one load per 64 ops, a gap position one load each.  The
 //     ops go to the ring (free by then) in reverse, one byte each, and the lanes copy them
 //     forward into the pair's slot.  With kTrace = false none of it exists.
+//   * kGlobal: the same recurrences without the 0 candidate and with charged borders (global
+//     alignment, and with the wave-uniform flag `within` the query-in-target mode whose top border
+//     is free; semantics: include/gfy.h, gfy_align_global).  The borders are iterated sums, and
+//     they are iterated here: a wave-uniform running value goes down the left border across the
+//     strips, 64 subtractions per strip of which lane k keeps step k (its initial H) and step
+//     k - 1 (its initial diagonal), and one goes along the top border 32 columns at a time into
+//     what strip 0 takes for its carry.  The score is the last H of the lane that owns row Lq - 1
+//     (global) or that lane's best with a strict > from -inf (within); no other lane tracks
+//     anything.  With kTrace the box is rows 0 .. Lq - 1 and columns 0 .. end_j, whose top-left
+//     corner is the matrix's own; the walk has no "starts here", leaves the box over a border and
+//     the lanes add the border's ops behind it.  With kGlobal = false none of it exists.
 // ptr_a, ptr_b and pairs are device arrays: they are compared and clipped, a pair outside them or
 // longer than the limits gets NaN and (-2, -2), and nothing outside the caller's buffers is read.
 #pragma once
@@ -93,11 +104,14 @@ __device__ __forceinline__ void record_rows(const int32_t* ptr, int index, int64
   hi = hi < lo ? lo : hi > rows ? rows : hi;
 }
 
-// out_start ([P][2]) is written with kSpan alone, trace is read with kTrace alone
-template <bool kSpan, bool kTrace = false>
+// out_start ([P][2]) is written with kSpan, and with kTrace and kGlobal together; trace is read
+// with kTrace alone, within (wave-uniform) with kGlobal alone
+template <bool kSpan, bool kTrace = false, bool kGlobal = false>
 __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start,
-                                            const TraceArgs* trace = nullptr) {
+                                            const TraceArgs* trace = nullptr,
+                                            bool within = false) {
   static_assert(!(kSpan && kTrace), "the trace runs on the plain (H, F) carry");
+  static_assert(!(kSpan && kGlobal), "a global alignment starts at the matrix's corner");
   using Carry = AlignCarry<kSpan>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -133,7 +147,25 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
     ok = ok && a_hi - a_lo <= GFY_ALIGN_ROWS_MAX && b_hi - b_lo <= GFY_ALIGN_ROWS_MAX &&
          (kTrace || b_hi - b_lo <= p.cap);
     int64_t op_lo = 0;   // kTrace: where the pair's slot starts
-    if constexpr (kTrace) {
+    if constexpr (kTrace && kGlobal) {
+      // the box is rows 0 .. Lq - 1 and columns 0 .. end_j of the records: only an end that
+      // gfy_align_global can have named, whose box fits the wave's region and whose path fits the
+      // slot is followed; (-1, -1) is the empty alignment
+      const int ei = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair]);
+      const int ej = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair + 1]);
+      op_lo = trace->op_ptr[pair];
+      const int64_t op_hi = trace->op_ptr[pair + 1];
+      const int64_t full_q = a_hi - a_lo, full_r = b_hi - b_lo;
+      const bool none = ei == -1 && ej == -1;
+      bool box = ok && !none && ei == full_q - 1 && ej >= 0 && ej < full_r &&
+                 (within || ej == full_r - 1);
+      const int64_t box_rows = box ? full_q : 0, box_cols = box ? (int64_t)ej + 1 : 0;
+      box = box && box_cols <= p.cap && box_rows * ((box_cols + 7) >> 3) <= trace->region_words &&
+            op_lo >= 0 && op_hi - op_lo >= box_rows + box_cols;
+      ok = ok && (none || box);
+      a_hi = a_lo + box_rows;
+      b_hi = b_lo + box_cols;
+    } else if constexpr (kTrace) {
       // the box inside the records: only a box that lies in them, fits the wave's region and
       // whose path fits the slot is followed; (-1, -1) is the empty alignment
       const int si = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair]);
@@ -159,11 +191,13 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
     const f16* rows_a = p.a + a_lo * 128;
     const f16* rows_b = p.b + b_lo * 128;
 
-    float best = 0.f;   // strict >: only a positive cell is ever kept
+    // strict >: only a positive cell is ever kept; kGlobal: any cell of row Lq - 1
+    float best = kGlobal ? -__builtin_inff() : 0.f;
     int best_i = -1, best_j = -1;
     uint32_t best_o = 0;   // kSpan: the origin of the best cell
     const int dir_pitch = (lr + 7) >> 3;   // kTrace: words of a row of the box
-    float h_last = 0.f;                    // kTrace: a lane's H when its strip ended
+    float h_last = 0.f;                    // kTrace, kGlobal: a lane's H when its strip ended
+    float left_run = 0.f;                  // kGlobal: H[i0 - 1][-1], down the left border
 
     // 32 b-rows from column c0 on as this lane's eight 16-byte pieces: piece lane + 64 x is
     // chunk lane & 15 of row (lane >> 4) + 4 x — a row on 16 consecutive lanes (row_square_sum)
@@ -207,6 +241,19 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
 
       float h = 0.f, e = minus_inf, f = minus_inf;   // this lane's last cell
       float diag = 0.f;                              // H of the row above, one column back
+      float top_run = 0.f;                           // kGlobal: H[-1][c0 - 1], along the top border
+      bool tracks = false;                           // kGlobal: this lane owns row Lq - 1 (within)
+      if constexpr (kGlobal) {
+        // the left border, iterated: H[0][-1] = 0 - gap_open, H[i][-1] = H[i-1][-1] - gap_extend;
+        // lane k starts from step k and has step k - 1 on its diagonal
+#pragma unroll 8
+        for (int k = 0; k < kStrip; ++k) {
+          diag = lane == k ? left_run : diag;
+          left_run = i0 + k == 0 ? 0.f - go : left_run - ge;
+          h = lane == k ? left_run : h;
+        }
+        tracks = within && !onward && lane == ((lq - 1) & (kStrip - 1));
+      }
       uint32_t o_h = 0, o_e = 0, o_f = 0, o_diag = 0;   // kSpan: their origins
       uint32_t dir_word = 0;                            // kTrace: the row's 8 columns in the making
       f16x8 b_next[8];
@@ -217,6 +264,17 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
         if constexpr (kSpan) v = Carry{__float_as_uint(0.f), __float_as_uint(minus_inf), 0u, 0u};
         else v = make_float2(0.f, minus_inf);
         if (strip > 0 && lane < kSub && c0 + lane < lr) v = carry_in[c0 + lane];
+        if constexpr (kGlobal) {
+          // the top border, iterated like the left one (F stays -inf); within: the rows of B in
+          // front of the alignment are free, H = 0
+          if (strip == 0 && !within) {
+#pragma unroll 8
+            for (int k = 0; k < kSub; ++k) {
+              top_run = c0 + k == 0 ? 0.f - go : top_run - ge;
+              v.x = lane == k ? top_run : v.x;
+            }
+          }
+        }
         return v;
       };
       Carry carry_next = load_carry(0);
@@ -275,8 +333,11 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           const float match = diag + s;
           const float e_new = __builtin_fmaxf(e_ext, e_open);
           const float f_new = __builtin_fmaxf(f_ext, f_open);
-          const float h_new = __builtin_fmaxf(__builtin_fmaxf(0.f, match),
-                                              __builtin_fmaxf(e_new, f_new));
+          float h_new;
+          if constexpr (kGlobal)   // no 0 candidate
+            h_new = __builtin_fmaxf(match, __builtin_fmaxf(e_new, f_new));
+          else
+            h_new = __builtin_fmaxf(__builtin_fmaxf(0.f, match), __builtin_fmaxf(e_new, f_new));
           uint32_t o_new = 0;
           if constexpr (kSpan) {
             uint32_t up_oh = (uint32_t)__shfl_up((int)o_h, 1, 64);
@@ -298,7 +359,9 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           if constexpr (kTrace) {
             // the same selections as kSpan's, kept as bits: diagonal, then E, then F; opening
             // wins a tie
-            const uint32_t how = h_new == match ? (diag > 0.f ? 1u : 0u) : h_new == e_new ? 2u : 3u;
+            // (kGlobal: no path starts inside the matrix, 0 is unused)
+            const uint32_t how =
+                h_new == match ? (kGlobal || diag > 0.f ? 1u : 0u) : h_new == e_new ? 2u : 3u;
             const uint32_t bits = how | (e_open >= e_ext ? 4u : 0u) | (f_open >= f_ext ? 8u : 0u);
             if (live) {
               dir_word = (j & 7) == 0 ? bits : dir_word | (bits << (4 * (j & 7)));
@@ -310,7 +373,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           f = live ? f_new : f;
           h = live ? h_new : h;
           diag = live ? up_h : diag;
-          const bool better = live && h_new > best;
+          const bool better = live && (!kGlobal || tracks) && h_new > best;
           best = better ? h_new : best;
           best_i = better ? i0 + lane : best_i;
           best_j = better ? j : best_j;
@@ -323,7 +386,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           }
         }
       }
-      if constexpr (kTrace) h_last = h;
+      if constexpr (kTrace || kGlobal) h_last = h;
       // the next strip reads what lane 63 stored (and restages the ring); kTrace: the walk reads
       // the direction words the lanes stored
       __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
@@ -333,9 +396,11 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
     if constexpr (kTrace) {
       int length = 0;
       // H of the box's last cell is the last H of the lane that owns its row
-      if (strips > 0 && lane_value(h_last, (lq - 1) & (kStrip - 1)) > 0.f) {
-        uint8_t* reversed = reinterpret_cast<uint8_t*>(ring);   // <= 8191 ops of a byte
-        const int limit = lq + lr - 1;
+      int start_j = 0;   // kGlobal: the first row of B the path consumes
+      // (kGlobal: any H is walked back from, and a path that is all gaps has Lq + Lr ops)
+      if (strips > 0 && (kGlobal || lane_value(h_last, (lq - 1) & (kStrip - 1)) > 0.f)) {
+        uint8_t* reversed = reinterpret_cast<uint8_t*>(ring);   // <= 8192 ops of a byte
+        const int limit = lq + lr - (kGlobal ? 0 : 1);
         int i = lq - 1, j = lr - 1, state = 0;   // 0 in H, 1 in E, 2 in F
         int anchor_i = -1, anchor_j = -1;        // lane l holds the word of cell anchor - (l, l)
         uint32_t window = 0;
@@ -358,7 +423,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
               state = (int)how - 1;
               continue;
             }
-            op = 0, last = how == 0u;
+            op = 0, last = !kGlobal && how == 0u;
             --i, --j;
           } else if (state == 1) {
             op = 1, state = bits & 4u ? 0 : 1;
@@ -371,13 +436,47 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           ++length;
           if (last) break;
         }
+        if constexpr (kGlobal) {
+          // the walk left the box in H (a gap that reaches a border opened there).  The left
+          // border is a charged gap of i + 1 rows of A, the top border one of j + 1 rows of B, or
+          // with `within` free: the path starts behind it.  They are the path's first ops.
+          int more = 0, op = 2;
+          if (j < 0) more = i + 1;
+          else if (i < 0 && within) start_j = j + 1;
+          else if (i < 0) more = j + 1, op = 1;
+          more = more < limit - length ? more : limit - length;
+          wave_sync();
+          for (int x = lane; x < more; x += 64) reversed[length + x] = (uint8_t)op;
+          length += more;
+        }
         wave_sync();
         for (int x = lane; x < length; x += 64) trace->out_ops[op_lo + x] = reversed[length - 1 - x];
         wave_sync();   // the next pair restages the ring
       }
       if (lane == 0) trace->out_len[pair] = ok ? length : -2;
+      if constexpr (kGlobal) {
+        if (lane == 0) {
+          out_start[2 * pair] = ok ? (strips > 0 ? 0 : -1) : -2;
+          out_start[2 * pair + 1] = ok ? (strips > 0 ? start_j : -1) : -2;
+        }
+      }
     }
 
+    if constexpr (kGlobal) {
+      // the last cell, or the first best cell of the last row: one lane holds either
+      if (!kTrace) {
+        const int owner = (lq - 1) & (kStrip - 1);
+        const float score = within ? lane_value(best, owner) : lane_value(h_last, owner);
+        const int end_j = within ? __builtin_amdgcn_readlane(best_j, owner) : lr - 1;
+        if (lane == 0) {
+          const bool none = strips == 0;   // a record of zero rows: nothing to align
+          p.out_score[pair] = ok ? (none ? 0.f : score) : __builtin_nanf("");
+          p.out_end[2 * pair] = ok ? (none ? -1 : lq - 1) : -2;
+          p.out_end[2 * pair + 1] = ok ? (none ? -1 : end_j) : -2;
+        }
+      }
+      continue;
+    }
 #pragma unroll
     for (int mask = 1; mask < 64; mask <<= 1) {
       const float ob = __shfl_xor(best, mask, 64);
@@ -427,6 +526,33 @@ int align_take_carry(const char* who, AlignArgs* p, void* ws, size_t ws_bytes) {
       ws_bytes / ((size_t)align_groups(p->P) * kAlignWaves * 2 * sizeof(AlignCarry<kSpan>));
   p->carry = ws;
   p->cap = (int)(columns < GFY_ALIGN_ROWS_MAX ? columns : GFY_ALIGN_ROWS_MAX);
+  return GFY_OK;
+}
+
+int64_t trace_region_words(int64_t max_box_rows, int64_t max_box_cols) {
+  return max_box_rows * ((max_box_cols + 7) / 8);
+}
+
+// a wave's part of a trace workspace: two carry buffers of max_box_cols (H, F) entries and the
+// direction words of the largest box
+size_t trace_wave_bytes(int64_t max_box_rows, int64_t max_box_cols) {
+  return align_up((size_t)2 * max_box_cols * sizeof(AlignCarry<false>) +
+                      (size_t)trace_region_words(max_box_rows, max_box_cols) * 4 + 1, 256);
+}
+
+// the caller's workspace cut into such parts: the check, then what the launcher's copies `p` and
+// `trace` of a trace call say about it
+int trace_take_workspace(const char* who, AlignArgs* p, TraceArgs* trace, int64_t max_box_rows,
+                         int64_t max_box_cols, void* ws, size_t ws_bytes) {
+  const size_t wave_bytes = trace_wave_bytes(max_box_rows, max_box_cols);
+  GFY_REQUIRE(ws_bytes >= wave_bytes, GFY_ERR_WORKSPACE,
+              "%s: workspace %zu < the %zu of one wave", who, ws_bytes, wave_bytes);
+  const size_t fit = ws_bytes / wave_bytes, waves = (size_t)align_groups(p->P) * kAlignWaves;
+  p->carry = ws;
+  p->cap = (int)max_box_cols;
+  trace->waves = (int64_t)(fit < waves ? fit : waves);
+  trace->wave_bytes = (int64_t)wave_bytes;
+  trace->region_words = trace_region_words(max_box_rows, max_box_cols);
   return GFY_OK;
 }
 

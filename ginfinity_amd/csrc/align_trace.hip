@@ -19,16 +19,6 @@ __global__ __launch_bounds__(kAlignThreads) void k_align_trace(const TraceKernel
   align_pairs<false, true>(p.align, nullptr, &p.trace);
 }
 
-int64_t trace_region_words(int64_t max_box_rows, int64_t max_box_cols) {
-  return max_box_rows * ((max_box_cols + 7) / 8);
-}
-
-// two carry buffers of max_box_cols (H, F) entries and the direction words of the largest box
-size_t trace_wave_bytes(int64_t max_box_rows, int64_t max_box_cols) {
-  return align_up((size_t)2 * max_box_cols * sizeof(AlignCarry<false>) +
-                      (size_t)trace_region_words(max_box_rows, max_box_cols) * 4 + 1, 256);
-}
-
 }  // namespace
 
 size_t align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols) {
@@ -37,16 +27,10 @@ size_t align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t 
 
 int launch_align_trace(const AlignArgs& call, const TraceArgs& trace, int64_t max_box_rows,
                        int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s) {
-  const size_t wave_bytes = trace_wave_bytes(max_box_rows, max_box_cols);
-  GFY_REQUIRE(ws_bytes >= wave_bytes, GFY_ERR_WORKSPACE,
-              "gfy_align_trace: workspace %zu < the %zu of one wave", ws_bytes, wave_bytes);
-  const size_t fit = ws_bytes / wave_bytes, waves = (size_t)align_groups(call.P) * kAlignWaves;
   TraceKernelArgs p{call, trace};
-  p.align.carry = ws;
-  p.align.cap = (int)max_box_cols;
-  p.trace.waves = (int64_t)(fit < waves ? fit : waves);
-  p.trace.wave_bytes = (int64_t)wave_bytes;
-  p.trace.region_words = trace_region_words(max_box_rows, max_box_cols);
+  if (const int rc = trace_take_workspace("gfy_align_trace", &p.align, &p.trace, max_box_rows,
+                                          max_box_cols, ws, ws_bytes))
+    return rc;
   // whole workgroups of the waves that have a part; the rest of the last one returns at once
   return align_launch<k_align_trace>(p, (int)((p.trace.waves + kAlignWaves - 1) / kAlignWaves), s);
 }

@@ -375,7 +375,7 @@ int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, 
                             hipStream_t s);
 size_t pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_b);
 int pairwise_record_chunks(int64_t n, int64_t m);
-// One alignment call (align_local.inc): what the three entry points of gfy_api.hip check and
+// One alignment call (align_local.inc): what the alignment entry points of gfy_api.hip check and
 // fill, the launchers complete (carry, cap) and the kernels read as their argument.
 struct AlignArgs {
   const f16* a;
@@ -395,7 +395,7 @@ struct AlignArgs {
 // what k_align_trace takes next to AlignArgs (whose out_score / out_end it leaves alone, and whose
 // carry is the whole workspace: per wave two carry buffers of cap entries, then the region)
 struct TraceArgs {
-  const int32_t* starts;   // [P][2]
+  const int32_t* starts;   // [P][2] (not read by k_align_global_trace)
   const int32_t* ends;     // [P][2]
   const int64_t* op_ptr;   // [P + 1]: pair p owns out_ops[op_ptr[p] .. op_ptr[p + 1])
   uint8_t* out_ops;
@@ -417,6 +417,16 @@ size_t align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
 int launch_align_trace(const AlignArgs& call, const TraceArgs& trace, int64_t max_box_rows,
                        int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
 size_t align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols);
+// align_global.hip: global alignment, with `within` query-in-target (a free top border); the
+// workspace is align_workspace_bytes
+int launch_align_global(const AlignArgs& call, int within, void* ws, size_t ws_bytes,
+                        hipStream_t s);
+// align_global_trace.hip: the aligned path of rows 0 .. L_q - 1 x columns 0 .. end_j; of `trace`
+// the caller sets ends, op_ptr, out_ops and out_len (starts is not read)
+int launch_align_global_trace(const AlignArgs& call, const TraceArgs& trace, int32_t* out_start,
+                              int within, int64_t max_rows_a, int64_t max_rows_b, void* ws,
+                              size_t ws_bytes, hipStream_t s);
+size_t align_global_trace_workspace_bytes(int64_t pairs, int64_t max_rows_a, int64_t max_rows_b);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS

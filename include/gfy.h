@@ -612,7 +612,8 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
  *   Limits      a record has at most GFY_ALIGN_ROWS_MAX rows; 0 <= gap_extend <= gap_open, the
  *               four parameters finite; 1 <= P < 2^31.  Rows holding inf / NaN give unspecified
  *               values.  The start cell is gfy_align_local_span's and the aligned path
- *               gfy_align_trace's; no banded or global alignment, no normalisation of scores.
+ *               gfy_align_trace's; global and query-in-target alignment are gfy_align_global's;
+ *               no banded alignment, no normalisation of scores.
  *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), max_rows_b the longest b-record any
  *               pair names: the last row of a 64-row strip of A, per wave in flight.
  *   ptr_a, ptr_b and pairs are device arrays, which the kernel only compares and clips.  A pair
@@ -662,8 +663,8 @@ int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
  *               (H, F, origin of H, origin of F), 16 bytes per column, twice gfy_align_local's.
  *   Arguments, clipping of what the device arrays hold and error codes are those of
  *   gfy_align_local; a NULL out_start is GFY_ERR_INVALID and named.
- *   The aligned path itself is gfy_align_trace's; no banded or global alignment, no
- *   normalisation of scores.                                                                  */
+ *   The aligned path itself is gfy_align_trace's; global alignment is gfy_align_global's; no
+ *   banded alignment, no normalisation of scores.                                             */
 size_t gfy_align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
 int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
@@ -740,6 +741,91 @@ int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
                     const int64_t* op_ptr /* [P + 1] */, uint8_t* out_ops, int32_t* out_len /* [P] */,
                     int64_t max_box_rows, int64_t max_box_cols,
                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* GLOBAL and QUERY-IN-TARGET alignment of record pairs: the recurrences of gfy_align_local with
+ * charged borders and without the 0 candidate.  within = 0 aligns both records end to end
+ * (Needleman-Wunsch with affine gaps): unrelated flanks are charged for, not ignored.  within = 1
+ * aligns ALL of the a-record inside the b-record ("fit"): the b-record's rows in front of and
+ * behind the alignment are free, so a window cannot silently take part with a piece of itself.
+ * A, B, C, s[i][j], the four parameters and their checks are gfy_align_local's; every + and - is
+ * one rounded fp32 operation, max is exact, nothing is contracted.
+ *   Recurrences E[i][j] = max(E[i][j-1] - gap_extend, H[i][j-1] - gap_open)
+ *               F[i][j] = max(F[i-1][j] - gap_extend, H[i-1][j] - gap_open)
+ *               H[i][j] = max(H[i-1][j-1] + s[i][j], E[i][j], F[i][j])           (no 0 candidate)
+ *   Borders     the same recurrences carried onto row -1 and column -1, so a border is an
+ *               ITERATED sum and not a closed form.  H[-1][-1] = 0.
+ *               Left, both modes:  F[i][-1] = max(F[i-1][-1] - gap_extend, H[i-1][-1] - gap_open),
+ *                        H[i][-1] = F[i][-1], E[i][-1] = -inf, with F[-1][-1] = -inf: H[0][-1] =
+ *                        fl32(0 - gap_open), H[i][-1] = fl32(H[i-1][-1] - gap_extend).
+ *               Top, within = 0:  the mirror image, H[-1][j] = E[-1][j] iterated along j and
+ *                        F[-1][j] = -inf.
+ *               Top, within = 1:  H[-1][j] = 0 and E[-1][j] = F[-1][j] = -inf for every j: the
+ *                        leading rows of B are free.
+ *   Result      within = 0: out_score = H[L_q-1][L_r-1], out_end = (L_q-1, L_r-1).
+ *               within = 1: out_score = max over 0 <= j < L_r of H[L_q-1][j], out_end = (L_q-1, j)
+ *               for the first such j.  Scores may be negative, and only a zero keeps no promise
+ *               of its sign.  A pair with a record of zero rows on either side is "nothing to
+ *               align": score 0, end (-1, -1) (and an empty path), as in the local mode, not the
+ *               cost of a gap.  A pair that is refused gets NaN and (-2, -2), as
+ *               gfy_align_local's: the same clipping of ptr_a, ptr_b and pairs, the same limits.
+ *   Ordering    every operation is monotone in its inputs and the modes differ only in
+ *               candidates added, so for any pair and parameters, exactly, in fp32 comparison:
+ *               score(within = 0) <= score(within = 1) <= gfy_align_local's score.
+ *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), used as gfy_align_local uses it.
+ *   Arguments and error codes are those of gfy_align_local; a within other than 0 or 1 is
+ *   GFY_ERR_INVALID.  Out of scope: banded alignment, free ends on the a-side, a span-only call
+ *   for these modes, normalisation of scores.
+ *   Cost: DESIGN.md §4.                                                                       */
+int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                     const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                     const int32_t* pairs /* [P][2] device */, int64_t P,
+                     float match_scale, float match_shift, float gap_open, float gap_extend,
+                     int within, float* out_score /* [P] */, int32_t* out_end /* [P][2] */,
+                     void* workspace, size_t workspace_bytes, void* stream);
+
+/* The aligned PATH of gfy_align_global.  ends (int32 [P][2], device memory) is what that call
+ * returned for the same a, b, pairs, parameters and within.
+ *   Walk        from H at end by the tie rules of gfy_align_trace: in H the diagonal first, then
+ *               E, then F; in E and F opening wins a tie.  Ops 0, 1 and 2 as there, reported in
+ *               FORWARD order.  There is no "starts here" rule: the walk ends on a border, which
+ *               it always reaches in H (a gap that meets a border opened there).
+ *               At (-1, -1) it stops.  At (i, -1) it emits i + 1 ops 2: the left border is a
+ *               charged gap.  At (-1, j) it emits j + 1 ops 1 with within = 0 and stops with
+ *               within = 1: those rows of B are free.
+ *   Result      out_ops[op_ptr[p] ..], out_len[p] of them, at most L_q + L_r (a path of gaps
+ *               alone; one more than the local bound).  out_start[p] = (first row of A consumed,
+ *               first row of B consumed): start_i = 0 always, start_j = 0 with within = 0, and
+ *               with within = 1 start_j = end_j + 1 - #(ops != 2), which is end_j + 1 where no row
+ *               of B is consumed.  The ops 0 and 2 number L_q, the ops 0 and 1 end_j + 1 -
+ *               start_j.  An end of (-1, -1) has out_len = 0 and start (-1, -1).  Re-scoring the
+ *               ops by the rule of gfy_align_trace (h = 0; ...) gives out_score bit for bit: this
+ *               is why the borders are iterated.
+ *   The box     rows 0 .. L_q - 1, columns 0 .. end_j.  Its top-left corner is the matrix's own, so
+ *               every value in it is the full matrix's by construction and no argument is needed.
+ *               4 direction bits per cell as gfy_align_trace keeps them (which candidate H took:
+ *               1, 2 or 3; 0 is unused).
+ *   Slots       op_ptr int64 [P + 1], device memory: pair p owns out_ops[op_ptr[p] ..
+ *               op_ptr[p + 1]), at least L_q + end_j + 1 bytes of it (L_q + L_r always serves).
+ *   Workspace   gfy_align_global_trace_workspace_bytes(pairs, max_rows_a, max_rows_b), cut and
+ *               accepted as gfy_align_trace's is, for boxes of up to max_rows_a x max_rows_b.
+ *   Refused     out_len[p] = -2, out_start[p] = (-2, -2) and nothing written to the slot: what
+ *               gfy_align_global refuses, an end other than (-1, -1) that it cannot have named
+ *               (end_i != L_q - 1, end_j outside the b-record, with within = 0 end_j != L_r - 1),
+ *               a box of more columns than max_rows_b or of more direction words than a wave's
+ *               region, a slot shorter than L_q + end_j + 1.
+ *   Arguments and error codes are those of gfy_align_trace, with ends, op_ptr, out_ops, out_len
+ *   and out_start named when NULL; a within other than 0 or 1 is GFY_ERR_INVALID.            */
+size_t gfy_align_global_trace_workspace_bytes(int64_t pairs, int64_t max_rows_a,
+                                              int64_t max_rows_b);
+int gfy_align_global_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                           const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                           const int32_t* pairs /* [P][2] device */, int64_t P,
+                           float match_scale, float match_shift, float gap_open, float gap_extend,
+                           int within, const int32_t* ends /* [P][2] */,
+                           const int64_t* op_ptr /* [P + 1] */, uint8_t* out_ops,
+                           int32_t* out_len /* [P] */, int32_t* out_start /* [P][2] */,
+                           int64_t max_rows_a, int64_t max_rows_b,
+                           void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

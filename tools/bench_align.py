@@ -24,8 +24,14 @@ alignments are a few cells long and the trace has next to nothing to do; the sam
 are therefore timed a second time on every record paired with ITSELF (``paths_self``), where the
 box is the whole matrix and the path its whole diagonal: the most a trace can be asked for.
 
+``--global`` and ``--within`` time ``align.global_align`` (``within=False`` / ``True``) after
+``local_align`` on the same pairs, and add ``global`` / ``within`` to the document: the seconds,
+pairs/s, cell updates/s and ``over_local_align``, the ratio of the two medians.  The loop is
+the local aligner's, so the ratio is information and no gate.
+
     python tools/bench_align.py --pairs 20000
     python tools/bench_align.py --pairs 20000 --spans
+    python tools/bench_align.py --pairs 20000 --global --within
     python tools/bench_align.py --pairs 20000 --paths
 """
 from __future__ import annotations
@@ -51,6 +57,7 @@ from ginfinity_amd import align, distance, synthetic  # noqa: E402
 KERNEL_SOURCE = "align_local.hip"
 SPAN_SOURCES = ("align_local.inc", "align_span.hip")     # --spans: the shared body and its kernel
 PATH_SOURCES = ("align_local.inc", "align_span.hip", "align_trace.hip")   # --paths
+GLOBAL_SOURCES = ("align_local.inc", "align_global.hip")                  # --global, --within
 
 
 def _commit() -> str | None:
@@ -133,6 +140,11 @@ def main() -> None:
     parser.add_argument("--paths", action="store_true",
                         help="time align.local_paths next to align.local_spans, on the pairs and "
                              "on every record with itself")
+    parser.add_argument("--global", dest="whole", action="store_true",
+                        help="time align.global_align (global alignment) after local_align")
+    parser.add_argument("--within", action="store_true",
+                        help="time align.global_align(within=True) (query-in-target) after "
+                             "local_align")
     parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
     parser.add_argument("--out", default=str(ROOT / "profiles" / "align_bench.json"))
     args = parser.parse_args()
@@ -180,6 +192,23 @@ def main() -> None:
             for name in SPAN_SOURCES}
         print(f"local_spans: {span_mid:.4f} s = {cells / span_mid:.3e} cell updates/s, "
               f"{span_mid / mid:.3f} x local_align", file=sys.stderr, flush=True)
+    for name, wanted, within in (("global", args.whole, False), ("within", args.within, True)):
+        if not wanted:
+            continue
+        mode_seconds = _timed(lambda: align.global_align(rows, counts_a=counts, pairs=pairs_dev,
+                                                         within=within, workspace=keeper,
+                                                         **parameters), args.repeats, args.warmup)
+        mode_mid = statistics.median(mode_seconds)
+        result[name] = {"call": f"align.global_align(within={within})",
+                        "seconds": _span(mode_seconds), "pairs_per_s": args.pairs / mode_mid,
+                        "cell_updates_per_s": cells / mode_mid,
+                        "over_local_align": mode_mid / mid}
+        result["global_source_sha256"] = {
+            source_name: hashlib.sha256((source.parent / source_name).read_bytes()).hexdigest()
+            for source_name in GLOBAL_SOURCES}
+        print(f"global_align(within={within}): {mode_mid:.4f} s = {args.pairs / mode_mid:.3e} "
+              f"pairs/s, {cells / mode_mid:.3e} cell updates/s, {mode_mid / mid:.3f} x local_align",
+              file=sys.stderr, flush=True)
     if args.paths:
         result["paths"] = _paths_against_spans(rows, counts, pairs, keeper, parameters,
                                                args.repeats, args.warmup)
