@@ -143,6 +143,14 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_align_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "gfy_align_trace": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                 c_int64, c_int64, c_void_p, c_size_t, c_void_p]),
+    # the local calls inside a band: `bands` (int32 [P][2], device) behind gap_extend
+    "gfy_align_local_band": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
+    "gfy_align_local_span_band": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
+    "gfy_align_trace_band": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t,
+                                     c_void_p]),
     "gfy_align_global": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
     "gfy_align_global_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),

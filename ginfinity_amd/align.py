@@ -113,11 +113,42 @@ row of B consumed): ``start_i`` is always 0, ``start_j`` is 0 for global and ``e
 start)`` gives the cells.  Re-scoring the ops by the rule above gives ``score`` bit for bit,
 which is why the borders are iterated.
 
+Alignment inside a band (seed and extend).  ``local_align``, ``local_spans`` and ``local_paths``
+take ``band``: per pair two integers ``(lo, hi)`` with ``lo <= hi``, diagonals ``d = j - i`` in
+the coordinates of the two records, both ends inclusive.  **The band is the matrix**: a cell
+whose diagonal lies outside ``[lo, hi]`` is outside the matrix in the sense above, ``H = 0``, ``E
+= F = -inf``, no origin.  Nothing else changes: the substitution scores, the recurrences, every
+rounded operation, the order that names ``end``, the origin rules, the tie rules of the walk and
+the op codes stay as they are.  "The best local alignment near this seed" is another question
+than the best one anywhere in the pair: eight seeds in one target get eight answers.  It
+follows that
+
+* a band that covers the matrix (``lo <= -(Lq - 1)`` and ``hi >= Lr - 1``) gives the results of
+  the call without a band bit for bit;
+* every operation is monotone and an outside cell holds the least values a cell can have, so
+  widening a band never lowers a pair's score, exactly, in float32 comparison;
+* a band that meets no cell of the matrix gives score 0, start and end ``(-1, -1)`` and an empty
+  path;
+* ``lo == hi`` is gapless extension along one diagonal;
+* the span property survives with the band shifted: the recurrences run on the box
+  ``start..end`` alone, under the band ``(lo - (start_j - start_i), hi - (start_j - start_i))``,
+  reach exactly ``score`` at the box's last cell, and the path is the walk inside that box; a
+  path cell always has a positive value, so the walk never leaves the band;
+* re-scoring the ops gives ``score`` bit for bit, as without a band.
+
+``band_around`` makes bands from seed cells, such as the hits of ``distance.topk``.  The device
+does not do the work outside the band: a strip of 64 rows from row ``i0`` holds band cells in the
+columns ``c_lo = max(0, i0 + lo) .. c_hi = min(Lr - 1, i0 + rows - 1 + hi)`` only, a strip
+without any is skipped, and a strip takes ``c_hi - (c_lo & ~31) + rows`` steps against ``Lr + rows
+- 1`` (arithmetic, not a measurement; two records of 4,096 rows and a band of 129 diagonals:
+about 290 steps per strip against about 4,160).
+
 Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIMUM_LENGTH_NT``),
-``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: banded alignment, a
-span-only kernel for the global and ``within`` modes, free ends on the a-side, a
-``device="cpu"`` path, and any z-score or normalisation of the scores.  Measured cost: DESIGN.md
-§4.
+``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: a band on the global
+and ``within`` modes (borders that leave the band, pairs with no admissible path at all),
+band-only storage of the direction words, a span-only kernel for the global and ``within`` modes,
+free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
+scores.  Measured cost: DESIGN.md §4.
 """
 from __future__ import annotations
 
@@ -165,6 +196,66 @@ def _checked_pairs(pairs, records_a: int, records_b: int) -> np.ndarray:
     return np.ascontiguousarray(pairs.astype(np.int32))
 
 
+def _checked_band(band, count: int) -> np.ndarray | None:
+    """``band`` as an int32 ``[count, 2]`` host array of ``(lo, hi)`` with ``lo <= hi``, clipped
+    into ``[-GFY_ALIGN_ROWS_MAX, GFY_ALIGN_ROWS_MAX]``; ``None`` stays ``None`` (no band)."""
+    if band is None:
+        return None
+    if isinstance(band, torch.Tensor):
+        band = band.detach().cpu().numpy()
+    elif isinstance(band, (tuple, list)) and any(isinstance(x, (bool, np.bool_)) for x in band):
+        raise ValueError("band must hold integers (lo, hi)")
+    band = np.asarray(band)
+    if band.size == 0 and count == 0 and band.ndim in (1, 2):
+        band = np.zeros((0, 2), dtype=np.int64)
+    if band.dtype.kind not in "iu":
+        raise ValueError("band must be an integer array of shape (P, 2) or one (lo, hi)")
+    if band.shape == (2,):
+        band = np.broadcast_to(band, (count, 2))
+    if band.ndim != 2 or band.shape != (count, 2):
+        raise ValueError(f"band must be one (lo, hi) or an integer array of shape (P, 2) = "
+                         f"({count}, 2), one (lo, hi) per pair")
+    if np.any(band[:, 0] > band[:, 1]):
+        bad = int(np.argmax(band[:, 0] > band[:, 1]))
+        raise ValueError(f"band of pair {bad} = ({int(band[bad, 0])}, {int(band[bad, 1])}): "
+                         "lo <= hi is required")
+    limit = native.GFY_ALIGN_ROWS_MAX
+    return np.ascontiguousarray(np.clip(band, -limit, limit).astype(np.int32))
+
+
+def band_around(seeds, half_width: int) -> np.ndarray:
+    """The bands of ``half_width`` diagonals on either side of seed cells: int32 ``[P, 2]`` of
+    ``(j - i - half_width, j - i + half_width)`` for ``seeds``, an integer ``[P, 2]`` array (numpy
+    or torch) of cells ``(i, j)`` inside the two records of each pair; ``half_width`` is a
+    non-negative integer, 0 the seed's diagonal alone.  A pure function of its arguments: no
+    device is needed.  A hit of ``distance.topk`` (row ``x`` of ``a``, row ``idx[x, k]`` of ``b``)
+    becomes a seed by taking away each record's first row:
+
+        q, r = distance.record_of(rows, counts_a), distance.record_of(idx[rows, k], counts_b)
+        seeds = stack([rows - cumsum(counts_a)[q] + counts_a[q],          # minus the record's
+                       idx[rows, k] - cumsum(counts_b)[r] + counts_b[r]], 1)    # first row
+        band = align.band_around(seeds, 64)            # with pairs=stack([q, r], 1)
+    """
+    if isinstance(half_width, (bool, np.bool_)) or \
+            not isinstance(half_width, (int, np.integer)) or half_width < 0:
+        raise ValueError("half_width must be a non-negative integer")
+    if isinstance(seeds, torch.Tensor):
+        seeds = seeds.detach().cpu().numpy()
+    seeds = np.asarray(seeds)
+    if seeds.size == 0 and seeds.ndim in (1, 2):
+        return np.zeros((0, 2), dtype=np.int32)
+    if seeds.ndim != 2 or seeds.shape[1] != 2 or seeds.dtype.kind not in "iu":
+        raise ValueError("seeds must be an integer array of shape (P, 2) of cells (i, j)")
+    seeds = seeds.astype(np.int64)
+    if seeds.min() < 0 or seeds.max() >= native.GFY_ALIGN_ROWS_MAX:
+        raise ValueError(f"seeds must be cells inside records: 0 <= i, j < "
+                         f"{native.GFY_ALIGN_ROWS_MAX}")
+    diagonal = seeds[:, 1] - seeds[:, 0]
+    limit = 2 * native.GFY_ALIGN_ROWS_MAX      # wider than any matrix: the values stay int32
+    width = min(int(half_width), limit)
+    return np.stack([diagonal - width, diagonal + width], axis=1).astype(np.int32)
+
+
 def _checked_parameter(value, name: str) -> float:
     if value is None:
         raise ValueError(f"{name} is required: it has no default")
@@ -179,7 +270,7 @@ def _checked_parameter(value, name: str) -> float:
 
 class _Call(NamedTuple):
     """A checked call: the rows (``b`` is ``a`` where it was omitted), the records and pairs on
-    both sides; ``on_device`` adds the device arrays."""
+    both sides and the band of every pair, or None; ``on_device`` adds the device arrays."""
     a: torch.Tensor
     b: torch.Tensor
     ptr_a: np.ndarray
@@ -190,6 +281,8 @@ class _Call(NamedTuple):
     ptr_a_dev: torch.Tensor | None = None
     ptr_b_dev: torch.Tensor | None = None
     pairs_dev: torch.Tensor | None = None
+    band: np.ndarray | None = None       # int32 [P, 2] of (lo, hi), clipped
+    band_dev: torch.Tensor | None = None
 
     @property
     def empty(self) -> bool:
@@ -206,17 +299,21 @@ class _Call(NamedTuple):
         return self._replace(a=a, b=b,
                              ptr_a_dev=torch.from_numpy(self.ptr_a.astype(np.int32)).to(a.device),
                              ptr_b_dev=torch.from_numpy(self.ptr_b.astype(np.int32)).to(a.device),
-                             pairs_dev=torch.from_numpy(self.pairs).to(a.device))
+                             pairs_dev=torch.from_numpy(self.pairs).to(a.device),
+                             band_dev=None if self.band is None
+                             else torch.from_numpy(self.band).to(a.device))
 
     def arguments(self) -> tuple:
-        """What every alignment call of the C ABI starts with."""
+        """What every alignment call of the C ABI starts with, and behind it the band where the
+        call has one (the ``*_band`` symbols)."""
+        band = () if self.band is None else (self.band_dev.data_ptr(),)
         return (self.a.data_ptr(), self.a.shape[0], self.ptr_a_dev.data_ptr(), self.ptr_a.size - 1,
                 self.b.data_ptr(), self.b.shape[0], self.ptr_b_dev.data_ptr(), self.ptr_b.size - 1,
-                self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters)
+                self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters, *band)
 
 
 def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-                  match_shift) -> _Call:
+                  match_shift, band=None) -> _Call:
     """Every check the alignment functions share: the call, or the ``ValueError``.  No device is
     touched."""
     gap_open = _checked_parameter(gap_open, "gap_open")
@@ -243,7 +340,8 @@ def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_s
             raise ValueError(f"pair {bad}: record {int(pairs[bad, column])} of {side} has "
                              f"{int(rows[bad])} rows, more than {native.GFY_ALIGN_ROWS_MAX}")
     return _Call(a, b, ptr_a, ptr_b, pairs, rows_b,
-                 (match_scale, match_shift, gap_open, gap_extend))
+                 (match_scale, match_shift, gap_open, gap_extend),
+                 band=_checked_band(band, pairs.shape[0]))
 
 
 def _launch(call: _Call, span: bool, workspace) -> tuple:
@@ -259,6 +357,7 @@ def _launch(call: _Call, span: bool, workspace) -> tuple:
         if not call.empty:
             lib = native.library()
             name = "gfy_align_local_span" if span else "gfy_align_local"
+            name += "_band" if call.band is not None else ""
             sizer = lib.gfy_align_span_workspace_bytes if span else lib.gfy_align_workspace_bytes
             need = sizer(count, int(call.rows_b.max()))
             scratch = (workspace or AlignWorkspace()).buffer(device, need)
@@ -269,8 +368,8 @@ def _launch(call: _Call, span: bool, workspace) -> tuple:
 
 
 def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None
-                ) -> tuple[torch.Tensor, torch.Tensor]:
+                match_scale=1.0, match_shift=0.0, band=None,
+                workspace: AlignWorkspace | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Local alignment of the record pairs ``pairs``: ``(scores float32 [P], ends int32 [P, 2])``
     on the device, exact, the ``Lq x Lr`` matrix of a pair never written (the definition is at
     the head of this module; it is this project's own and not ``ginfinity-sw``'s).
@@ -285,15 +384,23 @@ def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     cost of a gap's first position) and ``gap_extend`` are required, ``0 <= gap_extend <=
     gap_open``.
 
+    ``band=None`` aligns in the whole matrix.  Otherwise ``band`` is an integer array ``[P, 2]``
+    (numpy or torch, on any device) of ``(lo, hi)`` per pair, or one ``(lo, hi)`` for every pair:
+    only cells on the diagonals ``lo <= j - i <= hi`` exist (the head of this module says what
+    that means, ``band_around`` makes bands from seeds), and the columns of a strip outside the
+    band cost nothing.  Values are clipped into ``+-GFY_ALIGN_ROWS_MAX``, which covers any matrix.
+
     Every argument error is a ``ValueError`` before a device is touched: a pair out of range, a
     record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
-    finite or out of order.  ``P == 0`` returns empty tensors without a launch."""
+    finite or out of order, a band that is not integer, of another shape, or with ``lo > hi``.
+    ``P == 0`` returns empty tensors without a launch."""
     return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                 match_scale, match_shift).on_device(), False, workspace)
+                                 match_scale, match_shift, band).on_device(), False, workspace)
 
 
 def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None
+                match_scale=1.0, match_shift=0.0, band=None,
+                workspace: AlignWorkspace | None = None
                 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``local_align`` with the start cell of every alignment: ``(scores float32 [P], starts
     int32 [P, 2], ends int32 [P, 2])`` on the device.  Rows ``starts[p, 0] .. ends[p, 0]`` of the
@@ -301,10 +408,11 @@ def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     (the origin rules are at the head of this module).  Scores and ends are those of
     ``local_align`` bit for bit; a score of 0 gives a start of ``(-1, -1)``.
 
-    The arguments, their checks and the ``ValueError``s are those of ``local_align``; an
-    ``AlignWorkspace`` serves both functions (this one needs twice the bytes)."""
+    The arguments (``band`` among them), their checks and the ``ValueError``s are those of
+    ``local_align``; an ``AlignWorkspace`` serves both functions (this one needs twice the
+    bytes)."""
     return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                 match_scale, match_shift).on_device(), True, workspace)
+                                 match_scale, match_shift, band).on_device(), True, workspace)
 
 
 class AlignedPaths(NamedTuple):
@@ -318,7 +426,8 @@ class AlignedPaths(NamedTuple):
 
 
 def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                match_scale=1.0, match_shift=0.0, workspace: AlignWorkspace | None = None,
+                match_scale=1.0, match_shift=0.0, band=None,
+                workspace: AlignWorkspace | None = None,
                 max_workspace_bytes: int = 2 << 30) -> AlignedPaths:
     """``local_spans`` with the aligned path of every pair: ``AlignedPaths(scores, starts, ends,
     ops, offsets)`` on the device.  ``ops`` (uint8, all pairs one after the other) holds each
@@ -337,12 +446,13 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     the worst case, and still a wave per compute unit.  A ``max_workspace_bytes`` below one wave's
     need for the largest box of the call is refused by the library (``NativeLibraryError``).
 
-    The other arguments, their checks and the ``ValueError``s are those of ``local_spans``; an
-    ``AlignWorkspace`` serves all three functions.  ``P == 0``, or a call with no rows, returns
+    The other arguments, their checks and the ``ValueError``s are those of ``local_spans``;
+    with a ``band`` both launches get the same array (the trace shifts it into each box itself).
+    An ``AlignWorkspace`` serves all three functions.  ``P == 0``, or a call with no rows, returns
     empty tensors without a launch."""
     max_workspace_bytes = _checked_cap(max_workspace_bytes)
     call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-                         match_shift).on_device()
+                         match_shift, band).on_device()
     scores, starts, ends = _launch(call, True, workspace)
     device, count = scores.device, scores.shape[0]
     with torch.cuda.device(device):
@@ -362,12 +472,13 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
         slot_ptr_dev = torch.from_numpy(slot_ptr).to(device)
         slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
         lengths = torch.zeros(count, dtype=torch.int32, device=device)
-        native.check(lib.gfy_align_trace(
+        name = "gfy_align_trace" if call.band is None else "gfy_align_trace_band"
+        native.check(getattr(lib, name)(
             *call.arguments(), starts.data_ptr(), ends.data_ptr(), slot_ptr_dev.data_ptr(),
             slot_ops.data_ptr(), lengths.data_ptr(), box_rows, box_cols, scratch.data_ptr(), need,
-            torch.cuda.current_stream(device).cuda_stream), "gfy_align_trace")
+            torch.cuda.current_stream(device).cuda_stream), name)
         if bool((lengths < 0).any()):
-            raise native.NativeLibraryError("gfy_align_trace refused a box of gfy_align_local_span")
+            raise native.NativeLibraryError(f"{name} refused a box of its span call")
         return AlignedPaths(scores, starts, ends,
                             *_compacted(slot_ops, slot_ptr_dev, slots, lengths))
 
@@ -536,4 +647,4 @@ def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
 
 
 __all__ = ["local_align", "local_spans", "local_paths", "global_align", "global_paths",
-           "path_cells", "AlignedPaths", "AlignWorkspace", "top_pairs"]
+           "path_cells", "AlignedPaths", "AlignWorkspace", "top_pairs", "band_around"]

@@ -1,7 +1,8 @@
 // The one alignment loop of the library (semantics: include/gfy.h), shared by k_align_local
 // (align_local.hip, kSpan = false: score and end), k_align_span (align_span.hip, kSpan = true:
 // score, start and end) and k_align_trace (align_trace.hip, kTrace = true: the aligned path of a
-// given box), as pairwise_topk.inc is shared by the top-k family.
+// given box), their three twins inside a band of diagonals (align_band.hip, kBand = true) and the
+// two global kernels (kGlobal = true), as pairwise_topk.inc is shared by the top-k family.
 //
 // One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
 // wave takes pairs wave, wave + waves of the grid, ... until the list ends.
@@ -54,6 +55,40 @@
 //     anything.  With kTrace the box is rows 0 .. Lq - 1 and columns 0 .. end_j, whose top-left
 //     corner is the matrix's own; the walk has no "starts here", leaves the box over a border and
 //     the lanes add the border's ops behind it.  With kGlobal = false none of it exists.
+//   * kBand (not with kGlobal): the pair has a band (lo, hi) of diagonals d = j - i, both ends
+//     inclusive, read wave-uniformly from `bands` like the pair itself and clipped into
+//     +-GFY_ALIGN_ROWS_MAX; lo > hi is refused like a pair out of range.  A cell outside the band
+//     is outside the matrix (H = 0, E = F = -inf, no origin), and the work outside it is NOT
+//     DONE: a strip of rows i0 .. i0 + rows - 1 holds band cells in the one column range c_lo =
+//     max(0, i0 + lo) .. c_hi = min(lr - 1, i0 + rows - 1 + hi).  A strip with c_lo > c_hi is
+//     skipped whole (no staging of its a-rows, no multiply) and the strip loop ends once i0 + lo
+//     is past the last column; the step loop runs t from c_lo & ~31 to c_hi + rows - 1, which is
+//     c_hi - (c_lo & ~31) + rows steps against lr + rows - 1; b-rows are loaded from c_lo & ~31
+//     on and 32-column blocks are staged and multiplied only while t0 <= c_hi.  The ring needs
+//     no change: its slot (t & 127) and the staging quarter ((t0 >> 5) + 3) & 3 depend on t0
+//     modulo 128 alone and every block still starts at a multiple of 32, so a block writes the
+//     three quarters in front of its own start and stages in the fourth, whatever the first
+//     block was; at the first block nothing is in flight and every quarter is free.
+//     Where a band can go wrong in this loop, and what is done about it:
+//       - a lane's registers are what its neighbours read.  A cell in the matrix but outside the
+//         band sets h = 0, e = f = -inf instead of keeping the lane's registers; otherwise lane
+//         l + 1 would take the last band cell of lane l for "the row above" when that row has
+//         already left the band at hi.
+//       - diag (and its origin) follows up_h on every step in the matrix, in the band or not;
+//         otherwise a lane's first band cell at d == lo would find a stale diagonal predecessor,
+//         which lies on the same diagonal and hence in the band.  Lane 0 has no step in front of
+//         a start c_lo & ~31 > 0, so it takes its first diagonal predecessor, column (c_lo & ~31)
+//         - 1 of the row above, from the carry.
+//       - lane 63 stores only live cells, so load_carry (and that first diagonal) substitutes
+//         the outside entry for every column c with c - (i0 - 1) outside [lo, hi], per lane and
+//         without reading memory; that also covers a predecessor strip that was skipped.
+//       - kTrace: a row's band may begin and end inside an 8-column direction word, so the word
+//         is also stored at the row's last band cell (d == hi).  A word that is never written
+//         is never walked (a path cell is positive, hence in the band); the 64-lane window load
+//         may read it, inside the wave's own region.  The trace takes the band in the records'
+//         coordinates and shifts it by start_j - start_i itself; a box whose last cell lies
+//         outside the band has no path.  The region stays sized for the whole box.
+//     With kBand = false none of it exists.
 // ptr_a, ptr_b and pairs are device arrays: they are compared and clipped, a pair outside them or
 // longer than the limits gets NaN and (-2, -2), and nothing outside the caller's buffers is read.
 #pragma once
@@ -105,13 +140,14 @@ __device__ __forceinline__ void record_rows(const int32_t* ptr, int index, int64
 }
 
 // out_start ([P][2]) is written with kSpan, and with kTrace and kGlobal together; trace is read
-// with kTrace alone, within (wave-uniform) with kGlobal alone
-template <bool kSpan, bool kTrace = false, bool kGlobal = false>
+// with kTrace alone, within (wave-uniform) with kGlobal alone, p.bands with kBand alone
+template <bool kSpan, bool kTrace = false, bool kGlobal = false, bool kBand = false>
 __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start,
                                             const TraceArgs* trace = nullptr,
                                             bool within = false) {
   static_assert(!(kSpan && kTrace), "the trace runs on the plain (H, F) carry");
   static_assert(!(kSpan && kGlobal), "a global alignment starts at the matrix's corner");
+  static_assert(!(kBand && kGlobal), "a band on the global modes: borders that leave the band");
   using Carry = AlignCarry<kSpan>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;
@@ -140,6 +176,14 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
     const int rec = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair + 1]);
     bool ok = (uint32_t)q < (uint32_t)p.records_a && (uint32_t)rec < (uint32_t)p.records_b;
     int64_t a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;
+    int lo = 0, hi = 0;   // kBand: the band, from here on clipped
+    if constexpr (kBand) {
+      lo = __builtin_amdgcn_readfirstlane(p.bands[2 * pair]);
+      hi = __builtin_amdgcn_readfirstlane(p.bands[2 * pair + 1]);
+      ok = ok && lo <= hi;
+      lo = lo < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : lo > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : lo;
+      hi = hi < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : hi > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : hi;
+    }
     if (ok) {
       record_rows(p.ptr_a, q, p.n, a_lo, a_hi);
       record_rows(p.ptr_b, rec, p.m, b_lo, b_hi);
@@ -181,6 +225,10 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       box = box && box_cols <= p.cap && box_rows * ((box_cols + 7) >> 3) <= trace->region_words &&
             op_lo >= 0 && op_hi - op_lo >= box_rows + box_cols - 1;
       ok = ok && (none || box);
+      if constexpr (kBand) {   // the band in the box's coordinates
+        lo -= box ? sj - si : 0;
+        hi -= box ? sj - si : 0;
+      }
       a_lo += box ? si : 0;
       b_lo += box ? sj : 0;
       a_hi = a_lo + (box ? box_rows : 0);
@@ -215,6 +263,14 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       const int i0 = strip * kStrip;
       const int rows = lq - i0 < kStrip ? lq - i0 : kStrip;
       const bool onward = strip + 1 < strips;   // lane 63's row feeds another strip
+      int c_lo = 0, c_hi = lr - 1;              // kBand: the columns that hold the strip's band cells
+      if constexpr (kBand) {
+        c_lo = i0 + lo > 0 ? i0 + lo : 0;
+        c_hi = i0 + rows - 1 + hi < lr - 1 ? i0 + rows - 1 + hi : lr - 1;
+        if (i0 + lo > lr - 1) break;   // the band has left the matrix below
+        if (c_lo > c_hi) continue;     // not yet in it
+      }
+      const int t_first = kBand ? c_lo & ~(kSub - 1) : 0;
       const Carry* carry_in = carry + (size_t)((strip + 1) & 1) * p.cap;
       Carry* carry_out = carry + (size_t)(strip & 1) * p.cap;
 
@@ -257,13 +313,20 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       uint32_t o_h = 0, o_e = 0, o_f = 0, o_diag = 0;   // kSpan: their origins
       uint32_t dir_word = 0;                            // kTrace: the row's 8 columns in the making
       f16x8 b_next[8];
-      load_b(b_next, 0);
+      load_b(b_next, t_first);
       // the carry entries of the row above the strip for columns c0 + lane, lanes 0..31
       auto load_carry = [&](int c0) __attribute__((always_inline)) {
         Carry v;
         if constexpr (kSpan) v = Carry{__float_as_uint(0.f), __float_as_uint(minus_inf), 0u, 0u};
         else v = make_float2(0.f, minus_inf);
-        if (strip > 0 && lane < kSub && c0 + lane < lr) v = carry_in[c0 + lane];
+        if constexpr (kBand) {
+          // lane 63 stored the live cells alone: what is outside the band of row i0 - 1 is outside
+          if (strip > 0 && lane < kSub && c0 + lane < lr &&
+              (uint32_t)(c0 + lane - (i0 - 1) - lo) <= (uint32_t)(hi - lo))
+            v = carry_in[c0 + lane];
+        } else {
+          if (strip > 0 && lane < kSub && c0 + lane < lr) v = carry_in[c0 + lane];
+        }
         if constexpr (kGlobal) {
           // the top border, iterated like the left one (F stays -inf); within: the rows of B in
           // front of the alignment are free, H = 0
@@ -277,11 +340,20 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
         }
         return v;
       };
-      Carry carry_next = load_carry(0);
+      Carry carry_next = load_carry(t_first);
+      if constexpr (kBand) {
+        // lane 0's first diagonal predecessor, (i0 - 1, t_first - 1): no step brings it
+        if (strip > 0 && t_first > 0 && lane == 0 &&
+            (uint32_t)(t_first - 1 - (i0 - 1) - lo) <= (uint32_t)(hi - lo)) {
+          const Carry v = carry_in[t_first - 1];
+          if constexpr (kSpan) diag = __uint_as_float(v.x), o_diag = v.z;
+          else diag = v.x;
+        }
+      }
 
-      const int steps = lr + rows - 1;
-      for (int t0 = 0; t0 < steps; t0 += kSub) {
-        if (t0 < lr) {   // columns t0 .. t0 + 31 join the ring
+      const int steps = kBand ? c_hi + rows : lr + rows - 1;   // the step behind the last one
+      for (int t0 = t_first; t0 < steps; t0 += kSub) {
+        if (kBand ? t0 <= c_hi : t0 < lr) {   // columns t0 .. t0 + 31 join the ring
           char* stage = ring + (((t0 >> 5) + 3) & 3) * (kSub * 256);
 #pragma unroll
           for (int x = 0; x < 8; ++x) {
@@ -293,7 +365,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           wave_sync();
           f32x16 acc[2];
           sweep_multiply<2, false>(acc, af, stage, 0, 0, r, hq);
-          if (t0 + kSub < lr) load_b(b_next, t0 + kSub);
+          if (kBand ? t0 + kSub <= c_hi : t0 + kSub < lr) load_b(b_next, t0 + kSub);
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int jl = 4 * hq + 8 * g;   // 4 consecutive b-rows
@@ -327,7 +399,9 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           }
           if (lane == 0) up_h = above_h, up_f = above_f;
           const float s = ring_f[(t & 127) * kStrip + lane];
-          const bool live = (uint32_t)j < (uint32_t)lr && lane < rows;
+          const bool inside = (uint32_t)j < (uint32_t)lr && lane < rows;   // in the matrix
+          bool live = inside;
+          if constexpr (kBand) live = inside && (uint32_t)(j - (i0 + lane) - lo) <= (uint32_t)(hi - lo);
           const float e_ext = e - ge, e_open = h - go;
           const float f_ext = up_f - ge, f_open = up_h - go;
           const float match = diag + s;
@@ -354,7 +428,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
             o_e = live ? oe_new : o_e;
             o_f = live ? of_new : o_f;
             o_h = live ? o_new : o_h;
-            o_diag = live ? up_oh : o_diag;
+            o_diag = inside ? up_oh : o_diag;
           }
           if constexpr (kTrace) {
             // the same selections as kSpan's, kept as bits: diagonal, then E, then F; opening
@@ -365,14 +439,21 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
             const uint32_t bits = how | (e_open >= e_ext ? 4u : 0u) | (f_open >= f_ext ? 8u : 0u);
             if (live) {
               dir_word = (j & 7) == 0 ? bits : dir_word | (bits << (4 * (j & 7)));
-              if ((j & 7) == 7 || j == lr - 1)
+              if ((j & 7) == 7 || j == lr - 1 || (kBand && j - (i0 + lane) == hi))
                 dir[(size_t)(i0 + lane) * dir_pitch + (j >> 3)] = dir_word;
             }
           }
-          e = live ? e_new : e;
-          f = live ? f_new : f;
-          h = live ? h_new : h;
-          diag = live ? up_h : diag;
+          if constexpr (kBand) {
+            // in the matrix, outside the band: the outside values, for the neighbours to read
+            e = live ? e_new : inside ? minus_inf : e;
+            f = live ? f_new : inside ? minus_inf : f;
+            h = live ? h_new : inside ? 0.f : h;
+          } else {
+            e = live ? e_new : e;
+            f = live ? f_new : f;
+            h = live ? h_new : h;
+          }
+          diag = inside ? up_h : diag;
           const bool better = live && (!kGlobal || tracks) && h_new > best;
           best = better ? h_new : best;
           best_i = better ? i0 + lane : best_i;
@@ -398,7 +479,9 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       // H of the box's last cell is the last H of the lane that owns its row
       int start_j = 0;   // kGlobal: the first row of B the path consumes
       // (kGlobal: any H is walked back from, and a path that is all gaps has Lq + Lr ops)
-      if (strips > 0 && (kGlobal || lane_value(h_last, (lq - 1) & (kStrip - 1)) > 0.f)) {
+      bool corner = strips > 0;   // the box's last cell exists (kBand: and lies in the band)
+      if constexpr (kBand) corner = corner && (uint32_t)(lr - lq - lo) <= (uint32_t)(hi - lo);
+      if (corner && (kGlobal || lane_value(h_last, (lq - 1) & (kStrip - 1)) > 0.f)) {
         uint8_t* reversed = reinterpret_cast<uint8_t*>(ring);   // <= 8192 ops of a byte
         const int limit = lq + lr - (kGlobal ? 0 : 1);
         int i = lq - 1, j = lr - 1, state = 0;   // 0 in H, 1 in E, 2 in F

@@ -1305,6 +1305,91 @@ int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
                             clipped_align_rows(max_box_cols), ws, ws_bytes, (hipStream_t)stream);
 }
 
+// The three local calls inside a band per pair: their counterpart's checks in its order, with
+// `bands` named first, and the banded kernels (align_band.hip).
+#define GFY_REQUIRE_BANDS(who, plain)                                                         \
+  GFY_REQUIRE(bands, GFY_ERR_INVALID,                                                         \
+              who ": bands is NULL (int32 [P][2] of (lo, hi) diagonals in device memory; " plain \
+              " is the call without a band)")
+
+int gfy_align_local_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                         float gap_open, float gap_extend, const int32_t* bands, float* out_score,
+                         int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  GFY_REQUIRE_BANDS("gfy_align_local_band", "gfy_align_local");
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_local_band",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
+    return rc;
+  call.bands = bands;
+  call.out_score = out_score;
+  call.out_end = out_end;
+  return launch_align_local_band(call, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_align_local_span_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                              const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                              const int32_t* pairs, int64_t P, float match_scale,
+                              float match_shift, float gap_open, float gap_extend,
+                              const int32_t* bands, float* out_score, int32_t* out_start,
+                              int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  GFY_REQUIRE_BANDS("gfy_align_local_span_band", "gfy_align_local_span");
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_local_span_band",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{out_score, "out_score"}, {out_start, "out_start"}, {out_end, "out_end"}}, ws, &call))
+    return rc;
+  call.bands = bands;
+  call.out_score = out_score;
+  call.out_end = out_end;
+  return launch_align_local_span_band(call, out_start, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_align_trace_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                         float gap_open, float gap_extend, const int32_t* bands,
+                         const int32_t* starts, const int32_t* ends, const int64_t* op_ptr,
+                         uint8_t* out_ops, int32_t* out_len, int64_t max_box_rows,
+                         int64_t max_box_cols, void* ws, size_t ws_bytes, void* stream) {
+  clear_error();
+  GFY_REQUIRE_BANDS("gfy_align_trace_band", "gfy_align_trace");
+  GFY_REQUIRE(starts, GFY_ERR_INVALID, "gfy_align_trace_band: starts is NULL");
+  GFY_REQUIRE(ends, GFY_ERR_INVALID, "gfy_align_trace_band: ends is NULL");
+  GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_trace_band: op_ptr is NULL");
+  GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_trace_band: out_ops is NULL");
+  GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_trace_band: out_len is NULL");
+  AlignArgs call;   // the pointers are named above: no output is left to the shared check
+  if (const int rc = checked_align_call(
+          "gfy_align_trace_band",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {}, ws, &call))
+    return rc;
+  GFY_REQUIRE(max_box_rows >= 0 && max_box_cols >= 0, GFY_ERR_INVALID,
+              "gfy_align_trace_band: max_box_rows = %lld, max_box_cols = %lld are negative",
+              (long long)max_box_rows, (long long)max_box_cols);
+  call.bands = bands;
+  TraceArgs trace{};
+  trace.starts = starts;
+  trace.ends = ends;
+  trace.op_ptr = op_ptr;
+  trace.out_ops = out_ops;
+  trace.out_len = out_len;
+  return launch_align_trace_band(call, trace, clipped_align_rows(max_box_rows),
+                                 clipped_align_rows(max_box_cols), ws, ws_bytes,
+                                 (hipStream_t)stream);
+}
+#undef GFY_REQUIRE_BANDS
+
 int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                      const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                      const int32_t* pairs, int64_t P, float match_scale, float match_shift,

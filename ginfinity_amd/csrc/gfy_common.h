@@ -390,6 +390,7 @@ struct AlignArgs {
   int32_t* out_end;       // [P][2]
   void* carry;            // [waves of the grid][2][cap] entries of a strip's last row
   int cap;                // columns a carry buffer holds
+  const int32_t* bands;   // [P][2] (lo, hi) diagonals j - i per pair: the *_band kernels alone
 };
 
 // what k_align_trace takes next to AlignArgs (whose out_score / out_end it leaves alone, and whose
@@ -427,6 +428,13 @@ int launch_align_global_trace(const AlignArgs& call, const TraceArgs& trace, int
                               int within, int64_t max_rows_a, int64_t max_rows_b, void* ws,
                               size_t ws_bytes, hipStream_t s);
 size_t align_global_trace_workspace_bytes(int64_t pairs, int64_t max_rows_a, int64_t max_rows_b);
+// align_band.hip: the three local calls inside a band of diagonals per pair (call.bands); the
+// workspaces are those of the unbanded calls
+int launch_align_local_band(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_align_local_span_band(const AlignArgs& call, int32_t* out_start, void* ws,
+                                 size_t ws_bytes, hipStream_t s);
+int launch_align_trace_band(const AlignArgs& call, const TraceArgs& trace, int64_t max_box_rows,
+                            int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS

@@ -613,7 +613,8 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
  *               four parameters finite; 1 <= P < 2^31.  Rows holding inf / NaN give unspecified
  *               values.  The start cell is gfy_align_local_span's and the aligned path
  *               gfy_align_trace's; global and query-in-target alignment are gfy_align_global's;
- *               no banded alignment, no normalisation of scores.
+ *               alignment inside a band of diagonals is gfy_align_local_band's; no normalisation
+ *               of scores.
  *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), max_rows_b the longest b-record any
  *               pair names: the last row of a 64-row strip of A, per wave in flight.
  *   ptr_a, ptr_b and pairs are device arrays, which the kernel only compares and clips.  A pair
@@ -663,8 +664,8 @@ int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
  *               (H, F, origin of H, origin of F), 16 bytes per column, twice gfy_align_local's.
  *   Arguments, clipping of what the device arrays hold and error codes are those of
  *   gfy_align_local; a NULL out_start is GFY_ERR_INVALID and named.
- *   The aligned path itself is gfy_align_trace's; global alignment is gfy_align_global's; no
- *   banded alignment, no normalisation of scores.                                             */
+ *   The aligned path itself is gfy_align_trace's; global alignment is gfy_align_global's; a band
+ *   is gfy_align_local_span_band's; no normalisation of scores.                               */
 size_t gfy_align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
 int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
@@ -742,6 +743,75 @@ int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
                     int64_t max_box_rows, int64_t max_box_cols,
                     void* workspace, size_t workspace_bytes, void* stream);
 
+/* Local alignment INSIDE A BAND of diagonals per pair (seed and extend): gfy_align_local,
+ * gfy_align_local_span and gfy_align_trace with `bands` (int32 [P][2], device memory) behind
+ * gap_extend.  A seed hit (i, j) of a nearest-row search says on which diagonal j - i the common
+ * stretch lies; a band around it asks for the best local alignment NEAR THAT SEED, which is
+ * another question than the best one anywhere in the pair, and costs the band's cells only.
+ *   Band        bands[p] = (lo, hi), lo <= hi: diagonals d = j - i in the coordinates of the two
+ *               records, both ends inclusive.  THE BAND IS THE MATRIX: a cell whose diagonal lies
+ *               outside [lo, hi] is outside the matrix in the sense of gfy_align_local, H = 0, E =
+ *               F = -inf, no origin.  Nothing else changes: s[i][j], the recurrences, every
+ *               rounded operation, the order that names out_end, the origin rules, the tie rules
+ *               of the walk and the op codes are those of the calls without a band.
+ *   It follows  - a band that covers the matrix (lo <= -(L_q - 1) and hi >= L_r - 1) gives the
+ *                 results of the call without a band, bit for bit.
+ *               - every operation is monotone and an outside cell holds the least values a cell
+ *                 can have, so widening a band never lowers a pair's score, exactly, in fp32
+ *                 comparison.
+ *               - a band that meets no cell of the matrix gives score 0, start and end (-1, -1)
+ *                 and out_len 0.
+ *               - lo == hi is gapless extension along one diagonal.
+ *               - the span property holds with the band shifted: the recurrences run on the box
+ *                 start..end alone, under the band (lo - (start_j - start_i), hi - (start_j -
+ *                 start_i)), reach exactly out_score at the box's last cell (the argument of
+ *                 gfy_align_trace: what the box lacks counts as 0 or -inf, as what the band
+ *                 lacks does).  The path is the walk inside that box; a path cell has a positive
+ *                 value, so the walk never leaves the band.
+ *               - re-scoring the ops gives out_score bit for bit, as without a band.
+ *   Clipping    the kernel reads lo and hi per pair like the pair itself and clips them into
+ *               [-GFY_ALIGN_ROWS_MAX, GFY_ALIGN_ROWS_MAX], which covers any matrix.  A pair with
+ *               lo > hi is refused like a pair out of range: NaN, (-2, -2), out_len -2.
+ *   Trace       gfy_align_trace_band takes the SAME bands as the span call, in the records'
+ *               coordinates, and shifts each into its box itself.  A box whose last cell lies
+ *               outside the band has out_len 0.
+ *   Work        what lies outside the band is not done, not masked: of a 64-row strip from row
+ *               i0, only the columns c_lo = max(0, i0 + lo) .. c_hi = min(L_r - 1, i0 + rows - 1 +
+ *               hi) are loaded, multiplied and stepped over, c_hi - (c_lo & ~31) + rows steps
+ *               against L_r + rows - 1, and a strip without a band cell is skipped (arithmetic
+ *               from the loop bounds; no time is claimed).
+ *   Workspace   the sizers, the cut and the acceptance of the calls without a band; the trace's
+ *               region stays sized for the whole box.
+ *   Arguments, checks and error codes are those of the counterpart; a NULL bands is
+ *   GFY_ERR_INVALID, named, with a pointer to the call without a band.  Out of scope: a band on
+ *   gfy_align_global and gfy_align_global_trace (borders that leave the band, pairs with no
+ *   admissible path), band-only storage of the direction words.
+ *   Cost: not measured.                                                                       */
+int gfy_align_local_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs /* [P][2] device */, int64_t P,
+                         float match_scale, float match_shift, float gap_open, float gap_extend,
+                         const int32_t* bands /* [P][2] device */,
+                         float* out_score /* [P] */, int32_t* out_end /* [P][2] */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int gfy_align_local_span_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                              const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                              const int32_t* pairs /* [P][2] device */, int64_t P,
+                              float match_scale, float match_shift, float gap_open,
+                              float gap_extend, const int32_t* bands /* [P][2] device */,
+                              float* out_score /* [P] */, int32_t* out_start /* [P][2] */,
+                              int32_t* out_end /* [P][2] */,
+                              void* workspace, size_t workspace_bytes, void* stream);
+int gfy_align_trace_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs /* [P][2] device */, int64_t P,
+                         float match_scale, float match_shift, float gap_open, float gap_extend,
+                         const int32_t* bands /* [P][2] device */,
+                         const int32_t* starts /* [P][2] */, const int32_t* ends /* [P][2] */,
+                         const int64_t* op_ptr /* [P + 1] */, uint8_t* out_ops,
+                         int32_t* out_len /* [P] */, int64_t max_box_rows, int64_t max_box_cols,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* GLOBAL and QUERY-IN-TARGET alignment of record pairs: the recurrences of gfy_align_local with
  * charged borders and without the 0 candidate.  within = 0 aligns both records end to end
  * (Needleman-Wunsch with affine gaps): unrelated flanks are charged for, not ignored.  within = 1
@@ -773,8 +843,8 @@ int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
  *               score(within = 0) <= score(within = 1) <= gfy_align_local's score.
  *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), used as gfy_align_local uses it.
  *   Arguments and error codes are those of gfy_align_local; a within other than 0 or 1 is
- *   GFY_ERR_INVALID.  Out of scope: banded alignment, free ends on the a-side, a span-only call
- *   for these modes, normalisation of scores.
+ *   GFY_ERR_INVALID.  Out of scope: a band on these modes (the gfy_align_*_band calls are local
+ *   only), free ends on the a-side, a span-only call for these modes, normalisation of scores.
  *   Cost: DESIGN.md §4.                                                                       */
 int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                      const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,

@@ -29,8 +29,18 @@ box is the whole matrix and the path its whole diagonal: the most a trace can be
 pairs/s, cell updates/s and ``over_local_align``, the ratio of the two medians.  The loop is
 the local aligner's, so the ratio is information and no gate.
 
+``--band W`` times the same pairs inside a band of ``W`` diagonals around diagonal 0 (``band =
+(-(W // 2), W - 1 - W // 2)`` for every pair) next to the call without a band, and adds ``band``
+to the document: ``local_align`` with the band, its seconds, pairs/s and ``over_unbanded`` (the
+ratio of the two medians), the cells inside the band and the steps per strip by the
+kernel's loop bounds (arithmetic, counted on the host); with ``--spans`` the same for
+``local_spans``, with ``--paths`` for ``local_paths`` (on the pairs and on every record with
+itself, whose diagonal 0 is the path).  Random records share nothing: the band changes which
+alignment is found, and the times say what the band saves, not what it finds.
+
     python tools/bench_align.py --pairs 20000
     python tools/bench_align.py --pairs 20000 --spans
+    python tools/bench_align.py --pairs 20000 --band 129 --spans --paths
     python tools/bench_align.py --pairs 20000 --global --within
     python tools/bench_align.py --pairs 20000 --paths
 """
@@ -58,6 +68,7 @@ KERNEL_SOURCE = "align_local.hip"
 SPAN_SOURCES = ("align_local.inc", "align_span.hip")     # --spans: the shared body and its kernel
 PATH_SOURCES = ("align_local.inc", "align_span.hip", "align_trace.hip")   # --paths
 GLOBAL_SOURCES = ("align_local.inc", "align_global.hip")                  # --global, --within
+BAND_SOURCES = ("align_local.inc", "align_band.hip")                      # --band
 
 
 def _commit() -> str | None:
@@ -110,6 +121,30 @@ def _paths_against_spans(rows, counts, pairs, keeper, parameters, repeats, warmu
                      "launch, the compaction"}
 
 
+def _band_counts(counts, pairs, lo: int, hi: int) -> dict:
+    """Cells inside the band and steps of the kernel's step loop, by its bounds: per strip of 64
+    rows from i0, columns c_lo = max(0, i0 + lo) .. c_hi = min(Lr - 1, i0 + rows - 1 + hi) and
+    c_hi - (c_lo & ~31) + rows steps, against Lr + rows - 1 without a band.  Arithmetic."""
+    cells = steps = steps_plain = 0
+    for lq, lr in zip(counts[pairs[:, 0]].tolist(), counts[pairs[:, 1]].tolist()):
+        i = np.arange(lq)
+        cells += int(np.maximum(np.minimum(lr - 1, i + hi) - np.maximum(0, i + lo) + 1, 0).sum())
+        for i0 in range(0, lq, 64):
+            rows = min(64, lq - i0)
+            steps_plain += lr + rows - 1
+            c_lo, c_hi = max(0, i0 + lo), min(lr - 1, i0 + rows - 1 + hi)
+            if c_lo <= c_hi:
+                steps += c_hi - (c_lo & ~31) + rows
+    return {"band_cells": cells, "steps": steps, "steps_without_band": steps_plain,
+            "counted": "on the host from the loop bounds, not measured"}
+
+
+def _band_against_plain(call, plain_mid: float, pairs: int, repeats: int, warmup: int) -> dict:
+    seconds = _timed(call, repeats, warmup)
+    mid = statistics.median(seconds)
+    return {"seconds": _span(seconds), "pairs_per_s": pairs / mid, "over_unbanded": mid / plain_mid}
+
+
 def _host_gotoh(S: np.ndarray, go: np.float32, ge: np.float32) -> np.float32:
     """max H of the recurrences in numpy float32, one anti-diagonal at a time."""
     lq, lr = S.shape
@@ -145,11 +180,17 @@ def main() -> None:
     parser.add_argument("--within", action="store_true",
                         help="time align.global_align(within=True) (query-in-target) after "
                              "local_align")
+    parser.add_argument("--band", type=int, default=0, metavar="W",
+                        help="time the same pairs inside a band of W diagonals around diagonal 0 "
+                             "next to the calls without a band (with --spans and --paths: those "
+                             "calls too)")
     parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
     parser.add_argument("--out", default=str(ROOT / "profiles" / "align_bench.json"))
     args = parser.parse_args()
     if args.pairs < 1 or args.records < 1:
         parser.error("--pairs, --records: positive")
+    if args.band < 0:
+        parser.error("--band: a positive number of diagonals")
     rng = np.random.default_rng(0)
     counts = rng.integers(200, 601, size=args.records)
     ptr = np.concatenate(([0], np.cumsum(counts)))
@@ -224,6 +265,38 @@ def main() -> None:
                   f"{part['paths_seconds']['median']:.4f} s = {part['paths_over_local_spans']:.3f} x, "
                   f"{part['ops']} ops, {part['box_cells']} box cells of {part['cells']}",
                   file=sys.stderr, flush=True)
+    if args.band:
+        band = (-(args.band // 2), args.band - 1 - args.band // 2)
+        part = {"diagonals": args.band, "band": list(band),
+                **_band_counts(counts, pairs, *band),
+                "local_align": _band_against_plain(
+                    lambda: align.local_align(rows, counts_a=counts, pairs=pairs_dev, band=band,
+                                              workspace=keeper, **parameters),
+                    mid, args.pairs, args.repeats, args.warmup)}
+        if args.spans:
+            part["local_spans"] = _band_against_plain(
+                lambda: align.local_spans(rows, counts_a=counts, pairs=pairs_dev, band=band,
+                                          workspace=keeper, **parameters),
+                statistics.median(result["spans_seconds"]["runs"]), args.pairs, args.repeats,
+                args.warmup)
+        if args.paths:
+            for name, which in (("paths", pairs), ("paths_self", own)):
+                which_dev = torch.from_numpy(which)
+                part["local_" + name] = _band_against_plain(
+                    lambda: align.local_paths(rows, counts_a=counts, pairs=which_dev, band=band,
+                                              workspace=keeper, **parameters),
+                    result[name]["paths_seconds"]["median"], int(which.shape[0]), args.repeats,
+                    args.warmup)
+        part["source_sha256"] = {
+            name: hashlib.sha256((source.parent / name).read_bytes()).hexdigest()
+            for name in BAND_SOURCES}
+        result["band"] = part
+        for name, timed in part.items():
+            if isinstance(timed, dict) and "over_unbanded" in timed:
+                print(f"band of {args.band} diagonals, {name}: {timed['seconds']['median']:.4f} s = "
+                      f"{timed['over_unbanded']:.3f} x the call without a band; steps "
+                      f"{part['steps']} of {part['steps_without_band']} (counted)",
+                      file=sys.stderr, flush=True)
     if args.host_pairs > 0:
         some = pairs[:args.host_pairs]
         host_seconds, host_cells = 0.0, 0
