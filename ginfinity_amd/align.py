@@ -344,10 +344,11 @@ def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_s
                  band=_checked_band(band, pairs.shape[0]))
 
 
-def _launch(call: _Call, span: bool, workspace) -> tuple:
-    """The one launch behind ``local_align`` (``span`` False: ``(scores, ends)``) and
-    ``local_spans`` (True: ``(scores, starts, ends)``) of a call that is ``on_device``; an
-    empty call gives its results without one."""
+def _launch(call: _Call, name: str, sizer: str, leading: tuple, span: bool, workspace) -> tuple:
+    """The one score launch of a call that is ``on_device``: the symbol ``name`` with ``leading``
+    between the call's arguments and the outputs, its workspace sized by the symbol ``sizer``.
+    ``span`` False gives ``(scores, ends)``, True ``(scores, starts, ends)``; an empty call gives
+    its results without a launch."""
     device, count = call.a.device, call.pairs.shape[0]
     with torch.cuda.device(device):
         scores = torch.zeros(count, dtype=torch.float32, device=device)
@@ -356,15 +357,21 @@ def _launch(call: _Call, span: bool, workspace) -> tuple:
         outputs = (scores, starts, ends) if span else (scores, ends)
         if not call.empty:
             lib = native.library()
-            name = "gfy_align_local_span" if span else "gfy_align_local"
-            name += "_band" if call.band is not None else ""
-            sizer = lib.gfy_align_span_workspace_bytes if span else lib.gfy_align_workspace_bytes
-            need = sizer(count, int(call.rows_b.max()))
+            need = getattr(lib, sizer)(count, int(call.rows_b.max()))
             scratch = (workspace or AlignWorkspace()).buffer(device, need)
             native.check(getattr(lib, name)(
-                *call.arguments(), *(out.data_ptr() for out in outputs), scratch.data_ptr(),
-                scratch.numel(), torch.cuda.current_stream(device).cuda_stream), name)
+                *call.arguments(), *leading, *(out.data_ptr() for out in outputs),
+                scratch.data_ptr(), scratch.numel(),
+                torch.cuda.current_stream(device).cuda_stream), name)
     return outputs
+
+
+def _launch_local(call: _Call, span: bool, workspace) -> tuple:
+    """``_launch`` for ``local_align`` (``span`` False) and ``local_spans`` (True)."""
+    name = "gfy_align_local_span" if span else "gfy_align_local"
+    name += "_band" if call.band is not None else ""
+    sizer = "gfy_align_span_workspace_bytes" if span else "gfy_align_workspace_bytes"
+    return _launch(call, name, sizer, (), span, workspace)
 
 
 def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -394,8 +401,8 @@ def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
     finite or out of order, a band that is not integer, of another shape, or with ``lo > hi``.
     ``P == 0`` returns empty tensors without a launch."""
-    return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                 match_scale, match_shift, band).on_device(), False, workspace)
+    return _launch_local(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                       match_scale, match_shift, band).on_device(), False, workspace)
 
 
 def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -411,8 +418,8 @@ def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     The arguments (``band`` among them), their checks and the ``ValueError``s are those of
     ``local_align``; an ``AlignWorkspace`` serves both functions (this one needs twice the
     bytes)."""
-    return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                 match_scale, match_shift, band).on_device(), True, workspace)
+    return _launch_local(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                       match_scale, match_shift, band).on_device(), True, workspace)
 
 
 class AlignedPaths(NamedTuple):
@@ -453,34 +460,47 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     max_workspace_bytes = _checked_cap(max_workspace_bytes)
     call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
                          match_shift, band).on_device()
-    scores, starts, ends = _launch(call, True, workspace)
-    device, count = scores.device, scores.shape[0]
-    with torch.cuda.device(device):
+    scores, starts, ends = _launch_local(call, True, workspace)
+    with torch.cuda.device(scores.device):
         box = (ends - starts + 1).cpu().numpy().astype(np.int64)    # waits for the span launch
         box[starts.cpu().numpy()[:, 0] < 0] = 0                     # nothing aligned: no box
         slots = np.maximum(box.sum(axis=1) - 1, 0)                  # rows + cols - 1 ops at most
-        slot_ptr = np.concatenate(([0], np.cumsum(slots)))
-        if call.empty or slot_ptr[-1] == 0:                         # every path is empty
-            return AlignedPaths(scores, starts, ends,
-                                torch.zeros(0, dtype=torch.uint8, device=device),
-                                torch.zeros(count + 1, dtype=torch.int64, device=device))
-        lib = native.library()
-        box_rows, box_cols = int(box[:, 0].max()), int(box[:, 1].max())
-        need = min(lib.gfy_align_trace_workspace_bytes(count, box_rows, box_cols),
-                   max_workspace_bytes)
-        scratch = (workspace or AlignWorkspace()).buffer(device, need)
-        slot_ptr_dev = torch.from_numpy(slot_ptr).to(device)
-        slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
-        lengths = torch.zeros(count, dtype=torch.int32, device=device)
         name = "gfy_align_trace" if call.band is None else "gfy_align_trace_band"
-        native.check(getattr(lib, name)(
-            *call.arguments(), starts.data_ptr(), ends.data_ptr(), slot_ptr_dev.data_ptr(),
-            slot_ops.data_ptr(), lengths.data_ptr(), box_rows, box_cols, scratch.data_ptr(), need,
-            torch.cuda.current_stream(device).cuda_stream), name)
-        if bool((lengths < 0).any()):
-            raise native.NativeLibraryError(f"{name} refused a box of its span call")
+
+        def trace(lib, slot_ptr, slot_ops, lengths, *rest):   # rest: box, workspace, stream
+            return getattr(lib, name)(*call.arguments(), starts.data_ptr(), ends.data_ptr(),
+                                      slot_ptr, slot_ops, lengths, *rest)
+        return _traced(call, name, trace, "gfy_align_trace_workspace_bytes",
+                       f"{name} refused a box of its span call", scores, starts, ends, slots, box,
+                       max_workspace_bytes, workspace)
+
+
+def _traced(call: _Call, name: str, trace, sizer: str, refusal: str, scores, starts, ends,
+            slots: np.ndarray, boxes: np.ndarray, cap: int, workspace) -> AlignedPaths:
+    """The trace launch behind ``local_paths`` and ``global_paths`` and what it returns.  Pair p
+    owns ``slots[p]`` ops and has a box of ``boxes[p]`` (rows, columns); ``trace(lib, slot_ptr,
+    slot_ops, lengths, box_rows, box_cols, scratch, bytes, stream)`` calls the symbol ``name``
+    with the call site's own arguments in front, on ``min(what the symbol sizer asks for, cap)``
+    bytes.  A negative length is ``refusal``."""
+    device, count = scores.device, scores.shape[0]
+    slot_ptr = np.concatenate(([0], np.cumsum(slots)))
+    if call.empty or slot_ptr[-1] == 0:                             # every path is empty
         return AlignedPaths(scores, starts, ends,
-                            *_compacted(slot_ops, slot_ptr_dev, slots, lengths))
+                            torch.zeros(0, dtype=torch.uint8, device=device),
+                            torch.zeros(count + 1, dtype=torch.int64, device=device))
+    lib = native.library()
+    box_rows, box_cols = int(boxes[:, 0].max()), int(boxes[:, 1].max())
+    need = min(getattr(lib, sizer)(count, box_rows, box_cols), cap)
+    scratch = (workspace or AlignWorkspace()).buffer(device, need)
+    slot_ptr_dev = torch.from_numpy(slot_ptr).to(device)
+    slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
+    lengths = torch.zeros(count, dtype=torch.int32, device=device)
+    native.check(trace(lib, slot_ptr_dev.data_ptr(), slot_ops.data_ptr(), lengths.data_ptr(),
+                       box_rows, box_cols, scratch.data_ptr(), need,
+                       torch.cuda.current_stream(device).cuda_stream), name)
+    if bool((lengths < 0).any()):
+        raise native.NativeLibraryError(refusal)
+    return AlignedPaths(scores, starts, ends, *_compacted(slot_ops, slot_ptr_dev, slots, lengths))
 
 
 def _compacted(slot_ops, slot_ptr_dev, slots: np.ndarray, lengths) -> tuple:
@@ -509,21 +529,9 @@ def _checked_cap(max_workspace_bytes) -> int:
 
 
 def _launch_global(call: _Call, within: bool, workspace) -> tuple:
-    """The launch behind ``global_align``: ``(scores, ends)`` of a call that is ``on_device``; an
-    empty call gives its results without one."""
-    device, count = call.a.device, call.pairs.shape[0]
-    with torch.cuda.device(device):
-        scores = torch.zeros(count, dtype=torch.float32, device=device)
-        ends = torch.full((count, 2), -1, dtype=torch.int32, device=device)
-        if not call.empty:
-            lib = native.library()
-            need = lib.gfy_align_workspace_bytes(count, int(call.rows_b.max()))
-            scratch = (workspace or AlignWorkspace()).buffer(device, need)
-            native.check(lib.gfy_align_global(
-                *call.arguments(), int(within), scores.data_ptr(), ends.data_ptr(),
-                scratch.data_ptr(), scratch.numel(),
-                torch.cuda.current_stream(device).cuda_stream), "gfy_align_global")
-    return scores, ends
+    """``_launch`` for ``global_align``: ``(scores, ends)``."""
+    return _launch(call, "gfy_align_global", "gfy_align_workspace_bytes", (int(within),), False,
+                   workspace)
 
 
 def global_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -576,28 +584,15 @@ def global_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_ext
         rows_a = np.diff(call.ptr_a)[call.pairs[:, 0]].astype(np.int64)
         rows_b = call.rows_b.astype(np.int64)
         slots = np.where((rows_a > 0) & (rows_b > 0), rows_a + rows_b, 0)   # Lq + Lr ops at most
-        slot_ptr = np.concatenate(([0], np.cumsum(slots)))
-        if call.empty or slot_ptr[-1] == 0:                         # every path is empty
-            return AlignedPaths(scores, starts, ends,
-                                torch.zeros(0, dtype=torch.uint8, device=device),
-                                torch.zeros(count + 1, dtype=torch.int64, device=device))
-        lib = native.library()
-        most_a, most_b = int(rows_a.max()), int(rows_b.max())
-        need = min(lib.gfy_align_global_trace_workspace_bytes(count, most_a, most_b), cap)
-        scratch = (workspace or AlignWorkspace()).buffer(device, need)
-        slot_ptr_dev = torch.from_numpy(slot_ptr).to(device)
-        slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
-        lengths = torch.zeros(count, dtype=torch.int32, device=device)
-        native.check(lib.gfy_align_global_trace(
-            *call.arguments(), int(within), ends.data_ptr(), slot_ptr_dev.data_ptr(),
-            slot_ops.data_ptr(), lengths.data_ptr(), starts.data_ptr(), most_a, most_b,
-            scratch.data_ptr(), need, torch.cuda.current_stream(device).cuda_stream),
-            "gfy_align_global_trace")
-        if bool((lengths < 0).any()):
-            raise native.NativeLibraryError(
-                "gfy_align_global_trace refused an end of gfy_align_global")
-        return AlignedPaths(scores, starts, ends,
-                            *_compacted(slot_ops, slot_ptr_dev, slots, lengths))
+
+        def trace(lib, slot_ptr, slot_ops, lengths, *rest):   # rest: box, workspace, stream
+            return lib.gfy_align_global_trace(
+                *call.arguments(), int(within), ends.data_ptr(), slot_ptr, slot_ops, lengths,
+                starts.data_ptr(), *rest)
+        return _traced(call, "gfy_align_global_trace", trace,
+                       "gfy_align_global_trace_workspace_bytes",
+                       "gfy_align_global_trace refused an end of gfy_align_global", scores, starts,
+                       ends, slots, np.stack([rows_a, rows_b], axis=1), cap, workspace)
 
 
 def path_cells(ops, start) -> np.ndarray:

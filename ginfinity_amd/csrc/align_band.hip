@@ -1,10 +1,10 @@
 // Local alignment inside a band of diagonals per pair (gfy_align_local_band,
 // gfy_align_local_span_band, gfy_align_trace_band; semantics: include/gfy.h): the loop of
-// align_local.inc with kBand = true, once for each of the three local kernels.  The band is the
-// matrix: a cell whose diagonal j - i lies outside (lo, hi) is outside it, and the columns of a
-// strip that hold no band cell are neither staged, multiplied nor stepped over (the loop bounds
-// and the places where a band could go wrong are in the header of align_local.inc).  Arguments,
-// workspaces and their cut are those of the unbanded kernels.
+// align_local.inc with the mode bit kBand, once for each of the three local kernels.  The band is
+// the matrix: a cell whose diagonal j - i lies outside (lo, hi) is outside it, and the columns of
+// a strip that hold no band cell are neither staged, multiplied nor stepped over (the loop bounds
+// and the places where a band could go wrong are said in align_local.inc at the statements that
+// deal with them).  Arguments, workspaces and their cut are those of the unbanded kernels.
 #include "align_local.inc"
 
 namespace gfy {
@@ -21,15 +21,15 @@ struct TraceBandArgs {
 };
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_local_band(const AlignArgs p) {
-  align_pairs<false, false, false, true>(p, nullptr);
+  align_pairs<kBand>(p, nullptr);
 }
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_span_band(const SpanBandArgs p) {
-  align_pairs<true, false, false, true>(p.align, p.out_start);
+  align_pairs<kSpan | kBand>(p.align, p.out_start);
 }
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_trace_band(const TraceBandArgs p) {
-  align_pairs<false, true, false, true>(p.align, nullptr, &p.trace);
+  align_pairs<kTrace | kBand>(p.align, nullptr, &p.trace);
 }
 
 }  // namespace

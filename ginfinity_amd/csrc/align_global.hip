@@ -1,5 +1,5 @@
 // Global and query-in-target alignment of record pairs (gfy_align_global; semantics:
-// include/gfy.h): the loop of align_local.inc with kGlobal = true.  The recurrences, the strips,
+// include/gfy.h): the loop of align_local.inc in mode kGlobal.  The recurrences, the strips,
 // the skew and the carry are the local aligner's; what differs is what lies outside the matrix
 // (charged borders, iterated, and with `within` a free top border), that 0 is no candidate of the
 // max, and where the score is read (the last cell, or the best of the last row).  The workspace
@@ -15,7 +15,7 @@ struct GlobalArgs {
 };
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_global(const GlobalArgs p) {
-  align_pairs<false, false, true>(p.align, nullptr, nullptr, p.within != 0);
+  align_pairs<kGlobal>(p.align, nullptr, nullptr, p.within != 0);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // The aligned path of a global or query-in-target alignment (gfy_align_global_trace; semantics:
-// include/gfy.h): the loop of align_local.inc with kTrace = true and kGlobal = true.  The box is
+// include/gfy.h): the loop of align_local.inc in mode kTrace | kGlobal.  The box is
 // rows 0 .. L_q - 1 and columns 0 .. end_j of the pair's records, whose top-left corner is the
 // matrix's own, so every value in it is the full matrix's by construction; the walk leaves it
 // over a border and the border's ops are added behind it.  The workspace is cut as
@@ -17,7 +17,7 @@ struct GlobalTraceArgs {
 };
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_global_trace(const GlobalTraceArgs p) {
-  align_pairs<false, true, true>(p.align, p.out_start, &p.trace, p.within != 0);
+  align_pairs<kTrace | kGlobal>(p.align, p.out_start, &p.trace, p.within != 0);
 }
 
 }  // namespace

@@ -4,14 +4,14 @@
 // external aligner of the reference, whose scoring formula is nowhere in its tree.
 //
 // The kernel's body, and how a wave walks a pair, is align_local.inc; this file instantiates it
-// without origins (kSpan = false: score and end), align_span.hip with them.
+// without origins (mode 0: score and end), align_span.hip with them.
 #include "align_local.inc"
 
 namespace gfy {
 namespace {
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_local(const AlignArgs p) {
-  align_pairs<false>(p, nullptr);
+  align_pairs<0>(p, nullptr);
 }
 
 }  // namespace

@@ -1,8 +1,8 @@
 // The one alignment loop of the library (semantics: include/gfy.h), shared by k_align_local
-// (align_local.hip, kSpan = false: score and end), k_align_span (align_span.hip, kSpan = true:
-// score, start and end) and k_align_trace (align_trace.hip, kTrace = true: the aligned path of a
-// given box), their three twins inside a band of diagonals (align_band.hip, kBand = true) and the
-// two global kernels (kGlobal = true), as pairwise_topk.inc is shared by the top-k family.
+// (align_local.hip, mode 0: score and end), k_align_span (align_span.hip, kSpan: score, start and
+// end) and k_align_trace (align_trace.hip, kTrace: the aligned path of a given box), their three
+// twins inside a band of diagonals (align_band.hip, | kBand) and the two global kernels
+// (kGlobal), as pairwise_topk.inc is shared by the top-k family.
 //
 // One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
 // wave takes pairs wave, wave + waves of the grid, ... until the list ends.
@@ -11,84 +11,17 @@
 //     lane l - 1 (one wave shift each), H of the diagonal is last step's H from above, E and H
 //     of the left neighbour are the lane's own registers.  Every cell is the fixed expression of
 //     include/gfy.h of its three predecessors, so nothing depends on the schedule.
-//   * The substitution scores come 32 columns at a time: the 32 b-rows go to LDS in the swizzled
-//     layout of the sweep, sweep_multiply (pairwise_sweep.inc, the one multiply of the library)
-//     forms the 64 x 32 products against the strip's fragments, which stay in registers, and the
-//     epilogue turns them into the dense kernel's cosine (same key, same pair_value), scales and
-//     shifts it with two rounded operations and stores it BY ANTI-DIAGONAL: cell (l, j) at
-//     [(l + j) % 128][l], a ring of 128 diagonals of 64 lanes (32 KB).  A step reads one diagonal:
-//     64 consecutive words, no bank conflict.  Before step t = 32 kb the ring holds diagonals
-//     t .. t + 62 of earlier columns, the new columns add up to t + 94, and the quarter behind
-//     them (t + 96 .. t + 127, spent by the last 32 steps) stages the b-rows.
+//   * The substitution scores come 32 columns at a time, through the one multiply of the library,
+//     into a ring of 128 anti-diagonals in LDS of which a step reads one.
 //   * The strip's last row goes to the workspace as lane 63 forms it and comes back to lane 0 of
-//     the next strip 32 columns at a time, one load ahead, two buffers in turn: (H, F) per column,
-//     8 bytes, and with kSpan (H, F, origin of H, origin of F), 16 bytes in one store and one load.
-//   * Each lane keeps its best (H, i, j) with a strict >, which is the lowest (i, j) of the lane's
-//     rows; one butterfly at the end orders by (score descending, i ascending, j ascending).
-//   * kSpan: every positive H, E and F has an origin, the first matched cell of the path behind
-//     it, one word (i0 << 12) | j0.  A lane keeps the origins of h, e, f and diag and that of its
-//     best cell; the two values that cross lanes each step take theirs along, and so does the
-//     butterfly.  An origin is SELECTED where its value is formed, by comparing the very operands
-//     of the max — the max expressions themselves are those of kSpan = false, so scores and ends
-//     are the same bits.  With kSpan = false none of it exists.
-//   * kTrace (without kSpan): the pair's records are replaced by the box start..end the caller
-//     names (a-rows from start_i, b-rows from start_j, lq and lr the box's sizes; read from device
-//     arrays, compared and clipped like the records), and every cell leaves 4 direction bits,
-//     selected like the origins from the operands of the max: which candidate H took (0 starts
-//     here, 1 diagonal continuing, 2 E, 3 F), bit 2 E opened, bit 3 F opened.  A lane packs the 8
-//     consecutive columns of its row into a word and stores it when it fills or the row ends:
-//     [box rows][ceil(box cols / 8)] words, row-major, in the wave's region of the workspace (the
-//     only thing proportional to Lq x Lr the library ever writes, and the box alone).  After the
-//     last strip (behind the fence the carry hand-over uses) the wave walks back from the box's
-//     last cell, uniformly: the 64 lanes load the words of the diagonal behind the current cell
-//     at once, so a run of matches costs one load per 64 ops, a gap position one load each.  The
-//     ops go to the ring (free by then) in reverse, one byte each, and the lanes copy them
-//     forward into the pair's slot.  With kTrace = false none of it exists.
-//   * kGlobal: the same recurrences without the 0 candidate and with charged borders (global
-//     alignment, and with the wave-uniform flag `within` the query-in-target mode whose top border
-//     is free; semantics: include/gfy.h, gfy_align_global).  The borders are iterated sums, and
-//     they are iterated here: a wave-uniform running value goes down the left border across the
-//     strips, 64 subtractions per strip of which lane k keeps step k (its initial H) and step
-//     k - 1 (its initial diagonal), and one goes along the top border 32 columns at a time into
-//     what strip 0 takes for its carry.  The score is the last H of the lane that owns row Lq - 1
-//     (global) or that lane's best with a strict > from -inf (within); no other lane tracks
-//     anything.  With kTrace the box is rows 0 .. Lq - 1 and columns 0 .. end_j, whose top-left
-//     corner is the matrix's own; the walk has no "starts here", leaves the box over a border and
-//     the lanes add the border's ops behind it.  With kGlobal = false none of it exists.
-//   * kBand (not with kGlobal): the pair has a band (lo, hi) of diagonals d = j - i, both ends
-//     inclusive, read wave-uniformly from `bands` like the pair itself and clipped into
-//     +-GFY_ALIGN_ROWS_MAX; lo > hi is refused like a pair out of range.  A cell outside the band
-//     is outside the matrix (H = 0, E = F = -inf, no origin), and the work outside it is NOT
-//     DONE: a strip of rows i0 .. i0 + rows - 1 holds band cells in the one column range c_lo =
-//     max(0, i0 + lo) .. c_hi = min(lr - 1, i0 + rows - 1 + hi).  A strip with c_lo > c_hi is
-//     skipped whole (no staging of its a-rows, no multiply) and the strip loop ends once i0 + lo
-//     is past the last column; the step loop runs t from c_lo & ~31 to c_hi + rows - 1, which is
-//     c_hi - (c_lo & ~31) + rows steps against lr + rows - 1; b-rows are loaded from c_lo & ~31
-//     on and 32-column blocks are staged and multiplied only while t0 <= c_hi.  The ring needs
-//     no change: its slot (t & 127) and the staging quarter ((t0 >> 5) + 3) & 3 depend on t0
-//     modulo 128 alone and every block still starts at a multiple of 32, so a block writes the
-//     three quarters in front of its own start and stages in the fourth, whatever the first
-//     block was; at the first block nothing is in flight and every quarter is free.
-//     Where a band can go wrong in this loop, and what is done about it:
-//       - a lane's registers are what its neighbours read.  A cell in the matrix but outside the
-//         band sets h = 0, e = f = -inf instead of keeping the lane's registers; otherwise lane
-//         l + 1 would take the last band cell of lane l for "the row above" when that row has
-//         already left the band at hi.
-//       - diag (and its origin) follows up_h on every step in the matrix, in the band or not;
-//         otherwise a lane's first band cell at d == lo would find a stale diagonal predecessor,
-//         which lies on the same diagonal and hence in the band.  Lane 0 has no step in front of
-//         a start c_lo & ~31 > 0, so it takes its first diagonal predecessor, column (c_lo & ~31)
-//         - 1 of the row above, from the carry.
-//       - lane 63 stores only live cells, so load_carry (and that first diagonal) substitutes
-//         the outside entry for every column c with c - (i0 - 1) outside [lo, hi], per lane and
-//         without reading memory; that also covers a predecessor strip that was skipped.
-//       - kTrace: a row's band may begin and end inside an 8-column direction word, so the word
-//         is also stored at the row's last band cell (d == hi).  A word that is never written
-//         is never walked (a path cell is positive, hence in the band); the 64-lane window load
-//         may read it, inside the wave's own region.  The trace takes the band in the records'
-//         coordinates and shifts it by start_j - start_i itself; a box whose last cell lies
-//         outside the band has no path.  The region stays sized for the whole box.
-//     With kBand = false none of it exists.
+//     the next strip 32 columns at a time, one load ahead, two buffers in turn.
+//   * Each lane keeps its best cell and one butterfly at the end orders them.
+// What a pair needs before and after its strips stands in front of the loop: resolve_pair (the
+// pair's rows, its band, its trace box), trace_walk (kTrace: the path) and finish_pair (score, end
+// and start).  align_pairs itself is the pair loop and, inline, the strip loop: stage the strip,
+// the borders of kGlobal, the carry, the 32-column blocks and the cell step; what each mode adds
+// is said at the statement that does it.  (The strip loop stays in one body on purpose: taking
+// any of its parts out, as a function or as a lambda, changed the kernels' register counts.)
 // ptr_a, ptr_b and pairs are device arrays: they are compared and clipped, a pair outside them or
 // longer than the limits gets NaN and (-2, -2), and nothing outside the caller's buffers is read.
 #pragma once
@@ -115,6 +48,15 @@ static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an or
 
 // (AlignArgs and TraceArgs, the kernels' arguments: gfy_common.h)
 
+// The modes of align_pairs<kMode>, or-ed together.  A mode that is not set costs nothing: behind
+// `if constexpr` none of its code exists.
+//   kSpan    score, end and the start cell
+//   kTrace   the aligned path of a box the caller names; not with kSpan
+//   kGlobal  no 0 candidate and charged borders, with the wave-uniform flag `within` the
+//            query-in-target mode; not with kSpan
+//   kBand    only the cells of a band of diagonals exist; not with kGlobal
+enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8 };
+
 // a carry entry: (H, F) of a column, and with kSpan their origins behind them
 template <bool kSpan>
 using AlignCarry = std::conditional_t<kSpan, u32x4, float2>;
@@ -139,12 +81,243 @@ __device__ __forceinline__ void record_rows(const int32_t* ptr, int index, int64
   hi = hi < lo ? lo : hi > rows ? rows : hi;
 }
 
+// a pair, resolved: with ok == false lq = lr = 0 and the pair gets the refusal values
+struct AlignPair {
+  bool ok;
+  int lq, lr;            // rows of A and B that are aligned (kTrace: the box's sizes)
+  const f16* rows_a;
+  const f16* rows_b;
+  int lo, hi;            // kBand: the band, clipped (kTrace: in the box's coordinates)
+  int64_t op_lo;         // kTrace: where the pair's slot starts
+  int dir_pitch;         // kTrace: words of a row of the box
+};
+
+// The pair, wave-uniformly: its records compared and clipped, and what the modes add to it.
+//   kBand: the pair has a band (lo, hi) of diagonals d = j - i, both ends inclusive, read like the
+//     pair itself from `bands` and clipped into +-GFY_ALIGN_ROWS_MAX; lo > hi is refused like a
+//     pair out of range.  A cell outside the band is outside the matrix (H = 0, E = F = -inf, no
+//     origin).
+//   kTrace (without kSpan): the pair's records are replaced by the box start..end the caller names
+//     (a-rows from start_i, b-rows from start_j, lq and lr the box's sizes; read from device
+//     arrays, compared and clipped like the records).  With kBand the trace takes the band in the
+//     records' coordinates and shifts it by start_j - start_i itself.
+//   kTrace and kGlobal: the box is rows 0 .. Lq - 1 and columns 0 .. end_j, whose top-left corner
+//     is the matrix's own.
+template <unsigned kMode>
+__device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs* trace,
+                                             bool within, int64_t pair, AlignPair& pr) {
+  constexpr bool kTrace = kMode & AlignMode::kTrace, kGlobal = kMode & AlignMode::kGlobal;
+  constexpr bool kBand = kMode & AlignMode::kBand;
+  const int q = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair]);
+  const int rec = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair + 1]);
+  bool ok = (uint32_t)q < (uint32_t)p.records_a && (uint32_t)rec < (uint32_t)p.records_b;
+  int64_t a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;
+  int lo = 0, hi = 0;   // kBand: the band, from here on clipped
+  if constexpr (kBand) {
+    lo = __builtin_amdgcn_readfirstlane(p.bands[2 * pair]);
+    hi = __builtin_amdgcn_readfirstlane(p.bands[2 * pair + 1]);
+    ok = ok && lo <= hi;
+    lo = lo < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : lo > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : lo;
+    hi = hi < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : hi > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : hi;
+  }
+  if (ok) {
+    record_rows(p.ptr_a, q, p.n, a_lo, a_hi);
+    record_rows(p.ptr_b, rec, p.m, b_lo, b_hi);
+  }
+  ok = ok && a_hi - a_lo <= GFY_ALIGN_ROWS_MAX && b_hi - b_lo <= GFY_ALIGN_ROWS_MAX &&
+       (kTrace || b_hi - b_lo <= p.cap);
+  pr.op_lo = 0;
+  if constexpr (kTrace) {
+    // only a box that the span call (kGlobal: gfy_align_global) can have named, that fits the
+    // wave's region and whose path fits the slot is followed; (-1, -1) is the empty alignment
+    int si = 0, sj = 0;   // kGlobal: the box starts at the matrix's corner
+    if constexpr (!kGlobal) {
+      si = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair]);
+      sj = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair + 1]);
+    }
+    const int ei = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair]);
+    const int ej = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair + 1]);
+    pr.op_lo = trace->op_ptr[pair];
+    const int64_t op_hi = trace->op_ptr[pair + 1];
+    bool none, box;
+    int64_t box_rows, box_cols;
+    if constexpr (kGlobal) {
+      // rows 0 .. Lq - 1 and columns 0 .. end_j of the records
+      const int64_t full_q = a_hi - a_lo, full_r = b_hi - b_lo;
+      none = ei == -1 && ej == -1;
+      box = ok && !none && ei == full_q - 1 && ej >= 0 && ej < full_r &&
+            (within || ej == full_r - 1);
+      box_rows = box ? full_q : 0, box_cols = box ? (int64_t)ej + 1 : 0;
+    } else {
+      // the box inside the records
+      none = si == -1 && sj == -1;
+      box = ok && !none && si >= 0 && sj >= 0 && si <= ei && sj <= ej && ei < a_hi - a_lo &&
+            ej < b_hi - b_lo;
+      box_rows = box ? ei - si + 1 : 0, box_cols = box ? ej - sj + 1 : 0;
+    }
+    // a local path has at most rows + cols - 1 ops; a global one may be all gaps
+    const int64_t ops_most = box_rows + box_cols - (kGlobal ? 0 : 1);
+    box = box && box_cols <= p.cap && box_rows * ((box_cols + 7) >> 3) <= trace->region_words &&
+          pr.op_lo >= 0 && op_hi - pr.op_lo >= ops_most;
+    ok = ok && (none || box);
+    if constexpr (kBand) {   // the band in the box's coordinates
+      lo -= box ? sj - si : 0;
+      hi -= box ? sj - si : 0;
+    }
+    a_lo += box ? si : 0;
+    b_lo += box ? sj : 0;
+    a_hi = a_lo + (box ? box_rows : 0);
+    b_hi = b_lo + (box ? box_cols : 0);
+  }
+  pr.ok = ok;
+  pr.lo = lo, pr.hi = hi;
+  pr.lq = __builtin_amdgcn_readfirstlane(ok ? (int)(a_hi - a_lo) : 0);
+  pr.lr = __builtin_amdgcn_readfirstlane(ok ? (int)(b_hi - b_lo) : 0);
+  pr.rows_a = p.a + a_lo * 128;
+  pr.rows_b = p.b + b_lo * 128;
+  pr.dir_pitch = (pr.lr + 7) >> 3;
+}
+
+// kTrace: after the last strip (behind the fence the carry hand-over uses) the wave walks back
+// from the box's last cell, uniformly: the 64 lanes load the words of the diagonal behind the
+// current cell at once, so a run of matches costs one load per 64 ops, a gap position one load
+// each.  The ops go to the ring (free by then) in reverse, one byte each, and the lanes copy them
+// forward into the pair's slot.  h_last is a lane's H when its strip ended: H of the box's last
+// cell is the last H of the lane that owns its row.
+//   kGlobal: the walk has no "starts here", leaves the box over a border and the lanes add the
+//     border's ops behind it; any H is walked back from, and a path that is all gaps has Lq + Lr
+//     ops.  start_j is the first row of B the path consumes.
+//   kBand: a box whose last cell lies outside the band has no path.
+template <unsigned kMode>
+__device__ __forceinline__ void trace_walk(int lane, char* ring, const uint32_t* dir,
+                                           const AlignPair& pr, const TraceArgs* trace,
+                                           bool within, int64_t pair, int strips, float h_last,
+                                           int32_t* out_start) {
+  constexpr bool kGlobal = kMode & AlignMode::kGlobal, kBand = kMode & AlignMode::kBand;
+  const int lq = pr.lq, lr = pr.lr;
+  int length = 0;
+  int start_j = 0;
+  bool corner = strips > 0;   // the box's last cell exists (kBand: and lies in the band)
+  if constexpr (kBand) corner = corner && (uint32_t)(lr - lq - pr.lo) <= (uint32_t)(pr.hi - pr.lo);
+  if (corner && (kGlobal || lane_value(h_last, (lq - 1) & (kStrip - 1)) > 0.f)) {
+    uint8_t* reversed = reinterpret_cast<uint8_t*>(ring);   // <= 8192 ops of a byte
+    const int limit = lq + lr - (kGlobal ? 0 : 1);
+    int i = lq - 1, j = lr - 1, state = 0;   // 0 in H, 1 in E, 2 in F
+    int anchor_i = -1, anchor_j = -1;        // lane l holds the word of cell anchor - (l, l)
+    uint32_t window = 0;
+    while (length < limit && i >= 0 && j >= 0) {
+      int k = anchor_i - i;
+      if ((uint32_t)k >= 64u || anchor_j - j != k) {
+        anchor_i = i, anchor_j = j, k = 0;
+        const int wi = i - lane, wj = j - lane;
+        window = 0;
+        if (wi >= 0 && wj >= 0)
+          window = __hip_atomic_load(dir + (size_t)wi * pr.dir_pitch + (wj >> 3),
+                                     __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      const uint32_t bits = ((uint32_t)__builtin_amdgcn_readlane((int)window, k) >> (4 * (j & 7))) & 15u;
+      int op;
+      bool last = false;
+      if (state == 0) {
+        const uint32_t how = bits & 3u;
+        if (how >= 2u) {   // H is E's or F's value: the same cell in that state
+          state = (int)how - 1;
+          continue;
+        }
+        op = 0, last = !kGlobal && how == 0u;
+        --i, --j;
+      } else if (state == 1) {
+        op = 1, state = bits & 4u ? 0 : 1;
+        --j;
+      } else {
+        op = 2, state = bits & 8u ? 0 : 2;
+        --i;
+      }
+      if (lane == 0) reversed[length] = (uint8_t)op;
+      ++length;
+      if (last) break;
+    }
+    if constexpr (kGlobal) {
+      // the walk left the box in H (a gap that reaches a border opened there).  The left
+      // border is a charged gap of i + 1 rows of A, the top border one of j + 1 rows of B, or
+      // with `within` free: the path starts behind it.  They are the path's first ops.
+      int more = 0, op = 2;
+      if (j < 0) more = i + 1;
+      else if (i < 0 && within) start_j = j + 1;
+      else if (i < 0) more = j + 1, op = 1;
+      more = more < limit - length ? more : limit - length;
+      wave_sync();
+      for (int x = lane; x < more; x += 64) reversed[length + x] = (uint8_t)op;
+      length += more;
+    }
+    wave_sync();
+    for (int x = lane; x < length; x += 64) trace->out_ops[pr.op_lo + x] = reversed[length - 1 - x];
+    wave_sync();   // the next pair restages the ring
+  }
+  if (lane == 0) trace->out_len[pair] = pr.ok ? length : -2;
+  if constexpr (kGlobal) {
+    if (lane == 0) {
+      out_start[2 * pair] = pr.ok ? (strips > 0 ? 0 : -1) : -2;
+      out_start[2 * pair + 1] = pr.ok ? (strips > 0 ? start_j : -1) : -2;
+    }
+  }
+}
+
+// The pair's result.  kGlobal: the last cell, or (within) the first best cell of the last row:
+// one lane holds either.  Otherwise one butterfly orders the lanes' best cells by (score
+// descending, i ascending, j ascending), and with kSpan the origin goes along.
+template <unsigned kMode>
+__device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const AlignPair& pr,
+                                            bool within, int64_t pair, int strips, float h_last,
+                                            float best, int best_i, int best_j,
+                                            uint32_t best_o, int32_t* out_start) {
+  constexpr bool kSpan = kMode & AlignMode::kSpan, kGlobal = kMode & AlignMode::kGlobal;
+  const bool ok = pr.ok;
+  if constexpr (kGlobal) {
+    const int owner = (pr.lq - 1) & (kStrip - 1);
+    const float score = within ? lane_value(best, owner) : lane_value(h_last, owner);
+    const int end_j = within ? __builtin_amdgcn_readlane(best_j, owner) : pr.lr - 1;
+    if (lane == 0) {
+      const bool none = strips == 0;   // a record of zero rows: nothing to align
+      p.out_score[pair] = ok ? (none ? 0.f : score) : __builtin_nanf("");
+      p.out_end[2 * pair] = ok ? (none ? -1 : pr.lq - 1) : -2;
+      p.out_end[2 * pair + 1] = ok ? (none ? -1 : end_j) : -2;
+    }
+  } else {
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) {
+      const float ob = __shfl_xor(best, mask, 64);
+      const int oi = __shfl_xor(best_i, mask, 64), oj = __shfl_xor(best_j, mask, 64);
+      const bool take = ob > best || (ob == best && (oi < best_i || (oi == best_i && oj < best_j)));
+      if constexpr (kSpan) {
+        const uint32_t oo = (uint32_t)__shfl_xor((int)best_o, mask, 64);
+        best_o = take ? oo : best_o;
+      }
+      best = take ? ob : best;
+      best_i = take ? oi : best_i;
+      best_j = take ? oj : best_j;
+    }
+    if (lane == 0) {
+      const bool none = !(best > 0.f);
+      p.out_score[pair] = ok ? (none ? 0.f : best) : __builtin_nanf("");
+      p.out_end[2 * pair] = ok ? (none ? -1 : best_i) : -2;
+      p.out_end[2 * pair + 1] = ok ? (none ? -1 : best_j) : -2;
+      if constexpr (kSpan) {
+        out_start[2 * pair] = ok ? (none ? -1 : (int)(best_o >> kOriginBits)) : -2;
+        out_start[2 * pair + 1] = ok ? (none ? -1 : (int)(best_o & ((1u << kOriginBits) - 1))) : -2;
+      }
+    }
+  }
+}
+
 // out_start ([P][2]) is written with kSpan, and with kTrace and kGlobal together; trace is read
 // with kTrace alone, within (wave-uniform) with kGlobal alone, p.bands with kBand alone
-template <bool kSpan, bool kTrace = false, bool kGlobal = false, bool kBand = false>
+template <unsigned kMode>
 __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start,
                                             const TraceArgs* trace = nullptr,
                                             bool within = false) {
+  constexpr bool kSpan = kMode & AlignMode::kSpan, kTrace = kMode & AlignMode::kTrace;
+  constexpr bool kGlobal = kMode & AlignMode::kGlobal, kBand = kMode & AlignMode::kBand;
   static_assert(!(kSpan && kTrace), "the trace runs on the plain (H, F) carry");
   static_assert(!(kSpan && kGlobal), "a global alignment starts at the matrix's corner");
   static_assert(!(kBand && kGlobal), "a band on the global modes: borders that leave the band");
@@ -172,78 +345,16 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
   const float minus_inf = -__builtin_inff();
 
   for (int64_t pair = slot; pair < p.P; pair += slots) {
-    const int q = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair]);
-    const int rec = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair + 1]);
-    bool ok = (uint32_t)q < (uint32_t)p.records_a && (uint32_t)rec < (uint32_t)p.records_b;
-    int64_t a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;
-    int lo = 0, hi = 0;   // kBand: the band, from here on clipped
-    if constexpr (kBand) {
-      lo = __builtin_amdgcn_readfirstlane(p.bands[2 * pair]);
-      hi = __builtin_amdgcn_readfirstlane(p.bands[2 * pair + 1]);
-      ok = ok && lo <= hi;
-      lo = lo < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : lo > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : lo;
-      hi = hi < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : hi > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : hi;
-    }
-    if (ok) {
-      record_rows(p.ptr_a, q, p.n, a_lo, a_hi);
-      record_rows(p.ptr_b, rec, p.m, b_lo, b_hi);
-    }
-    ok = ok && a_hi - a_lo <= GFY_ALIGN_ROWS_MAX && b_hi - b_lo <= GFY_ALIGN_ROWS_MAX &&
-         (kTrace || b_hi - b_lo <= p.cap);
-    int64_t op_lo = 0;   // kTrace: where the pair's slot starts
-    if constexpr (kTrace && kGlobal) {
-      // the box is rows 0 .. Lq - 1 and columns 0 .. end_j of the records: only an end that
-      // gfy_align_global can have named, whose box fits the wave's region and whose path fits the
-      // slot is followed; (-1, -1) is the empty alignment
-      const int ei = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair]);
-      const int ej = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair + 1]);
-      op_lo = trace->op_ptr[pair];
-      const int64_t op_hi = trace->op_ptr[pair + 1];
-      const int64_t full_q = a_hi - a_lo, full_r = b_hi - b_lo;
-      const bool none = ei == -1 && ej == -1;
-      bool box = ok && !none && ei == full_q - 1 && ej >= 0 && ej < full_r &&
-                 (within || ej == full_r - 1);
-      const int64_t box_rows = box ? full_q : 0, box_cols = box ? (int64_t)ej + 1 : 0;
-      box = box && box_cols <= p.cap && box_rows * ((box_cols + 7) >> 3) <= trace->region_words &&
-            op_lo >= 0 && op_hi - op_lo >= box_rows + box_cols;
-      ok = ok && (none || box);
-      a_hi = a_lo + box_rows;
-      b_hi = b_lo + box_cols;
-    } else if constexpr (kTrace) {
-      // the box inside the records: only a box that lies in them, fits the wave's region and
-      // whose path fits the slot is followed; (-1, -1) is the empty alignment
-      const int si = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair]);
-      const int sj = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair + 1]);
-      const int ei = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair]);
-      const int ej = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair + 1]);
-      op_lo = trace->op_ptr[pair];
-      const int64_t op_hi = trace->op_ptr[pair + 1];
-      const bool none = si == -1 && sj == -1;
-      bool box = ok && !none && si >= 0 && sj >= 0 && si <= ei && sj <= ej && ei < a_hi - a_lo &&
-                 ej < b_hi - b_lo;
-      const int64_t box_rows = box ? ei - si + 1 : 0, box_cols = box ? ej - sj + 1 : 0;
-      box = box && box_cols <= p.cap && box_rows * ((box_cols + 7) >> 3) <= trace->region_words &&
-            op_lo >= 0 && op_hi - op_lo >= box_rows + box_cols - 1;
-      ok = ok && (none || box);
-      if constexpr (kBand) {   // the band in the box's coordinates
-        lo -= box ? sj - si : 0;
-        hi -= box ? sj - si : 0;
-      }
-      a_lo += box ? si : 0;
-      b_lo += box ? sj : 0;
-      a_hi = a_lo + (box ? box_rows : 0);
-      b_hi = b_lo + (box ? box_cols : 0);
-    }
-    const int lq = __builtin_amdgcn_readfirstlane(ok ? (int)(a_hi - a_lo) : 0);
-    const int lr = __builtin_amdgcn_readfirstlane(ok ? (int)(b_hi - b_lo) : 0);
-    const f16* rows_a = p.a + a_lo * 128;
-    const f16* rows_b = p.b + b_lo * 128;
+    AlignPair pr;
+    resolve_pair<kMode>(p, trace, within, pair, pr);
+    const int lq = pr.lq, lr = pr.lr, lo = pr.lo, hi = pr.hi, dir_pitch = pr.dir_pitch;
+    const f16* rows_a = pr.rows_a;
+    const f16* rows_b = pr.rows_b;
 
     // strict >: only a positive cell is ever kept; kGlobal: any cell of row Lq - 1
     float best = kGlobal ? -__builtin_inff() : 0.f;
     int best_i = -1, best_j = -1;
     uint32_t best_o = 0;   // kSpan: the origin of the best cell
-    const int dir_pitch = (lr + 7) >> 3;   // kTrace: words of a row of the box
     float h_last = 0.f;                    // kTrace, kGlobal: a lane's H when its strip ended
     float left_run = 0.f;                  // kGlobal: H[i0 - 1][-1], down the left border
 
@@ -264,6 +375,13 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       const int rows = lq - i0 < kStrip ? lq - i0 : kStrip;
       const bool onward = strip + 1 < strips;   // lane 63's row feeds another strip
       int c_lo = 0, c_hi = lr - 1;              // kBand: the columns that hold the strip's band cells
+      // kBand: the work outside the band is NOT DONE: a strip of rows i0 .. i0 + rows - 1 holds
+      // band cells in the one column range c_lo = max(0, i0 + lo) .. c_hi = min(lr - 1, i0 +
+      // rows - 1 + hi).  A strip with c_lo > c_hi is skipped whole (no staging of its a-rows, no
+      // multiply) and the strip loop ends once i0 + lo is past the last column; the step loop
+      // runs t from c_lo & ~31 to c_hi + rows - 1, which is c_hi - (c_lo & ~31) + rows steps
+      // against lr + rows - 1; b-rows are loaded from c_lo & ~31 on and 32-column blocks are
+      // staged and multiplied only while t0 <= c_hi.
       if constexpr (kBand) {
         c_lo = i0 + lo > 0 ? i0 + lo : 0;
         c_hi = i0 + rows - 1 + hi < lr - 1 ? i0 + rows - 1 + hi : lr - 1;
@@ -274,8 +392,8 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       const Carry* carry_in = carry + (size_t)((strip + 1) & 1) * p.cap;
       Carry* carry_out = carry + (size_t)(strip & 1) * p.cap;
 
-      // the strip's rows through the ring's first half (free: no column is in flight) into the
-      // MFMA fragments, and 1 / |a_i| next to them
+      // stage the strip: its rows through the ring's first half (free: no column is in flight)
+      // into the MFMA fragments, which stay in registers, and 1 / |a_i| next to them
 #pragma unroll 4
       for (int x = 0; x < 16; ++x) {
         const int row = (lane >> 4) + 4 * x, ch = lane & 15;
@@ -300,8 +418,13 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       float top_run = 0.f;                           // kGlobal: H[-1][c0 - 1], along the top border
       bool tracks = false;                           // kGlobal: this lane owns row Lq - 1 (within)
       if constexpr (kGlobal) {
-        // the left border, iterated: H[0][-1] = 0 - gap_open, H[i][-1] = H[i-1][-1] - gap_extend;
-        // lane k starts from step k and has step k - 1 on its diagonal
+        // kGlobal: the same recurrences without the 0 candidate and with charged borders (global
+        // alignment, and with the wave-uniform flag `within` the query-in-target mode whose top
+        // border is free; semantics: include/gfy.h, gfy_align_global).  The borders are iterated
+        // sums, and they are iterated here.  The left border: a wave-uniform running value goes
+        // down it across the strips, H[0][-1] = 0 - gap_open, H[i][-1] = H[i-1][-1] -
+        // gap_extend, 64 subtractions per strip of which lane k keeps step k (its initial H) and
+        // step k - 1 (its initial diagonal).
 #pragma unroll 8
         for (int k = 0; k < kStrip; ++k) {
           diag = lane == k ? left_run : diag;
@@ -314,13 +437,18 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       uint32_t dir_word = 0;                            // kTrace: the row's 8 columns in the making
       f16x8 b_next[8];
       load_b(b_next, t_first);
-      // the carry entries of the row above the strip for columns c0 + lane, lanes 0..31
+      // the carry entries of the row above the strip for columns c0 + lane, lanes 0..31: the
+      // strip's last row comes back to lane 0 of the next strip 32 columns at a time, one load
+      // ahead, from the two buffers in turn
       auto load_carry = [&](int c0) __attribute__((always_inline)) {
         Carry v;
         if constexpr (kSpan) v = Carry{__float_as_uint(0.f), __float_as_uint(minus_inf), 0u, 0u};
         else v = make_float2(0.f, minus_inf);
         if constexpr (kBand) {
-          // lane 63 stored the live cells alone: what is outside the band of row i0 - 1 is outside
+          // kBand: lane 63 stores only live cells, so this (and the first diagonal below)
+          // substitutes the outside entry for every column c with c - (i0 - 1) outside [lo, hi],
+          // per lane and without reading memory; that also covers a predecessor strip that was
+          // skipped
           if (strip > 0 && lane < kSub && c0 + lane < lr &&
               (uint32_t)(c0 + lane - (i0 - 1) - lo) <= (uint32_t)(hi - lo))
             v = carry_in[c0 + lane];
@@ -328,8 +456,9 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           if (strip > 0 && lane < kSub && c0 + lane < lr) v = carry_in[c0 + lane];
         }
         if constexpr (kGlobal) {
-          // the top border, iterated like the left one (F stays -inf); within: the rows of B in
-          // front of the alignment are free, H = 0
+          // the top border of kGlobal: a running value goes along it 32 columns at a time into
+          // what strip 0 takes for its carry, iterated like the left one (F stays -inf); within:
+          // the rows of B in front of the alignment are free, H = 0
           if (strip == 0 && !within) {
 #pragma unroll 8
             for (int k = 0; k < kSub; ++k) {
@@ -342,7 +471,9 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       };
       Carry carry_next = load_carry(t_first);
       if constexpr (kBand) {
-        // lane 0's first diagonal predecessor, (i0 - 1, t_first - 1): no step brings it
+        // kBand: lane 0 has no step in front of a start t_first = c_lo & ~31 > 0, so it takes
+        // its first diagonal predecessor, column t_first - 1 of the row above, (i0 - 1, t_first
+        // - 1), from the carry: no step brings it
         if (strip > 0 && t_first > 0 && lane == 0 &&
             (uint32_t)(t_first - 1 - (i0 - 1) - lo) <= (uint32_t)(hi - lo)) {
           const Carry v = carry_in[t_first - 1];
@@ -353,7 +484,22 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
 
       const int steps = kBand ? c_hi + rows : lr + rows - 1;   // the step behind the last one
       for (int t0 = t_first; t0 < steps; t0 += kSub) {
-        if (kBand ? t0 <= c_hi : t0 < lr) {   // columns t0 .. t0 + 31 join the ring
+        // Columns t0 .. t0 + 31 join the ring.  The substitution scores come 32 columns at a
+        // time: the 32 b-rows go to LDS in the swizzled layout of the sweep, sweep_multiply
+        // (pairwise_sweep.inc, the one multiply of the library) forms the 64 x 32 products against
+        // the strip's fragments, and the epilogue turns them into the dense kernel's cosine (same
+        // key, same pair_value), scales and shifts it with two rounded operations and stores it
+        // BY ANTI-DIAGONAL: cell (l, j) at [(l + j) % 128][l], a ring of 128 diagonals of 64
+        // lanes (32 KB).  A step reads one diagonal: 64 consecutive words, no bank conflict.
+        // Before step t = 32 kb the ring holds diagonals t .. t + 62 of earlier columns, the new
+        // columns add up to t + 94, and the quarter behind them (t + 96 .. t + 127, spent by the
+        // last 32 steps) stages the b-rows.
+        //   kBand: the ring needs no change: its slot (t & 127) and the staging quarter ((t0 >>
+        //   5) + 3) & 3 depend on t0 modulo 128 alone and every block still starts at a multiple
+        //   of 32, so a block writes the three quarters in front of its own start and stages in
+        //   the fourth, whatever the first block was; at the first block nothing is in flight
+        //   and every quarter is free.
+        if (kBand ? t0 <= c_hi : t0 < lr) {
           char* stage = ring + (((t0 >> 5) + 3) & 3) * (kSub * 256);
 #pragma unroll
           for (int x = 0; x < 8; ++x) {
@@ -387,6 +533,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
         carry_next = load_carry(t0 + kSub);
         const int t_end = t0 + kSub < steps ? t0 + kSub : steps;
         for (int t = t0; t < t_end; ++t) {
+          // the recurrence proper, the same expressions in every mode but for kGlobal's missing 0
           const int j = t - lane;
           float up_h = __shfl_up(h, 1, 64), up_f = __shfl_up(f, 1, 64);
           float above_h, above_f;
@@ -413,6 +560,12 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           else
             h_new = __builtin_fmaxf(__builtin_fmaxf(0.f, match), __builtin_fmaxf(e_new, f_new));
           uint32_t o_new = 0;
+          // kSpan: every positive H, E and F has an origin, the first matched cell of the path
+          // behind it, one word (i0 << 12) | j0.  A lane keeps the origins of h, e, f and diag
+          // and that of its best cell; the two values that cross lanes each step take theirs
+          // along, and so does the butterfly.  An origin is SELECTED where its value is formed,
+          // by comparing the very operands of the max — the max expressions themselves are those
+          // of the mode without kSpan, so scores and ends are the same bits.
           if constexpr (kSpan) {
             uint32_t up_oh = (uint32_t)__shfl_up((int)o_h, 1, 64);
             uint32_t up_of = (uint32_t)__shfl_up((int)o_f, 1, 64);
@@ -430,6 +583,12 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
             o_h = live ? o_new : o_h;
             o_diag = inside ? up_oh : o_diag;
           }
+          // kTrace: every cell leaves 4 direction bits, selected like the origins from the
+          // operands of the max: which candidate H took (0 starts here, 1 diagonal continuing, 2
+          // E, 3 F), bit 2 E opened, bit 3 F opened.  A lane packs the 8 consecutive columns of
+          // its row into a word and stores it when it fills or the row ends: [box rows][ceil(box
+          // cols / 8)] words, row-major, in the wave's region of the workspace (the only thing
+          // proportional to Lq x Lr the library ever writes, and the box alone).
           if constexpr (kTrace) {
             // the same selections as kSpan's, kept as bits: diagonal, then E, then F; opening
             // wins a tie
@@ -439,12 +598,20 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
             const uint32_t bits = how | (e_open >= e_ext ? 4u : 0u) | (f_open >= f_ext ? 8u : 0u);
             if (live) {
               dir_word = (j & 7) == 0 ? bits : dir_word | (bits << (4 * (j & 7)));
+              // kBand: a row's band may begin and end inside an 8-column direction word, so the
+              // word is also stored at the row's last band cell (d == hi).  A word that is never
+              // written is never walked (a path cell is positive, hence in the band); the
+              // 64-lane window load of trace_walk may read it, inside the wave's own region.
+              // The region stays sized for the whole box.
               if ((j & 7) == 7 || j == lr - 1 || (kBand && j - (i0 + lane) == hi))
                 dir[(size_t)(i0 + lane) * dir_pitch + (j >> 3)] = dir_word;
             }
           }
           if constexpr (kBand) {
-            // in the matrix, outside the band: the outside values, for the neighbours to read
+            // a lane's registers are what its neighbours read.  A cell in the matrix but outside
+            // the band sets h = 0, e = f = -inf instead of keeping the lane's registers;
+            // otherwise lane l + 1 would take the last band cell of lane l for "the row above"
+            // when that row has already left the band at hi.
             e = live ? e_new : inside ? minus_inf : e;
             f = live ? f_new : inside ? minus_inf : f;
             h = live ? h_new : inside ? 0.f : h;
@@ -453,12 +620,22 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
             f = live ? f_new : f;
             h = live ? h_new : h;
           }
+          // kBand: diag (and its origin, above) follows up_h on every step in the matrix, in the
+          // band or not; otherwise a lane's first band cell at d == lo would find a stale
+          // diagonal predecessor, which lies on the same diagonal and hence in the band.
           diag = inside ? up_h : diag;
+          // Each lane keeps its best (H, i, j) with a strict >, which is the lowest (i, j) of the
+          // lane's rows.  kGlobal: the score is the last H of the lane that owns row Lq - 1
+          // (global) or that lane's best with a strict > from -inf (within, `tracks`); no other
+          // lane tracks anything.
           const bool better = live && (!kGlobal || tracks) && h_new > best;
           best = better ? h_new : best;
           best_i = better ? i0 + lane : best_i;
           best_j = better ? j : best_j;
           if constexpr (kSpan) best_o = better ? o_new : best_o;
+          // the strip's last row goes to the workspace as lane 63 forms it: (H, F) per column, 8
+          // bytes, and with kSpan (H, F, origin of H, origin of F), 16 bytes in one store and one
+          // load
           if (onward && lane == kStrip - 1 && live) {
             if constexpr (kSpan)
               carry_out[j] = Carry{__float_as_uint(h_new), __float_as_uint(f_new), o_h, o_f};
@@ -474,115 +651,11 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       wave_sync();
     }
 
-    if constexpr (kTrace) {
-      int length = 0;
-      // H of the box's last cell is the last H of the lane that owns its row
-      int start_j = 0;   // kGlobal: the first row of B the path consumes
-      // (kGlobal: any H is walked back from, and a path that is all gaps has Lq + Lr ops)
-      bool corner = strips > 0;   // the box's last cell exists (kBand: and lies in the band)
-      if constexpr (kBand) corner = corner && (uint32_t)(lr - lq - lo) <= (uint32_t)(hi - lo);
-      if (corner && (kGlobal || lane_value(h_last, (lq - 1) & (kStrip - 1)) > 0.f)) {
-        uint8_t* reversed = reinterpret_cast<uint8_t*>(ring);   // <= 8192 ops of a byte
-        const int limit = lq + lr - (kGlobal ? 0 : 1);
-        int i = lq - 1, j = lr - 1, state = 0;   // 0 in H, 1 in E, 2 in F
-        int anchor_i = -1, anchor_j = -1;        // lane l holds the word of cell anchor - (l, l)
-        uint32_t window = 0;
-        while (length < limit && i >= 0 && j >= 0) {
-          int k = anchor_i - i;
-          if ((uint32_t)k >= 64u || anchor_j - j != k) {
-            anchor_i = i, anchor_j = j, k = 0;
-            const int wi = i - lane, wj = j - lane;
-            window = 0;
-            if (wi >= 0 && wj >= 0)
-              window = __hip_atomic_load(dir + (size_t)wi * dir_pitch + (wj >> 3), __ATOMIC_RELAXED,
-                                         __HIP_MEMORY_SCOPE_WORKGROUP);
-          }
-          const uint32_t bits = ((uint32_t)__builtin_amdgcn_readlane((int)window, k) >> (4 * (j & 7))) & 15u;
-          int op;
-          bool last = false;
-          if (state == 0) {
-            const uint32_t how = bits & 3u;
-            if (how >= 2u) {   // H is E's or F's value: the same cell in that state
-              state = (int)how - 1;
-              continue;
-            }
-            op = 0, last = !kGlobal && how == 0u;
-            --i, --j;
-          } else if (state == 1) {
-            op = 1, state = bits & 4u ? 0 : 1;
-            --j;
-          } else {
-            op = 2, state = bits & 8u ? 0 : 2;
-            --i;
-          }
-          if (lane == 0) reversed[length] = (uint8_t)op;
-          ++length;
-          if (last) break;
-        }
-        if constexpr (kGlobal) {
-          // the walk left the box in H (a gap that reaches a border opened there).  The left
-          // border is a charged gap of i + 1 rows of A, the top border one of j + 1 rows of B, or
-          // with `within` free: the path starts behind it.  They are the path's first ops.
-          int more = 0, op = 2;
-          if (j < 0) more = i + 1;
-          else if (i < 0 && within) start_j = j + 1;
-          else if (i < 0) more = j + 1, op = 1;
-          more = more < limit - length ? more : limit - length;
-          wave_sync();
-          for (int x = lane; x < more; x += 64) reversed[length + x] = (uint8_t)op;
-          length += more;
-        }
-        wave_sync();
-        for (int x = lane; x < length; x += 64) trace->out_ops[op_lo + x] = reversed[length - 1 - x];
-        wave_sync();   // the next pair restages the ring
-      }
-      if (lane == 0) trace->out_len[pair] = ok ? length : -2;
-      if constexpr (kGlobal) {
-        if (lane == 0) {
-          out_start[2 * pair] = ok ? (strips > 0 ? 0 : -1) : -2;
-          out_start[2 * pair + 1] = ok ? (strips > 0 ? start_j : -1) : -2;
-        }
-      }
-    }
-
-    if constexpr (kGlobal) {
-      // the last cell, or the first best cell of the last row: one lane holds either
-      if (!kTrace) {
-        const int owner = (lq - 1) & (kStrip - 1);
-        const float score = within ? lane_value(best, owner) : lane_value(h_last, owner);
-        const int end_j = within ? __builtin_amdgcn_readlane(best_j, owner) : lr - 1;
-        if (lane == 0) {
-          const bool none = strips == 0;   // a record of zero rows: nothing to align
-          p.out_score[pair] = ok ? (none ? 0.f : score) : __builtin_nanf("");
-          p.out_end[2 * pair] = ok ? (none ? -1 : lq - 1) : -2;
-          p.out_end[2 * pair + 1] = ok ? (none ? -1 : end_j) : -2;
-        }
-      }
-      continue;
-    }
-#pragma unroll
-    for (int mask = 1; mask < 64; mask <<= 1) {
-      const float ob = __shfl_xor(best, mask, 64);
-      const int oi = __shfl_xor(best_i, mask, 64), oj = __shfl_xor(best_j, mask, 64);
-      const bool take = ob > best || (ob == best && (oi < best_i || (oi == best_i && oj < best_j)));
-      if constexpr (kSpan) {
-        const uint32_t oo = (uint32_t)__shfl_xor((int)best_o, mask, 64);
-        best_o = take ? oo : best_o;
-      }
-      best = take ? ob : best;
-      best_i = take ? oi : best_i;
-      best_j = take ? oj : best_j;
-    }
-    if (!kTrace && lane == 0) {
-      const bool none = !(best > 0.f);
-      p.out_score[pair] = ok ? (none ? 0.f : best) : __builtin_nanf("");
-      p.out_end[2 * pair] = ok ? (none ? -1 : best_i) : -2;
-      p.out_end[2 * pair + 1] = ok ? (none ? -1 : best_j) : -2;
-      if constexpr (kSpan) {
-        out_start[2 * pair] = ok ? (none ? -1 : (int)(best_o >> kOriginBits)) : -2;
-        out_start[2 * pair + 1] = ok ? (none ? -1 : (int)(best_o & ((1u << kOriginBits) - 1))) : -2;
-      }
-    }
+    if constexpr (kTrace)
+      trace_walk<kMode>(lane, ring, dir, pr, trace, within, pair, strips, h_last, out_start);
+    else
+      finish_pair<kMode>(p, lane, pr, within, pair, strips, h_last, best, best_i, best_j, best_o,
+                         out_start);
   }
 }
 

@@ -1,5 +1,5 @@
 // Local alignment with start cells (gfy_align_local_span; semantics: include/gfy.h): the loop of
-// align_local.inc with kSpan = true.  Next to H, E and F every lane carries the origin of each,
+// align_local.inc in mode kSpan.  Next to H, E and F every lane carries the origin of each,
 // the first matched cell of the path behind it, so a pair's (start, end) box comes out of the
 // same sweep and the Lq x Lr matrix is still never written.  The workspace holds 16-byte carry
 // entries (H, F and their origins), twice that of gfy_align_local.
@@ -14,7 +14,7 @@ struct SpanArgs {
 };
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_span(const SpanArgs p) {
-  align_pairs<true>(p.align, p.out_start);
+  align_pairs<kSpan>(p.align, p.out_start);
 }
 
 }  // namespace

@@ -1,5 +1,5 @@
 // The aligned path of each pair (gfy_align_trace; semantics: include/gfy.h): the loop of
-// align_local.inc with kTrace = true, run on the box start..end that gfy_align_local_span named.
+// align_local.inc in mode kTrace, run on the box start..end that gfy_align_local_span named.
 // The recurrences on the box alone take every cell of the chosen path to the value it has in the
 // full matrix, so the walk back by the origin rules gives the same ops; the box's direction bits,
 // 4 per cell, are the first thing proportional to L_q x L_r the library writes, per wave in
@@ -16,7 +16,7 @@ struct TraceKernelArgs {
 };
 
 __global__ __launch_bounds__(kAlignThreads) void k_align_trace(const TraceKernelArgs p) {
-  align_pairs<false, true>(p.align, nullptr, &p.trace);
+  align_pairs<kTrace>(p.align, nullptr, &p.trace);
 }
 
 }  // namespace
