@@ -229,8 +229,13 @@ def band_around(seeds, half_width: int) -> np.ndarray:
     or torch) of cells ``(i, j)`` inside the two records of each pair; ``half_width`` is a
     non-negative integer, 0 the seed's diagonal alone.  A pure function of its arguments: no
     device is needed.  A hit of ``distance.topk`` (row ``x`` of ``a``, row ``idx[x, k]`` of ``b``)
-    becomes a seed by taking away each record's first row:
+    becomes a seed by taking away each record's first row.  ``rows``, ``idx`` and the counts are
+    arrays of one library (torch: on one device) — the tuple of counts that
+    ``encode_graphs_device`` returns cannot be indexed by ``q``, so it is made a tensor first —
+    and ``stack`` and ``cumsum`` are that library's:
 
+        counts_a = torch.as_tensor(counts_a, device=idx.device)           # counts_b likewise;
+                                                                          # numpy: np.asarray(counts_a)
         q, r = distance.record_of(rows, counts_a), distance.record_of(idx[rows, k], counts_b)
         seeds = stack([rows - cumsum(counts_a)[q] + counts_a[q],          # minus the record's
                        idx[rows, k] - cumsum(counts_b)[r] + counts_b[r]], 1)    # first row
