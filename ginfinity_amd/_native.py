@@ -135,6 +135,14 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_pairwise_record_scores": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p,
                                            c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                            c_size_t, c_void_p]),
+    "gfy_pairwise_within_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gfy_pairwise_within_chunks": (c_int, [c_int64, c_int64]),
+    "gfy_pairwise_within_count": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float,
+                                          c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
+    "gfy_pairwise_within_fill": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_float,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     "gfy_align_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gfy_align_local": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gfy_align_span_workspace_bytes": (c_size_t, [c_int64, c_int64]),

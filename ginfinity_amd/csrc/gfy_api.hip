@@ -1151,6 +1151,49 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
                                  out_scores, ws, ws_bytes, (hipStream_t)stream);
 }
 
+size_t gfy_pairwise_within_workspace_bytes(int64_t n, int64_t m) {
+  return pairwise_within_workspace_bytes(n < 1 ? 1 : n, m < 1 ? 1 : m);
+}
+
+int gfy_pairwise_within_chunks(int64_t n, int64_t m) {
+  return pairwise_within_chunks(n < 1 ? 1 : n, m < 1 ? 1 : m);
+}
+
+// what the two radius calls check behind check_pairwise_call
+static int check_within_call(const char* who, int64_t n, float threshold, const int32_t* skip_lo,
+                             const int32_t* skip_hi) {
+  GFY_REQUIRE(n < INT32_MAX, GFY_ERR_INVALID, "%s: n = %lld outside 1..2^31 - 2", who,
+              (long long)n);
+  GFY_REQUIRE(__builtin_isfinite(threshold), GFY_ERR_INVALID, "%s: threshold is not finite", who);
+  GFY_REQUIRE((skip_lo == nullptr) == (skip_hi == nullptr), GFY_ERR_INVALID,
+              "%s: skip_lo and skip_hi go together (both NULL: no exclusion)", who);
+  return GFY_OK;
+}
+
+int gfy_pairwise_within_count(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                              float threshold, const int32_t* skip_lo, const int32_t* skip_hi,
+                              int32_t* counts, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "gfy_pairwise_within_count";
+  clear_error();
+  if (const int rc = check_pairwise_call(who, a, n, b, m, metric, counts, counts, ws)) return rc;
+  if (const int rc = check_within_call(who, n, threshold, skip_lo, skip_hi)) return rc;
+  return launch_pairwise_within(a, n, b, m, metric, threshold, skip_lo, skip_hi, counts, nullptr,
+                                nullptr, nullptr, nullptr, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_pairwise_within_fill(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                             float threshold, const int32_t* skip_lo, const int32_t* skip_hi,
+                             const int64_t* offsets, int32_t* indices, float* values,
+                             int32_t* status, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = "gfy_pairwise_within_fill";
+  clear_error();
+  if (const int rc = check_pairwise_call(who, a, n, b, m, metric, values, indices, ws)) return rc;
+  GFY_REQUIRE(offsets && status, GFY_ERR_INVALID, "%s: offsets or status is NULL", who);
+  if (const int rc = check_within_call(who, n, threshold, skip_lo, skip_hi)) return rc;
+  return launch_pairwise_within(a, n, b, m, metric, threshold, skip_lo, skip_hi, nullptr, offsets,
+                                indices, values, status, ws, ws_bytes, (hipStream_t)stream);
+}
+
 // The 14 values every alignment call of the ABI starts with, in the order of include/gfy.h, and
 // an output pointer with the name a refusal gives it.
 struct AlignAbi {

@@ -375,6 +375,15 @@ int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, 
                             hipStream_t s);
 size_t pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_b);
 int pairwise_record_chunks(int64_t n, int64_t m);
+// pairwise_within.hip; counts != nullptr: the count, else the fill into (offsets, indices,
+// values, status); skip_lo / skip_hi both or neither, [n] each
+int launch_pairwise_within(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                           float threshold, const int32_t* skip_lo, const int32_t* skip_hi,
+                           int32_t* counts, const int64_t* offsets, int32_t* indices,
+                           float* values, int32_t* status, void* ws, size_t ws_bytes,
+                           hipStream_t s);
+size_t pairwise_within_workspace_bytes(int64_t n, int64_t m);
+int pairwise_within_chunks(int64_t n, int64_t m);
 // One alignment call (align_local.inc): what the alignment entry points of gfy_api.hip check and
 // fill, the launchers complete (carry, cap) and the kernels read as their argument.
 struct AlignArgs {

@@ -33,8 +33,27 @@ records of ``counts_a`` rows (non-negative integers, checked as ``record_ranges`
 call is cut into blocks, chunks or workgroups, and is the same from run to run bit for bit.  The
 score is directional (``a`` onto ``b``): the symmetric form is two calls.  Nothing is excluded:
 in a self-search the pairs (i, i) are simply the best ones.
+
+Radius search (``count_within``, ``within``; also include/gfy.h): every row of ``b`` that is at
+least as close as ``threshold`` to each row of ``a`` — a result whose length varies per row.  The
+key and the value of a pair are those of ``nearest`` / ``topk``, computed the same way;
+``threshold`` is rounded to float32 once on the host and compared in float32:
+
+    l2      the pair (i, j) is a hit iff value_ij <= threshold
+    cosine  the pair (i, j) is a hit iff value_ij >= threshold
+
+``value_ij`` is bit for bit what ``topk`` reports for the pair.  So the hit set of a row depends
+neither on the other rows of the call nor on how the call is cut into blocks and chunks, is the
+same from run to run bit for bit, is for ``m <= 16`` the entries of ``topk(k=m)`` that pass the
+comparison (same value bits), and is nested in a monotone threshold: raising an l2 threshold
+never loses a hit.  An excluded pair (``exclude_self``, ``exclude_ranges``, ``exclude_records``:
+one skipped range ``lo[i] <= j < hi[i]`` per row, as in ``topk``) is never a hit and never
+counted.  ``within`` sweeps twice (count, then fill) and waits for the device in between to
+learn the total.
 """
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -549,5 +568,172 @@ def record_scores(a, b=None, *, counts_a, counts_b=None, metric: str = "l2",
     return scores
 
 
+class Hits(NamedTuple):
+    """What ``within`` returns: row i's hits are ``indices[offsets[i]:offsets[i + 1]]`` (rows of
+    ``b``, ascending) with ``values`` next to them."""
+    offsets: torch.Tensor   # int64 [n + 1]
+    indices: torch.Tensor   # int32 [H]
+    values: torch.Tensor    # float32 [H]
+
+    def rows(self) -> torch.Tensor:
+        """The a-row of every hit: int64 ``[H]``, row i repeated once per hit of its."""
+        counts = self.offsets[1:] - self.offsets[:-1]
+        return torch.repeat_interleave(
+            torch.arange(counts.numel(), dtype=torch.int64, device=counts.device), counts)
+
+
+class TooManyHits(RuntimeError):
+    """``within(..., max_hits=...)`` found more hits than that; ``total`` is how many."""
+
+    def __init__(self, total: int, max_hits: int) -> None:
+        super().__init__(f"within: {total} hits, max_hits is {max_hits}")
+        self.total = total
+        self.max_hits = max_hits
+
+
+class WithinWorkspace:
+    """Scratch memory and the ``[n]`` counts of ``count_within`` / ``within`` kept across calls,
+    as ``TopKWorkspace`` keeps those of ``topk`` (the hits are always new tensors)."""
+
+    def __init__(self) -> None:
+        self.scratch: torch.Tensor | None = None
+        self.counts: torch.Tensor | None = None
+
+    def buffers(self, device, rows: int, scratch_bytes: int):
+        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
+        self.counts = _grown(self.counts, device, rows, torch.int32)
+        return self.scratch, self.counts[:rows]
+
+
+def _checked_threshold(threshold) -> float:
+    """``threshold`` rounded to float32 once; ``ValueError`` unless it is a real number (no bool)
+    that is finite in float32."""
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer,
+                                                                 np.floating)):
+        raise ValueError("threshold must be a real number")
+    with np.errstate(over="ignore"):
+        rounded = float(np.float32(threshold))
+    if not np.isfinite(rounded):
+        raise ValueError("threshold must be finite in float32")
+    return rounded
+
+
+class _WithinCall:
+    """The checked arguments of ``count_within`` / ``within`` (every argument error is raised
+    here, before a device is touched), then the two native calls on them."""
+
+    def __init__(self, a, b, threshold, metric, exclude_self, exclude_ranges, exclude_records,
+                 workspace) -> None:
+        self.threshold = _checked_threshold(threshold)
+        self.code = _metric(metric)
+        a = _checked(a)
+        b = None if b is None else _checked(b)
+        n = a.shape[0]
+        ranges = _checked_ranges(n, None if b is None else b.shape[0], exclude_ranges,
+                                 exclude_records, bool(exclude_self))
+        if ranges is None and exclude_self:   # the pair (i, i) as a range of one row
+            lo = torch.arange(n, dtype=torch.int64).clamp(max=2 ** 31 - 2)
+            ranges = lo.to(torch.int32), (lo + 1).to(torch.int32)
+        if workspace is not None and not isinstance(workspace, WithinWorkspace):
+            raise ValueError("workspace must be a WithinWorkspace")
+        self.keeper = workspace or WithinWorkspace()
+        self.a = _prepare(a, None)
+        self.b = self.a if b is None else _prepare(b, self.a.device)
+        self.device = self.a.device
+        self.n, self.m = self.a.shape[0], self.b.shape[0]
+        self.ranges = None if ranges is None else tuple(
+            bound.to(self.device).contiguous() for bound in ranges)
+
+    def _front(self) -> tuple:
+        skip = (None, None) if self.ranges is None else tuple(
+            bound.data_ptr() for bound in self.ranges)
+        return (self.a.data_ptr(), self.n, self.b.data_ptr(), self.m, self.code, self.threshold,
+                *skip)
+
+    def _back(self, scratch) -> tuple:
+        return (scratch.data_ptr(), scratch.numel(),
+                torch.cuda.current_stream(self.device).cuda_stream)
+
+    def buffers(self):
+        need = native.library().gfy_pairwise_within_workspace_bytes(self.n, self.m)
+        return self.keeper.buffers(self.device, self.n, need)
+
+    def count(self) -> torch.Tensor:
+        """int32 [n], a view of the workspace's buffer"""
+        scratch, counts = self.buffers()
+        if self.n == 0 or self.m == 0:
+            return counts.zero_()
+        native.check(native.library().gfy_pairwise_within_count(
+            *self._front(), counts.data_ptr(), *self._back(scratch)),
+            "gfy_pairwise_within_count")
+        return counts
+
+    def fill(self, offsets, total: int) -> tuple[torch.Tensor, torch.Tensor]:
+        scratch, _ = self.buffers()
+        indices = torch.empty(total, dtype=torch.int32, device=self.device)
+        values = torch.empty(total, dtype=torch.float32, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        native.check(native.library().gfy_pairwise_within_fill(
+            *self._front(), offsets.data_ptr(), indices.data_ptr(), values.data_ptr(),
+            status.data_ptr(), *self._back(scratch)), "gfy_pairwise_within_fill")
+        if int(status.item()) != 0:
+            raise native.NativeLibraryError(
+                "gfy_pairwise_within_fill: the hits did not match the counted segments")
+        return indices, values
+
+
+def count_within(a, b=None, *, threshold=None, metric: str = "l2", exclude_self: bool = False,
+                 exclude_ranges=None, exclude_records=None,
+                 workspace: WithinWorkspace | None = None) -> torch.Tensor:
+    """For every row of ``a`` the number of rows of ``b`` within ``threshold``: int32 ``[n]``,
+    exact, the N×M matrix never written.  A pair is a hit iff its value — the one ``topk``
+    reports, bit for bit — is ``<= threshold`` (l2) / ``>= threshold`` (cosine); ``threshold`` is
+    required and rounded to float32 once (the definitions are at the head of this module).
+
+    ``exclude_self`` (with ``b`` omitted or identical to ``a``) skips the pair (i, i);
+    ``exclude_ranges=(lo, hi)`` and ``exclude_records=counts`` are those of ``topk``.  The three
+    exclude each other; an excluded pair is not counted.  One sweep: the matrix-core work of
+    ``nearest`` with a lighter epilogue.  With ``workspace`` the returned tensor is a view of its
+    buffer, valid until its next use."""
+    call = _WithinCall(a, b, threshold, metric, exclude_self, exclude_ranges, exclude_records,
+                       workspace)
+    with torch.cuda.device(call.device):
+        return call.count()
+
+
+def within(a, b=None, *, threshold=None, metric: str = "l2", exclude_self: bool = False,
+           exclude_ranges=None, exclude_records=None, max_hits: int | None = None,
+           workspace: WithinWorkspace | None = None) -> Hits:
+    """For every row of ``a`` every row of ``b`` within ``threshold``: ``Hits(offsets int64
+    [n + 1], indices int32 [H], values float32 [H])``; row i's hits are
+    ``indices[offsets[i]:offsets[i + 1]]`` in ascending order of the row of ``b``, ``values``
+    next to them (a ``torch.sort`` of a segment orders it by value).  Hits, values, exclusions
+    and ``threshold`` are those of ``count_within``, whose result is ``offsets.diff()``.
+
+    Two sweeps and a wait: the count, its running sum, the total copied to the host (which waits
+    for the device), then the fill into exactly that many entries and the ordering of every
+    row's segment.  ``max_hits``: a positive integer; a total above it raises ``TooManyHits``
+    (which carries ``total``) before anything is allocated for the hits.  No rows, or no hit,
+    returns empty ``indices`` / ``values`` without the second sweep."""
+    if max_hits is not None and (isinstance(max_hits, bool)
+                                 or not isinstance(max_hits, (int, np.integer)) or max_hits < 1):
+        raise ValueError("max_hits must be a positive integer")
+    call = _WithinCall(a, b, threshold, metric, exclude_self, exclude_ranges, exclude_records,
+                       workspace)
+    with torch.cuda.device(call.device):
+        offsets = torch.zeros(call.n + 1, dtype=torch.int64, device=call.device)
+        total = 0
+        if call.n > 0 and call.m > 0:
+            torch.cumsum(call.count(), 0, dtype=torch.int64, out=offsets[1:])
+            total = int(offsets[-1].item())   # waits for the device
+        if max_hits is not None and total > max_hits:
+            raise TooManyHits(total, int(max_hits))
+        if total == 0:
+            return Hits(offsets, torch.empty(0, dtype=torch.int32, device=call.device),
+                        torch.empty(0, dtype=torch.float32, device=call.device))
+        return Hits(offsets, *call.fill(offsets, total))
+
+
 __all__ = ["pairwise", "nearest", "NearestWorkspace", "topk", "TopKWorkspace", "record_ranges",
-           "record_of", "record_best", "record_scores", "RecordWorkspace", "plan_record_blocks"]
+           "record_of", "record_best", "record_scores", "RecordWorkspace", "plan_record_blocks",
+           "count_within", "within", "Hits", "TooManyHits", "WithinWorkspace"]

@@ -582,6 +582,55 @@ int gfy_pairwise_record_scores(const void* a, int64_t n, const void* b, int64_t 
                                const int32_t* ptr_b, int64_t records_b, float* out_scores,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* Radius search: for every a-row EVERY b-row that is at least as close as a threshold — a result
+ * whose length varies per row, where top-k stops at k.  The N x M matrix is never materialised.
+ *   The key and the value of a pair are those of gfy_pairwise_nearest / gfy_pairwise_topk,
+ *   computed the same way (the folded start values for GFY_L2, the fma key form for GFY_COSINE,
+ *   the same per-row terms, the same value formulas): value_ij is bit for bit what
+ *   gfy_pairwise_topk reports for the pair.  threshold is a float32 and is compared in float32:
+ *     GFY_L2      the pair (i, j) is a hit iff value_ij <= threshold
+ *     GFY_COSINE  the pair (i, j) is a hit iff value_ij >= threshold
+ *   So the hit set of a row depends neither on the other rows of the call nor on how the call
+ *   is cut into blocks and chunks, is the same from run to run bit for bit, is for m <= 16 the
+ *   entries of gfy_pairwise_topk(k = m) that pass the comparison with the same value bits, and
+ *   is nested in a monotone threshold (raising a GFY_L2 threshold never loses a hit).
+ *   skip_lo, skip_hi int32 [n], device memory, both or both NULL (none): the pair (i, j) is
+ *   excluded iff skip_lo[i] <= j < skip_hi[i], with the meaning, the clipping and the cost of
+ *   gfy_pairwise_topk_ranges.  An excluded pair is never a hit and never counted.  Padded rows
+ *   of the ragged last tile are never hits.
+ *   gfy_pairwise_within_count: counts int32 [n], the number of hits of every a-row.
+ *   gfy_pairwise_within_fill: offsets int64 [n + 1], device memory — for a call with the same
+ *   arguments the running sums of the counts (offsets[0] = 0, offsets[n] = the entries that
+ *   indices and values hold).  Row i's hits go to [offsets[i], offsets[i + 1]) of indices int32
+ *   and values float32, in ASCENDING b-row order, the value next to its index.  The fill never
+ *   writes outside that segment whatever offsets holds: a segment is clipped to ascending order
+ *   and to [0, offsets[n]], a hit that does not fit is dropped, and *status (int32, one word,
+ *   device memory, zeroed by the call) is set non-zero — also when a row has fewer hits than
+ *   its segment is long.  Stale or wrong offsets are a reported error, never a stray store; the
+ *   entries of a segment longer than its row's hits are left as they were.
+ *   Cost: two sweeps, each the MFMA work of gfy_pairwise_nearest at 128 a-rows per workgroup
+ *   with a lighter epilogue (the count: one comparison per pair; the fill: one maximum per 16
+ *   pairs and the stores of the hits), one integer atomic per wave and a-row; then one wave per
+ *   a-row orders its segment — in registers up to 64 hits, in LDS up to 2,048, beyond that in
+ *   place in global memory, which is correct and not meant to be fast.  Measured once
+ *   (tools/bench_within.py, 262,144 x 262,144 unit rows, about 10 hits per row): the count 1.3 x
+ *   the time of gfy_pairwise_nearest, count + offsets + fill + order 2.7 x; nothing else is.
+ *   Workspace: gfy_pairwise_within_workspace_bytes(n, m), the same for both calls.
+ *   gfy_pairwise_within_chunks(n, m) tells into how many chunks a call of that shape cuts b.
+ *   The checks are those of gfy_pairwise_topk; besides, n above 2^31 - 2, a threshold that is
+ *   not finite and one skip pointer without the other are GFY_ERR_INVALID before any launch.  */
+size_t gfy_pairwise_within_workspace_bytes(int64_t n, int64_t m);
+int gfy_pairwise_within_chunks(int64_t n, int64_t m);
+int gfy_pairwise_within_count(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                              float threshold, const int32_t* skip_lo, const int32_t* skip_hi,
+                              int32_t* counts, void* workspace, size_t workspace_bytes,
+                              void* stream);
+int gfy_pairwise_within_fill(const void* a, int64_t n, const void* b, int64_t m, int metric,
+                             float threshold, const int32_t* skip_lo, const int32_t* skip_hi,
+                             const int64_t* offsets, int32_t* indices, float* values,
+                             int32_t* status, void* workspace, size_t workspace_bytes,
+                             void* stream);
+
 /* Batched local alignment of record pairs: Smith-Waterman with affine gaps (Gotoh) over the
  * cosine of the records' rows, the step behind the ranking of gfy_pairwise_record_scores.  The
  * L_q x L_r matrix of a pair is never written to memory.

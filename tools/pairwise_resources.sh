@@ -3,6 +3,7 @@
 #   bash tools/pairwise_resources.sh [extra hipcc flags]
 #   GFY_SOURCE=pairwise_topk.hip bash tools/pairwise_resources.sh     # the top-k kernels
 #   GFY_SOURCE=pairwise_topk_ranges.hip bash tools/pairwise_resources.sh   # ... with per-row ranges
+#   GFY_SOURCE=pairwise_within.hip bash tools/pairwise_resources.sh   # the radius search (count, fill, order)
 #   GFY_SOURCE=align_local.hip bash tools/pairwise_resources.sh       # the local aligner (no scratch, no barrier)
 #   GFY_SOURCE=align_span.hip bash tools/pairwise_resources.sh        # ... with start cells
 # Per kernel: registers, spills, scratch, and how many MFMA, LDS-DMA, 16-byte LDS read and barrier
