@@ -3,13 +3,13 @@
 // every record of b, and the mean of those over the rows of every record of a, without ever
 // writing the n x m matrix.
 //
-// The sweep is the shared one of pairwise_sweep.inc in the shape of k_pairwise_topk (told at the head
-// of pairwise_topk.hip): 128 a-rows per workgroup (8 waves, 2 x 4, a wave holds 64 a-rows against 32 b-rows of every
-// tile), b in 128-row tiles by LDS-DMA into the ring of four, two tiles per barrier, the next
-// pair requested behind the first multiply, the a-row on the MFMA lane with 16 values per lane
-// and a-row slot.  The pair's value g (maximised) is computed exactly as there and in the
-// nearest-row kernel:  L2  g = a.b - |b|^2 / 2  out of the MFMAs,  cosine  g = -fma(a.b, -1/|b|, 0).
-// What differs is the epilogue: instead of a k-deep list, ONE running maximum per lane and a-row
+// The sweep and the 128-row block are the shared ones of pairwise_sweep.inc (BlockFrame: 8
+// waves, 2 x 4, a wave holds 64 a-rows against 32 b-rows of every tile), b in 128-row tiles by
+// LDS-DMA into the ring of four, two tiles per barrier, the next pair requested behind the first
+// multiply, the a-row on the MFMA lane with 16 values per lane and a-row slot.  The pair's value
+// g (maximised) is computed exactly as in top-k and in the nearest-row kernel:  L2
+// g = a.b - |b|^2 / 2  out of the MFMAs,  cosine  g = -fma(a.b, -1/|b|, 0) (cosine_key).
+// What is here is the epilogue: instead of a k-deep list, ONE running maximum per lane and a-row
 // slot, which belongs to the record of b the sweep is in.
 //   * The records' boundaries (ptr_b, running sums) are the same for the whole workgroup: the
 //     current record, its end and the next record's end are wave-uniform and live in SGPRs.
@@ -40,17 +40,9 @@
 namespace gfy {
 namespace {
 
-constexpr int kBlockA = 128;  // a-rows per workgroup
 constexpr uint32_t kBelowAll = 0x007fffffu;    // ordered(-inf)
 
-struct RecordArgs {
-  const f16* a;
-  const f16* b;
-  const float* s;       // [m] padded to whole tiles (k_row_terms)
-  const float* t;
-  int64_t n, m;
-  int blocks_a, chunks;
-  int64_t chunk_rows;   // multiple of kTileB
+struct RecordArgs : SweepArgs {
   const int32_t* ptr_b; // [records_b + 1] running sums
   int records_b;
   uint32_t* bits;       // [records_b][n]: ordered(max g)
@@ -67,15 +59,6 @@ __device__ __forceinline__ float max16_inside(const f32x16& g, int jb, int from,
   return high;
 }
 
-// fp32 -> uint32, monotone: x < y  <=>  ordered(x) < ordered(y) (no NaN comes out of the sweep)
-__device__ __forceinline__ uint32_t ordered(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float unordered(uint32_t u) {
-  return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu));
-}
-
 // the value of k_nearest_finish for the maximum g of an (a-row, record) pair: the key is -2 g (L2)
 // or -g (cosine), both exact
 __device__ __forceinline__ float value_of(uint32_t bits, float a_term, int metric) {
@@ -88,30 +71,18 @@ __global__ __launch_bounds__(kThreads, 1) void k_record_sweep(const RecordArgs p
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int r = lane & 31, hq = lane >> 5;
-  // wave owns a-rows [64wa, 64wa+64) and b-rows [32wb, 32wb+32) of each tile
-  const int wa = wave & 1, wb = wave >> 1;
-  const int chunk = blockIdx.x / p.blocks_a;
-  const int block_a = blockIdx.x - chunk * p.blocks_a;
-  const int64_t a0 = (int64_t)block_a * kBlockA;
-  const int64_t j_begin = (int64_t)chunk * p.chunk_rows;
-  const int64_t j_end = j_begin + p.chunk_rows < p.m ? j_begin + p.chunk_rows : p.m;
+  const BlockFrame f = block_frame(p);
+  const int lane = f.lane, r = f.r, hq = f.hq, wa = f.wa, wb = f.wb, tiles = f.tiles;
+  const int64_t a0 = f.a0, j_begin = f.j_begin, j_end = f.j_end;
 
   auto request = [&](int k) __attribute__((always_inline)) {
-    sweep_request<kFold>(p, lds0, wave, j_begin, k);
+    sweep_request<kFold>(p, lds0, f.wave, j_begin, k);
   };
 
-  stage_a_block<kBlockA>(smem, p.a, p.n, a0);
-  if (j_begin < j_end) request(0);
-  __syncthreads();
+  stage_a_block<kFrameA>(smem, p.a, p.n, a0);
   f16x8 af[2][8];
-  load_a_fragments<2>(af, smem, wa, r, hq);
-
-  __syncthreads();   // the a-block has left buffer 1
-  const int tiles = j_begin < j_end ? (int)((j_end - j_begin + kTileB - 1) / kTileB) : 0;
-  if (tiles > 1) request(1);
+  load_block_fragments(af, smem, f, request);
+  release_a_block(f, request);
 
   // The record the sweep is in: the first one that ends behind j_begin (records of zero rows in
   // front of it own nothing), found by bisection over the running sums; then its end and the
@@ -146,7 +117,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_record_sweep(const RecordArgs p
   };
 
   f32x16 acc[2];   // [at]
-  const int jw = 32 * wb + 4 * hq;   // first of this lane's b-rows inside a tile
+  const int jw = f.jw;   // first of this lane's b-rows inside a tile
   auto multiply = [&](int k) __attribute__((always_inline)) {
     sweep_multiply<2, kFold>(acc, af, smem, k, wb, r, hq);
   };
@@ -158,22 +129,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_record_sweep(const RecordArgs p
     const int jb = j0 + jw;
     const int w_lo = j0 + 32 * wb, w_hi = w_lo + 32;   // this wave's b-rows
     __builtin_amdgcn_sched_barrier(0);
-    if constexpr (!kFold) {
-      const float* s_l = sweep_terms(smem, k);
-      const float* t_l = s_l + kTileB;
+    if constexpr (!kFold) {   // both a-row slots ahead of the segments, which read either
 #pragma unroll
-      for (int at = 0; at < 2; ++at)
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + jw + 8 * q4);
-          const f32x4 tv = *reinterpret_cast<const f32x4*>(t_l + jw + 8 * q4);
-          f32x4 a4;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) a4[i] = acc[at][4 * q4 + i];
-          const f32x4 key = __builtin_elementwise_fma(a4, sv, tv);   // the key of k_pairwise<false>
-#pragma unroll
-          for (int i = 0; i < 4; ++i) acc[at][4 * q4 + i] = -key[i];
-        }
+      for (int at = 0; at < 2; ++at) cosine_key(acc[at], smem, k, jw);
     }
     int seg_lo = j0;
     for (;;) {   // the segments of the tile, wave-uniform
@@ -259,18 +217,15 @@ __global__ __launch_bounds__(256) void k_record_finish_scores(
     scores[q * records_b + r0 + t] = (float)(sum / (double)(hi - lo));   // no rows: 0 / 0 = NaN
 }
 
-struct RecordWorkspace {
-  float *s, *t, *a_term;
+struct RecordWorkspace : SweepWorkspace {
   uint32_t* bits;
-  BSplit split;
-  size_t bytes;
 };
 
 // Layout: the terms (pairwise_sweep.inc), then bits ([records_b][n] words)
 RecordWorkspace carve_records(void* base, int64_t n, int64_t m, int64_t records_b) {
   RecordWorkspace w;
   Carver carver{base};
-  w.split = split_b(n, m, kBlockA);
+  w.split = split_b(n, m, kFrameA);
   carver.terms(n, m, w.s, w.t, w.a_term);
   w.bits = (uint32_t*)carver.take((size_t)records_b * (size_t)n * 4);
   w.bytes = carver.bytes;
@@ -283,7 +238,7 @@ size_t pairwise_record_workspace_bytes(int64_t n, int64_t m, int64_t records_b) 
   return carve_records(nullptr, n, m, records_b).bytes;
 }
 
-int pairwise_record_chunks(int64_t n, int64_t m) { return split_b(n, m, kBlockA).chunks; }
+int pairwise_record_chunks(int64_t n, int64_t m) { return split_b(n, m, kFrameA).chunks; }
 
 // ptr_a == nullptr: out is best [n][records_b]; else out is scores [records_a][records_b]
 int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, int metric,
@@ -292,26 +247,11 @@ int launch_pairwise_records(const void* a, int64_t n, const void* b, int64_t m, 
                             hipStream_t s) {
   const char* who = ptr_a ? "gfy_pairwise_record_scores" : "gfy_pairwise_record_best";
   const RecordWorkspace w = carve_records(ws, n, m, records_b);
-  GFY_REQUIRE(ws_bytes >= w.bytes, GFY_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who,
-              ws_bytes, w.bytes);
-  const int64_t padded_m = (m + kTileB - 1) / kTileB * kTileB;
+  RecordArgs p{};
+  if (const int rc = begin_sweep(who, w, ws_bytes, a, n, b, m, metric, s, p)) return rc;
   const bool fold = metric == GFY_L2;
-  if (const int rc = launch_pairwise_row_terms(b, m, padded_m, metric, fold, w.s, w.t, nullptr, s))
-    return rc;
-  if (const int rc = launch_pairwise_row_terms(a, n, n, metric, 0, nullptr, nullptr, w.a_term, s))
-    return rc;
   GFY_CHECK_HIP(hipMemsetD32Async((hipDeviceptr_t)w.bits, (int)kBelowAll,
                                   (size_t)records_b * (size_t)n, s));
-  RecordArgs p{};
-  p.a = (const f16*)a;
-  p.b = (const f16*)b;
-  p.s = w.s;
-  p.t = w.t;
-  p.n = n;
-  p.m = m;
-  p.blocks_a = w.split.blocks_a;
-  p.chunks = w.split.chunks;
-  p.chunk_rows = w.split.chunk_rows;
   p.ptr_b = ptr_b;
   p.records_b = (int)records_b;
   p.bits = w.bits;

@@ -1,9 +1,16 @@
-// The all-pairs sweep that nearest (pairwise.hip), top-k (pairwise_topk.inc) and the record
-// scores (pairwise_records.hip) share — the ONLY copy of: the b-tile ring and its LDS-DMA request,
-// the staging of the a-block, the MFMA multiply of one tile, the two-tiles-per-barrier loop, the
-// value formula, the split of b into chunks, the front of the workspace and the launch with
-// more than 64 KB of LDS.  Included after gfy_common.h; everything is inlined into the kernels of
-// the including file, whose a-block size (kBlockA: 256 or 128 rows) and epilogue are their own.
+// The all-pairs sweep that nearest (pairwise.hip), top-k (pairwise_topk.inc), the record scores
+// (pairwise_records.hip) and the radius search (pairwise_within.hip) share — the ONLY copy of:
+// the b-tile ring and its LDS-DMA request, the staging of the a-block, the MFMA multiply of one
+// tile, the two-tiles-per-barrier loop, the value formula, the split of b into chunks, the front
+// of the workspace and the launch with more than 64 KB of LDS.  For the kernels on a 128-row
+// a-block (all but nearest) also: kFrameA, kRangeBytes, kNoIndex, the cosine key, the mask of a
+// skip range, ordered / unordered and on the host the launchers' prologue (begin_sweep); and for
+// k_record_sweep and the radius sweep the common argument fields (SweepArgs), the block geometry
+// (BlockFrame), the front of the kernel up to the request of tile 1 and the staging and union of
+// the skip ranges.  k_pairwise_topk keeps its own copy of those last pieces and its own argument
+// layout: with them shared, three of its instantiations measured 0.7 to 1.0 % slower, their tile
+// loops unchanged (profiles/sweep_frame_refactor_ab.txt).  Included after gfy_common.h;
+// everything is inlined into the kernels of the including file, whose epilogue is their own.
 //
 // A workgroup of 8 waves keeps the MFMA fragments of its a-block in registers and sweeps its
 // chunk of b in 128-row tiles that LDS-DMA lands in a ring of four buffers, XOR-swizzled so that
@@ -214,6 +221,167 @@ __device__ __forceinline__ void sweep_tile_pairs(int tiles, Multiply&& multiply,
   }
 }
 
+// ---- the 128-row block -------------------------------------------------------------------------
+// What the kernels on a 128-row a-block share above the sweep: k_record_sweep and the radius
+// search's within_sweep all of it, k_pairwise_topk the constants, cosine_key, mask_skip_range and
+// begin_sweep.  (k_pairwise, 256 rows, keeps its own body.)
+
+// The fields every sweep's argument struct starts with; RecordArgs and WithinArgs derive from it
+// (TopkArgs holds the same nine under the same names, in the order its kernels were built for)
+struct SweepArgs {
+  const f16* a;
+  const f16* b;
+  const float* s;       // [m] padded to whole tiles (k_row_terms)
+  const float* t;
+  int64_t n, m;
+  int blocks_a, chunks;
+  int64_t chunk_rows;   // multiple of kTileB
+};
+
+constexpr int kFrameA = 128;                // a-rows per workgroup
+constexpr int kRangeBytes = kFrameA * 8;    // (first, count) of every a-row, behind the rings
+constexpr int kNoIndex = 0x7fffffff;
+
+// Where a thread and its workgroup stand: workgroup (block_a, chunk) sweeps the b-rows
+// [j_begin, j_end) in `tiles` tiles against the a-rows from a0 on.  A wave owns the a-rows
+// [64 wa, 64 wa + 64) and the b-rows [32 wb, 32 wb + 32) of every tile; a lane holds, per a-row
+// slot `at`, a-row 64 wa + 32 at + r against the 16 b-rows jw + 8 (q >> 2) + (q & 3) of a tile.
+struct BlockFrame {
+  int t, lane, wave, r, hq, wa, wb, jw;
+  int chunk;
+  int64_t a0, j_begin, j_end;
+  int tiles;
+};
+
+__device__ __forceinline__ BlockFrame block_frame(const SweepArgs& p) {
+  BlockFrame f;
+  f.t = threadIdx.x;
+  f.lane = f.t & 63;
+  f.wave = __builtin_amdgcn_readfirstlane(f.t >> 6);
+  f.r = f.lane & 31;
+  f.hq = f.lane >> 5;
+  f.wa = f.wave & 1;
+  f.wb = f.wave >> 1;
+  f.jw = 32 * f.wb + 4 * f.hq;
+  f.chunk = blockIdx.x / p.blocks_a;
+  const int block_a = blockIdx.x - f.chunk * p.blocks_a;
+  f.a0 = (int64_t)block_a * kFrameA;
+  f.j_begin = (int64_t)f.chunk * p.chunk_rows;
+  f.j_end = f.j_begin + p.chunk_rows < p.m ? f.j_begin + p.chunk_rows : p.m;
+  f.tiles = f.j_begin < f.j_end ? (int)((f.j_end - f.j_begin + kTileB - 1) / kTileB) : 0;
+  return f;
+}
+
+// The front of every kernel, in three steps with the kernel's own set-up in between:
+//   stage_a_block<kFrameA>     the a-block into the ring; then what the kernel itself puts into LDS
+//   load_block_fragments       request tile 0, barrier, the fragments into registers; then what
+//                              the kernel reads back from LDS (skip_union)
+//   release_a_block            barrier: the a-block has left buffer 1; request tile 1
+template <class Request>
+__device__ __forceinline__ void load_block_fragments(f16x8 (&af)[2][8], const char* smem,
+                                                     const BlockFrame& f, Request&& request) {
+  if (f.j_begin < f.j_end) request(0);
+  __syncthreads();
+  load_a_fragments<2>(af, smem, f.wa, f.r, f.hq);
+}
+
+template <class Request>
+__device__ __forceinline__ void release_a_block(const BlockFrame& f, Request&& request) {
+  __syncthreads();
+  if (f.tiles > 1) request(1);
+}
+
+// Per-row skip ranges.  Every a-row's range [skip_lo[i], skip_hi[i]), clipped to [0, m), as
+// (first, count) with 0 <= first and first + count <= m < 2^31 (count 0: nothing, also for the
+// rows past n); it stays in LDS behind the rings for the whole sweep, so that a tile that needs
+// it reads two words per a-row slot and no register holds a bound in between.  In front of the
+// first barrier.
+__device__ __forceinline__ int2* skip_ranges(char* smem) {
+  return reinterpret_cast<int2*>(smem + kSweepLds);
+}
+
+__device__ __forceinline__ void stage_skip_ranges(int2* ranges, const int32_t* skip_lo,
+                                                  const int32_t* skip_hi, const SweepArgs& p,
+                                                  const BlockFrame& f) {
+  if (f.t < kFrameA) {
+    int lo = 0, hi = 0;
+    if (f.a0 + f.t < p.n) {
+      lo = skip_lo[f.a0 + f.t];
+      hi = skip_hi[f.a0 + f.t];
+    }
+    lo = lo > 0 ? lo : 0;
+    hi = hi < (int)p.m ? hi : (int)p.m;
+    ranges[f.t] = lo < hi ? int2{lo, hi - lo} : int2{0, 0};
+  }
+}
+
+// [from, to): the union of the block's non-empty ranges, the same in every wave and held in
+// SGPRs; a tile outside it takes the path of a kernel without ranges.  Empty until skip_union
+// has run (behind the first barrier).
+struct SkipUnion {
+  int from = kNoIndex, to = 0;
+  __device__ __forceinline__ bool meets_tile(int64_t j0) const {
+    return from < j0 + kTileB && to > j0;
+  }
+};
+
+__device__ __forceinline__ SkipUnion skip_union(const int2* ranges, int lane) {
+  SkipUnion u;
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int2 range = ranges[64 * half + lane];
+    u.from = range.y > 0 && range.x < u.from ? range.x : u.from;
+    u.to = range.y > 0 && range.x + range.y > u.to ? range.x + range.y : u.to;
+  }
+#pragma unroll
+  for (int step = 32; step > 0; step >>= 1) {
+    const int from = __shfl_xor(u.from, step), to = __shfl_xor(u.to, step);
+    u.from = from < u.from ? from : u.from;
+    u.to = to > u.to ? to : u.to;
+  }
+  u.from = __builtin_amdgcn_readfirstlane(u.from);
+  u.to = __builtin_amdgcn_readfirstlane(u.to);
+  return u;
+}
+
+// The lane's values of one a-row whose b-row lies in `range` (an entry of skip_ranges) to -inf;
+// jb is the lane's first b-row of the tile.  b-row j is skipped iff first <= j < first + count:
+// one unsigned comparison, since 0 <= first <= first + count < 2^31 (the padded rows of a ragged
+// tile lie past m).
+__device__ __forceinline__ void mask_skip_range(f32x16& g, int2 range, int jb) {
+#pragma unroll
+  for (int q = 0; q < 16; ++q)
+    g[q] = (uint32_t)(jb + 8 * (q >> 2) + (q & 3) - range.x) < (uint32_t)range.y
+               ? -__builtin_inff() : g[q];
+}
+
+// Cosine: one a-row's 16 products of tile k into g = -key in place, key = fma(dot, s, t) being
+// the key of k_pairwise<false>.  (L2 has g out of the MFMAs: kFold.)
+__device__ __forceinline__ void cosine_key(f32x16& g, const char* smem, int k, int jw) {
+  const float* s_l = sweep_terms(smem, k);
+  const float* t_l = s_l + kTileB;
+#pragma unroll
+  for (int q4 = 0; q4 < 4; ++q4) {
+    const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + jw + 8 * q4);
+    const f32x4 tv = *reinterpret_cast<const f32x4*>(t_l + jw + 8 * q4);
+    f32x4 a4;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) a4[i] = g[4 * q4 + i];
+    const f32x4 key = __builtin_elementwise_fma(a4, sv, tv);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g[4 * q4 + i] = -key[i];
+  }
+}
+
+// fp32 <-> uint32, monotone: x < y  <=>  ordered(x) < ordered(y) (no NaN comes out of a sweep)
+__device__ __forceinline__ uint32_t ordered(float x) {
+  const uint32_t u = __float_as_uint(x);
+  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
+}
+__device__ __forceinline__ float unordered(uint32_t u) {
+  return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu));
+}
+
 // ---- host side ---------------------------------------------------------------------------------
 
 // How a sweep of n a-rows (in blocks of block_a) against m b-rows is cut: b into `chunks` pieces
@@ -270,6 +438,40 @@ struct Carver {
     a_term = (float*)take((size_t)n * 4);
   }
 };
+
+// The front of a 128-row sweep's carved workspace (Carver::terms) with the split it was carved
+// for and the size of the whole; a search's own workspace derives from it and adds its arrays.
+struct SweepWorkspace {
+  float *s, *t, *a_term;
+  BSplit split;
+  size_t bytes;
+};
+
+// What every launcher of a 128-row sweep starts with: refuse a workspace shorter than the carved
+// one, launch the row terms of b (folded for L2: the kFold kernels) and of a, and fill the common
+// argument fields of `p` (a SweepArgs, or TopkArgs with the same nine names).
+template <class Args>
+int begin_sweep(const char* who, const SweepWorkspace& w, size_t ws_bytes, const void* a, int64_t n,
+                const void* b, int64_t m, int metric, hipStream_t s, Args& p) {
+  GFY_REQUIRE(ws_bytes >= w.bytes, GFY_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who,
+              ws_bytes, w.bytes);
+  const int64_t padded_m = (m + kTileB - 1) / kTileB * kTileB;
+  const bool fold = metric == GFY_L2;
+  if (const int rc = launch_pairwise_row_terms(b, m, padded_m, metric, fold, w.s, w.t, nullptr, s))
+    return rc;
+  if (const int rc = launch_pairwise_row_terms(a, n, n, metric, 0, nullptr, nullptr, w.a_term, s))
+    return rc;
+  p.a = (const f16*)a;
+  p.b = (const f16*)b;
+  p.s = w.s;
+  p.t = w.t;
+  p.n = n;
+  p.m = m;
+  p.blocks_a = w.split.blocks_a;
+  p.chunks = w.split.chunks;
+  p.chunk_rows = w.split.chunk_rows;
+  return GFY_OK;
+}
 
 // kKernel<<<grid, kThreads, kLds>>>(p) with more than 64 KB of dynamic LDS: the opt-in once per
 // device and kernel, thread-safe (PerDeviceOnce, gfy_common.h)

@@ -52,11 +52,9 @@ __global__ __launch_bounds__(256) void k_topk_finish(const float* __restrict__ p
                      top_idx);
 }
 
-struct TopkWorkspace {
-  float *s, *t, *a_term, *part_key;
+struct TopkWorkspace : SweepWorkspace {
+  float* part_key;
   int32_t* part_idx;
-  BSplit split;
-  size_t bytes;
 };
 
 // Layout: the terms (pairwise_sweep.inc), then part_key and part_idx ([chunks][n][k] each); the
@@ -64,7 +62,7 @@ struct TopkWorkspace {
 TopkWorkspace carve_topk(void* base, int64_t n, int64_t m, int k) {
   TopkWorkspace w;
   Carver carver{base};
-  w.split = split_b(n, m, kBlockA);
+  w.split = split_b(n, m, kFrameA);
   carver.terms(n, m, w.s, w.t, w.a_term);
   w.part_key = (float*)carver.take((size_t)w.split.chunks * n * k * 4);
   w.part_idx = (int32_t*)carver.take((size_t)w.split.chunks * n * k * 4);
@@ -84,26 +82,12 @@ int launch_pairwise_topk(const void* a, int64_t n, const void* b, int64_t m, int
                          float* top_val, int32_t* top_idx, void* ws, size_t ws_bytes,
                          hipStream_t s) {
   const TopkWorkspace w = carve_topk(ws, n, m, k);
-  GFY_REQUIRE(ws_bytes >= w.bytes, GFY_ERR_WORKSPACE,
-              "gfy_pairwise_topk: workspace %zu < required %zu", ws_bytes, w.bytes);
-  const int64_t padded_m = (m + kTileB - 1) / kTileB * kTileB;
-  const bool fold = metric == GFY_L2;
-  if (const int rc = launch_pairwise_row_terms(b, m, padded_m, metric, fold, w.s, w.t, nullptr, s))
-    return rc;
-  if (const int rc = launch_pairwise_row_terms(a, n, n, metric, 0, nullptr, nullptr, w.a_term, s))
-    return rc;
   TopkArgs p{};
-  p.a = (const f16*)a;
-  p.b = (const f16*)b;
-  p.s = w.s;
-  p.t = w.t;
-  p.n = n;
-  p.m = m;
+  if (const int rc = begin_sweep("gfy_pairwise_topk", w, ws_bytes, a, n, b, m, metric, s, p))
+    return rc;
+  const bool fold = metric == GFY_L2;
   p.exclude_offset = exclude_offset;
   p.exclude_on = exclude_on;
-  p.blocks_a = w.split.blocks_a;
-  p.chunks = w.split.chunks;
-  p.chunk_rows = w.split.chunk_rows;
   p.k = k;
   p.part_key = w.part_key;
   p.part_idx = w.part_idx;

@@ -1,7 +1,8 @@
 // The sweep of the exact top-k search: k_pairwise_topk<D, kFold, kRanges, kDistinct>, its
 // launcher and the merge of the chunks' lists, topk_finish<kDistinct> (the design is told at the
-// head of pairwise_topk.hip; the ring, the tile request, the multiply and the tile loop are those
-// of pairwise_sweep.inc).
+// head of pairwise_topk.hip; the sweep, the cosine key and the mask of a skip range are those of
+// pairwise_sweep.inc; the block geometry, the front of the kernel and the staging and union of
+// the ranges are this kernel's own, as is its argument layout: told at the head of that file).
 // Included by the three translation units that instantiate it: pairwise_topk.hip (kRanges =
 // false: one excluded pair per a-row at most), pairwise_topk_ranges.hip (kRanges = true: an
 // excluded range of b-rows per a-row) and pairwise_topk_distinct.hip (kDistinct = true: at most
@@ -40,13 +41,10 @@ int launch_topk_finish_distinct(const TopkArgs& p, const float* a_term, int metr
 
 namespace {
 
-constexpr int kBlockA = 128;  // a-rows per workgroup
-constexpr int kRangeBytes = kBlockA * 8;       // kRanges: (first, count) of every a-row, behind the rings
 constexpr int kGroupBytes = 2 * kTileB * 4;    // kDistinct: (group_lo, group_hi) of a b-tile, a
 constexpr int kGroupSlots = 4;                 // ring like that of the terms, behind the ranges
 constexpr int kHolders = 8;                    // lists per a-row at the end of a sweep
-constexpr int kNoIndex = 0x7fffffff;
-static_assert(kHolders * GFY_PAIRWISE_TOPK_MAX * kBlockA * 8 <= kBuffers * kRowBytes,
+static_assert(kHolders * GFY_PAIRWISE_TOPK_MAX * kFrameA * 8 <= kBuffers * kRowBytes,
               "the holders' lists are merged in the row ring");
 
 // (ck, ci) into a list sorted by g descending; the entry that falls off the end is dropped.
@@ -118,7 +116,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
   const int wa = wave & 1, wb = wave >> 1;
   const int chunk = blockIdx.x / p.blocks_a;
   const int block_a = blockIdx.x - chunk * p.blocks_a;
-  const int64_t a0 = (int64_t)block_a * kBlockA;
+  const int64_t a0 = (int64_t)block_a * kFrameA;
   const int64_t j_begin = (int64_t)chunk * p.chunk_rows;
   const int64_t j_end = j_begin + p.chunk_rows < p.m ? j_begin + p.chunk_rows : p.m;
 
@@ -143,14 +141,14 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
     }
   };
 
-  stage_a_block<kBlockA>(smem, p.a, p.n, a0);
+  stage_a_block<kFrameA>(smem, p.a, p.n, a0);
   // kRanges: every a-row's range, clipped to [0, m), as (first, count) with 0 <= first and
   // first + count <= m < 2^31 (count 0: nothing, also for the rows past n); it stays in LDS
   // behind the rings for the whole sweep, so that a tile that needs it reads two words per
   // a-row slot and no register holds a bound in between
   int2* const ranges = reinterpret_cast<int2*>(smem + kSweepLds);
   if constexpr (kRanges) {
-    if (t < kBlockA) {
+    if (t < kFrameA) {
       int lo = 0, hi = 0;
       if (a0 + t < p.n) {
         lo = p.skip_lo[a0 + t];
@@ -210,7 +208,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
   auto reduce = [&](int k) __attribute__((always_inline)) {
     const int64_t j0 = j_begin + (int64_t)k * kTileB;
     // does this tile contain an excluded (i, i + offset) pair of this block?
-    const int64_t ex_lo = a0 + p.exclude_offset, ex_hi = ex_lo + kBlockA;
+    const int64_t ex_lo = a0 + p.exclude_offset, ex_hi = ex_lo + kFrameA;
     const bool may_exclude = !kRanges && p.exclude_on && ex_lo < j0 + kTileB && ex_hi > j0;
     // kRanges: does it meet the union of the block's ranges?
     const bool may_skip = kRanges && skip_from < j0 + kTileB && skip_to > j0;
@@ -220,21 +218,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
     for (int at = 0; at < 2; ++at) {
       __builtin_amdgcn_sched_barrier(0);   // one a-row at a time: its terms are not read early
       f32x16& g = acc[at];   // one a-row's 16 values at a time, in place: the products are spent
-      if constexpr (!kFold) {
-        const float* s_l = sweep_terms(smem, k);
-        const float* t_l = s_l + kTileB;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + jw + 8 * q4);
-          const f32x4 tv = *reinterpret_cast<const f32x4*>(t_l + jw + 8 * q4);
-          f32x4 a4;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) a4[i] = g[4 * q4 + i];
-          const f32x4 key = __builtin_elementwise_fma(a4, sv, tv);   // the key of k_pairwise<false>
-#pragma unroll
-          for (int i = 0; i < 4; ++i) g[4 * q4 + i] = -key[i];
-        }
-      }
+      if constexpr (!kFold) cosine_key(g, smem, k, jw);
       if (may_exclude) {   // block-uniform, at most two tiles per block
         // the one excluded b-row of this a-row, as a position among the lane's 16 values
         const int64_t off = (a0 + p.exclude_offset - j0) + (64 * wa + 32 * at + r - jw);
@@ -243,15 +227,8 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
 #pragma unroll
         for (int q = 0; q < 16; ++q) g[q] = q == slot ? -__builtin_inff() : g[q];
       }
-      if (may_skip) {   // block-uniform: the tiles under the block's own records, or every tile
-        // b-row j is skipped iff first <= j < first + count: one unsigned comparison, since
-        // 0 <= first <= first + count < 2^31 (the padded rows of a ragged tile lie past m)
-        const int2 range = ranges[64 * wa + 32 * at + r];
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          g[q] = (uint32_t)(jb + 8 * (q >> 2) + (q & 3) - range.x) < (uint32_t)range.y
-                     ? -__builtin_inff() : g[q];
-      }
+      if (may_skip)   // block-uniform: the tiles under the block's own records, or every tile
+        mask_skip_range(g, ranges[64 * wa + 32 * at + r], jb);
       float high = max16(g);
       bool better = high > lk[at][D - 1];   // strict: an earlier b-row keeps a tie
       while (__ballot(better)) {            // wave-uniform; rare once the sweep has settled
@@ -285,17 +262,17 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
   // [holder][position][a-row]: a lane's stores and the merging thread's reads (at a position
   // of its own) both touch 32 consecutive words
   float* m_key = reinterpret_cast<float*>(smem);
-  int* m_idx = reinterpret_cast<int*>(smem + kHolders * D * kBlockA * 4);
+  int* m_idx = reinterpret_cast<int*>(smem + kHolders * D * kFrameA * 4);
 #pragma unroll
   for (int at = 0; at < 2; ++at)
 #pragma unroll
     for (int q = 0; q < D; ++q) {
-      const int at_row = ((2 * wb + hq) * D + q) * kBlockA + 64 * wa + 32 * at + r;
+      const int at_row = ((2 * wb + hq) * D + q) * kFrameA + 64 * wa + 32 * at + r;
       m_key[at_row] = lk[at][q];
       m_idx[at_row] = li[at][q];
     }
   __syncthreads();
-  if (t < kBlockA && a0 + t < p.n) {
+  if (t < kFrameA && a0 + t < p.n) {
     uint64_t heads = 0;   // 8 bits per holder: entries taken from its list
     float* out_key = p.part_key + ((int64_t)chunk * p.n + a0 + t) * p.k;
     int32_t* out_idx = p.part_idx + ((int64_t)chunk * p.n + a0 + t) * p.k;
@@ -309,8 +286,8 @@ __global__ __launch_bounds__(kThreads, 1) void k_pairwise_topk(const TopkArgs p)
       for (int h = 0; h < kHolders; ++h) {
         const int pos = (int)((heads >> (8 * h)) & 0xffu);
         if (pos < D) {
-          const float hk = m_key[(h * D + pos) * kBlockA + t];
-          const int hi = m_idx[(h * D + pos) * kBlockA + t];
+          const float hk = m_key[(h * D + pos) * kFrameA + t];
+          const int hi = m_idx[(h * D + pos) * kFrameA + t];
           if (hk > bk || (hk == bk && hi < bi)) {
             bk = hk;
             bi = hi;

@@ -3,12 +3,12 @@
 // ever writing the n x m matrix.  Two sweeps: one counts, the caller turns the counts into
 // offsets, the other writes the hits into the segments the offsets describe.
 //
-// The sweep is the shared one of pairwise_sweep.inc in the shape of k_pairwise_topk and
-// k_record_sweep: 128 a-rows per workgroup (8 waves, 2 x 4, a wave holds 64 a-rows against 32
-// b-rows of every tile), b in 128-row tiles by LDS-DMA into the ring of four, two tiles per
-// barrier, the a-row on the MFMA lane with 16 values per lane and a-row slot.  The pair's g
-// (maximised) is computed exactly as there:  L2  g = a.b - |b|^2 / 2  out of the MFMAs,
-// cosine  g = -fma(a.b, -1/|b|, 0).  What differs is the epilogue.
+// The sweep and the 128-row block are the shared ones of pairwise_sweep.inc (BlockFrame: 8
+// waves, 2 x 4, a wave holds 64 a-rows against 32 b-rows of every tile), b in 128-row tiles by
+// LDS-DMA into the ring of four, two tiles per barrier, the a-row on the MFMA lane with 16 values
+// per lane and a-row slot.  The pair's g (maximised) is computed exactly as in top-k and the
+// record scores:  L2  g = a.b - |b|^2 / 2  out of the MFMAs,  cosine  g = -fma(a.b, -1/|b|, 0)
+// (cosine_key).  What is here is the epilogue.
 //   * The predicate.  The value of a pair is value(g) = pair_value(-2 g or -g, a_term), and a
 //     pair is a hit iff value <= threshold (L2) / value >= threshold (cosine).  value is
 //     monotone in g for a fixed a-row — fp32 add, a product with a positive term and the
@@ -28,8 +28,8 @@
 //     ascending order (row_segment); a hit whose slot lies past it is dropped and *status is
 //     set, so no store ever leaves the segment whatever offsets holds.  The path is taken per
 //     wave and tile only when a lane has a hit (one max16 and a ballot otherwise).
-//   * Ranges (kRanges): the mask of the top-k range mode — one unsigned comparison per value,
-//     skipped wave-uniformly in the tiles that miss the union of the block's ranges.
+//   * Ranges (kRanges): the skip ranges of pairwise_sweep.inc — one unsigned comparison per
+//     value, skipped wave-uniformly in the tiles that miss the union of the block's ranges.
 //   * Order (k_within_order): the arrival order inside a segment is arbitrary, so one wave per
 //     row sorts its segment by b-row, values moved along — up to 64 entries in registers, up to
 //     kOrderLds in LDS, longer ones in place in global memory with the same network, which is
@@ -43,19 +43,9 @@
 namespace gfy {
 namespace {
 
-constexpr int kBlockA = 128;                // a-rows per workgroup
-constexpr int kRangeBytes = kBlockA * 8;    // kRanges: (first, count) of every a-row, behind the rings
-constexpr int kNoIndex = 0x7fffffff;
 constexpr int kOrderLds = 2048;             // entries k_within_order sorts in LDS (16 KB)
 
-struct WithinArgs {
-  const f16* a;
-  const f16* b;
-  const float* s;       // [m] padded to whole tiles (k_row_terms)
-  const float* t;
-  int64_t n, m;
-  int blocks_a, chunks;
-  int64_t chunk_rows;   // multiple of kTileB
+struct WithinArgs : SweepArgs {
   const int32_t* skip_lo;   // kRanges: a-row i skips the b-rows [skip_lo[i], skip_hi[i]), [n] each
   const int32_t* skip_hi;
   const float* bound;   // [n]: the smallest g that is a hit (k_within_bound)
@@ -67,15 +57,6 @@ struct WithinArgs {
   float* values;
   int32_t* status;
 };
-
-// fp32 <-> uint32, monotone (pairwise_records.hip)
-__device__ __forceinline__ uint32_t ordered(float x) {
-  const uint32_t u = __float_as_uint(x);
-  return u ^ ((u >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float unordered(uint32_t u) {
-  return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu));
-}
 
 // what top-k reports for a pair whose sweep value is g: the key is -2 g (L2) or -g (cosine)
 template <bool kFold>
@@ -129,37 +110,17 @@ __device__ __forceinline__ void within_sweep(const WithinArgs& p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
 
-  const int t = threadIdx.x, lane = t & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int r = lane & 31, hq = lane >> 5;
-  // wave owns a-rows [64wa, 64wa+64) and b-rows [32wb, 32wb+32) of each tile
-  const int wa = wave & 1, wb = wave >> 1;
-  const int chunk = blockIdx.x / p.blocks_a;
-  const int block_a = blockIdx.x - chunk * p.blocks_a;
-  const int64_t a0 = (int64_t)block_a * kBlockA;
-  const int64_t j_begin = (int64_t)chunk * p.chunk_rows;
-  const int64_t j_end = j_begin + p.chunk_rows < p.m ? j_begin + p.chunk_rows : p.m;
+  const BlockFrame f = block_frame(p);
+  const int lane = f.lane, r = f.r, hq = f.hq, wa = f.wa, wb = f.wb;
+  const int64_t a0 = f.a0, j_begin = f.j_begin;
 
   auto request = [&](int k) __attribute__((always_inline)) {
-    sweep_request<kFold>(p, lds0, wave, j_begin, k);
+    sweep_request<kFold>(p, lds0, f.wave, j_begin, k);
   };
 
-  stage_a_block<kBlockA>(smem, p.a, p.n, a0);
-  // kRanges: every a-row's range as (first, count), clipped to [0, m), in LDS behind the rings
-  // for the whole sweep (k_pairwise_topk)
-  int2* const ranges = reinterpret_cast<int2*>(smem + kSweepLds);
-  if constexpr (kRanges) {
-    if (t < kBlockA) {
-      int lo = 0, hi = 0;
-      if (a0 + t < p.n) {
-        lo = p.skip_lo[a0 + t];
-        hi = p.skip_hi[a0 + t];
-      }
-      lo = lo > 0 ? lo : 0;
-      hi = hi < (int)p.m ? hi : (int)p.m;
-      ranges[t] = lo < hi ? int2{lo, hi - lo} : int2{0, 0};
-    }
-  }
+  stage_a_block<kFrameA>(smem, p.a, p.n, a0);
+  int2* const ranges = skip_ranges(smem);
+  if constexpr (kRanges) stage_skip_ranges(ranges, p.skip_lo, p.skip_hi, p, f);
   // the lane's two a-rows' bounds; a row past n gets NaN: never a hit
   float bound[2];
 #pragma unroll
@@ -167,39 +128,17 @@ __device__ __forceinline__ void within_sweep(const WithinArgs& p) {
     const int64_t i = a0 + 64 * wa + 32 * at + r;
     bound[at] = i < p.n ? p.bound[i] : __builtin_nanf("");
   }
-  if (j_begin < j_end) request(0);
-  __syncthreads();
   f16x8 af[2][8];
-  load_a_fragments<2>(af, smem, wa, r, hq);
-
-  // kRanges: [skip_from, skip_to) is the union of the block's non-empty ranges, wave-uniform
-  int skip_from = kNoIndex, skip_to = 0;
-  if constexpr (kRanges) {
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-      const int2 range = ranges[64 * half + lane];
-      skip_from = range.y > 0 && range.x < skip_from ? range.x : skip_from;
-      skip_to = range.y > 0 && range.x + range.y > skip_to ? range.x + range.y : skip_to;
-    }
-#pragma unroll
-    for (int step = 32; step > 0; step >>= 1) {
-      const int from = __shfl_xor(skip_from, step), to = __shfl_xor(skip_to, step);
-      skip_from = from < skip_from ? from : skip_from;
-      skip_to = to > skip_to ? to : skip_to;
-    }
-    skip_from = __builtin_amdgcn_readfirstlane(skip_from);
-    skip_to = __builtin_amdgcn_readfirstlane(skip_to);
-  }
-
-  __syncthreads();   // the a-block has left buffer 1
-  const int tiles = j_begin < j_end ? (int)((j_end - j_begin + kTileB - 1) / kTileB) : 0;
-  if (tiles > 1) request(1);
+  load_block_fragments(af, smem, f, request);
+  SkipUnion skip;
+  if constexpr (kRanges) skip = skip_union(ranges, lane);
+  release_a_block(f, request);
 
   int hits[2] = {0, 0};   // count: per a-row slot, the lane's hits of the chunk
   bool dropped = false;   // fill: a hit of this lane did not fit its row's segment
 
   f32x16 acc[2];   // [at]
-  const int jw = 32 * wb + 4 * hq;   // first of this lane's b-rows inside a tile
+  const int jw = f.jw;   // first of this lane's b-rows inside a tile
   auto multiply = [&](int k) __attribute__((always_inline)) {
     sweep_multiply<2, kFold>(acc, af, smem, k, wb, r, hq);
   };
@@ -207,35 +146,16 @@ __device__ __forceinline__ void within_sweep(const WithinArgs& p) {
   // what happens to the products of tile k (still in acc)
   auto reduce = [&](int k) __attribute__((always_inline)) {
     const int64_t j0 = j_begin + (int64_t)k * kTileB;
-    const bool may_skip = kRanges && skip_from < j0 + kTileB && skip_to > j0;
+    const bool may_skip = kRanges && skip.meets_tile(j0);
     const int jb = (int)(j0 + jw);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int at = 0; at < 2; ++at) {
       __builtin_amdgcn_sched_barrier(0);   // one a-row at a time: its terms are not read early
       f32x16& g = acc[at];   // in place: the products are spent
-      if constexpr (!kFold) {
-        const float* s_l = sweep_terms(smem, k);
-        const float* t_l = s_l + kTileB;
-#pragma unroll
-        for (int q4 = 0; q4 < 4; ++q4) {
-          const f32x4 sv = *reinterpret_cast<const f32x4*>(s_l + jw + 8 * q4);
-          const f32x4 tv = *reinterpret_cast<const f32x4*>(t_l + jw + 8 * q4);
-          f32x4 a4;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) a4[i] = g[4 * q4 + i];
-          const f32x4 key = __builtin_elementwise_fma(a4, sv, tv);   // the key of k_pairwise<false>
-#pragma unroll
-          for (int i = 0; i < 4; ++i) g[4 * q4 + i] = -key[i];
-        }
-      }
-      if (may_skip) {   // block-uniform: the tiles under the block's own ranges
-        const int2 range = ranges[64 * wa + 32 * at + r];
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-          g[q] = (uint32_t)(jb + 8 * (q >> 2) + (q & 3) - range.x) < (uint32_t)range.y
-                     ? -__builtin_inff() : g[q];
-      }
+      if constexpr (!kFold) cosine_key(g, smem, k, jw);
+      if (may_skip)   // block-uniform: the tiles under the block's own ranges
+        mask_skip_range(g, ranges[64 * wa + 32 * at + r], jb);
       if constexpr (!kFill) {
         int c = 0;
 #pragma unroll
@@ -273,7 +193,7 @@ __device__ __forceinline__ void within_sweep(const WithinArgs& p) {
     __builtin_amdgcn_sched_barrier(0);
   };
 
-  sweep_tile_pairs(tiles, multiply, request, reduce);
+  sweep_tile_pairs(f.tiles, multiply, request, reduce);
 
   if constexpr (!kFill) {
     // lane L ends up with the hits of a-row 64 wa + L (slot hq, row r)
@@ -385,18 +305,16 @@ __global__ __launch_bounds__(64) void k_within_order(const int64_t* offsets, con
   }
 }
 
-struct WithinWorkspace {
-  float *s, *t, *a_term, *bound;
+struct WithinWorkspace : SweepWorkspace {
+  float* bound;
   uint32_t* cursor;
-  BSplit split;
-  size_t bytes;
 };
 
 // Layout: the terms (pairwise_sweep.inc), then bound and cursor ([n] words each)
 WithinWorkspace carve_within(void* base, int64_t n, int64_t m) {
   WithinWorkspace w;
   Carver carver{base};
-  w.split = split_b(n, m, kBlockA);
+  w.split = split_b(n, m, kFrameA);
   carver.terms(n, m, w.s, w.t, w.a_term);
   w.bound = (float*)carver.take((size_t)n * 4);
   w.cursor = (uint32_t*)carver.take((size_t)n * 4);
@@ -429,7 +347,7 @@ size_t pairwise_within_workspace_bytes(int64_t n, int64_t m) {
   return carve_within(nullptr, n, m).bytes;
 }
 
-int pairwise_within_chunks(int64_t n, int64_t m) { return split_b(n, m, kBlockA).chunks; }
+int pairwise_within_chunks(int64_t n, int64_t m) { return split_b(n, m, kFrameA).chunks; }
 
 // counts != nullptr: the count; else the fill into (offsets, indices, values, status)
 int launch_pairwise_within(const void* a, int64_t n, const void* b, int64_t m, int metric,
@@ -439,30 +357,15 @@ int launch_pairwise_within(const void* a, int64_t n, const void* b, int64_t m, i
                            hipStream_t s) {
   const char* who = counts ? "gfy_pairwise_within_count" : "gfy_pairwise_within_fill";
   const WithinWorkspace w = carve_within(ws, n, m);
-  GFY_REQUIRE(ws_bytes >= w.bytes, GFY_ERR_WORKSPACE, "%s: workspace %zu < required %zu", who,
-              ws_bytes, w.bytes);
-  const int64_t padded_m = (m + kTileB - 1) / kTileB * kTileB;
+  WithinArgs p{};
+  if (const int rc = begin_sweep(who, w, ws_bytes, a, n, b, m, metric, s, p)) return rc;
   const bool fold = metric == GFY_L2;
-  if (const int rc = launch_pairwise_row_terms(b, m, padded_m, metric, fold, w.s, w.t, nullptr, s))
-    return rc;
-  if (const int rc = launch_pairwise_row_terms(a, n, n, metric, 0, nullptr, nullptr, w.a_term, s))
-    return rc;
   const int bound_grid = (int)((n + 255) / 256);
   if (fold)
     k_within_bound<true><<<bound_grid, 256, 0, s>>>(w.a_term, n, threshold, w.bound);
   else
     k_within_bound<false><<<bound_grid, 256, 0, s>>>(w.a_term, n, threshold, w.bound);
   GFY_CHECK_HIP(hipGetLastError());
-  WithinArgs p{};
-  p.a = (const f16*)a;
-  p.b = (const f16*)b;
-  p.s = w.s;
-  p.t = w.t;
-  p.n = n;
-  p.m = m;
-  p.blocks_a = w.split.blocks_a;
-  p.chunks = w.split.chunks;
-  p.chunk_rows = w.split.chunk_rows;
   p.skip_lo = skip_lo;
   p.skip_hi = skip_hi;
   p.bound = w.bound;

@@ -215,6 +215,27 @@ def _checked_ranges(n: int, b_rows: int | None, exclude_ranges, exclude_records,
     return tuple(bounds)
 
 
+def _pair_ranges(n: int, exclude_self: bool, exclude_offset: int | None,
+                 window_first: int | None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The single-pair exclusions of ``nearest`` / ``topk`` as ``(lo, hi)`` int32 host tensors of
+    length n, the form of ``exclude_ranges``: a range of one row per row of ``a``, or of none
+    (without an exclusion, and for a negative ``exclude_offset``, which excludes nothing).
+    A search times this on the host, so the usual case is two passes over int32.  ``lo`` and
+    ``hi`` may be one tensor (ranges of no row): callers read them and never write."""
+    if window_first is not None:
+        skip = -int(window_first)
+    else:
+        skip = 0 if exclude_self and exclude_offset is None else exclude_offset
+    first = 0 if skip is None else int(skip)
+    width = 0 if skip is None or (window_first is None and skip < 0) else 1
+    if first >= -1 and first + n + width < 2 ** 31:      # every bound fits int32 as it is
+        lo = torch.arange(first, first + n, dtype=torch.int32)
+        return lo, (lo + width if width else lo)
+    # a pair outside b excludes nothing; clamped so that the bounds fit int32
+    lo = torch.arange(n, dtype=torch.int64) + first
+    return tuple(bound.clamp(-1, 2 ** 31 - 1).to(torch.int32) for bound in (lo, lo + width))
+
+
 def _results(values, indices, scratch) -> tuple:
     """What a ``nearest`` / ``topk`` call of the C ABI ends with: the two results, the scratch
     memory and its size, the current stream of their device."""
@@ -361,14 +382,7 @@ def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
         if groups[0].numel() != m:
             raise ValueError(f"distinct_records sums to {groups[0].numel()} rows, b has {m}")
         if ranges is None:   # the single-pair exclusions (or none) as ranges of one row (or none)
-            if window_first is not None:
-                skip = -int(window_first)
-            else:
-                skip = 0 if exclude_self and exclude_offset is None else exclude_offset
-            lo = torch.arange(n, dtype=torch.int64) + (0 if skip is None else int(skip))
-            hi = lo + (0 if skip is None or (window_first is None and skip < 0) else 1)
-            # a pair outside b excludes nothing; clamped so that the bounds fit int32
-            ranges = tuple(bound.clamp(-1, 2 ** 31 - 1).to(torch.int32) for bound in (lo, hi))
+            ranges = _pair_ranges(n, exclude_self, exclude_offset, window_first)
     a = _prepare(a, None)
     b = a if b is None else _prepare(b, a.device)
     if ranges is not None:
@@ -632,8 +646,7 @@ class _WithinCall:
         ranges = _checked_ranges(n, None if b is None else b.shape[0], exclude_ranges,
                                  exclude_records, bool(exclude_self))
         if ranges is None and exclude_self:   # the pair (i, i) as a range of one row
-            lo = torch.arange(n, dtype=torch.int64).clamp(max=2 ** 31 - 2)
-            ranges = lo.to(torch.int32), (lo + 1).to(torch.int32)
+            ranges = _pair_ranges(n, True, None, None)
         if workspace is not None and not isinstance(workspace, WithinWorkspace):
             raise ValueError("workspace must be a WithinWorkspace")
         self.keeper = workspace or WithinWorkspace()

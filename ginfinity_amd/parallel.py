@@ -95,6 +95,70 @@ def all_gather_rows(block: torch.Tensor, group=None
     return torch.cat(pieces, dim=0), offsets
 
 
+def _exchange(block: torch.Tensor, group, chunk_rows: int):
+    """The chunked exchange of ``cross_shard_nearest`` and ``cross_shard_topk``: returns
+    ``(rank, offsets, pieces)``.  ``offsets`` is the row offset of every rank's block (W + 1
+    entries, from one small ``all_gather_into_tensor`` of the sizes, done here).  ``pieces`` is a
+    generator of ``(other_rank, first, piece)``: ``piece`` is rows ``[first, first + len(piece))``
+    of ``other_rank``'s block, every non-empty piece of every rank once, chunk by chunk, and
+    nothing when this rank has no rows (it still takes part in every collective).  A chunk is one
+    equal-count ``all_gather_into_tensor`` of at most ``chunk_rows`` rows per rank into one of two
+    staging buffers; chunk c+1 is started before chunk c's pieces are handed out, so it is in
+    flight under whatever the caller does with them, and a piece is valid until the caller asks
+    for the first piece of the next chunk.  The collectives of the chunks run as the generator is
+    advanced: every rank must exhaust it (a rank that stops early leaves the others waiting in
+    an ``all_gather``).  With world size 1 the pieces are slices of ``block`` and
+    ``torch.distributed`` is not touched."""
+    rank, size = world(group)
+    rows = int(block.shape[0])
+    device = block.device
+    if size > 1:
+        mine = torch.tensor([rows], dtype=torch.int64, device=device)
+        everyone = torch.empty(size, dtype=torch.int64, device=device)
+        dist.all_gather_into_tensor(everyone, mine, group=group)
+        sizes = [int(v) for v in everyone.tolist()]
+    else:
+        sizes = [rows]
+    offsets = [0]
+    for value in sizes:
+        offsets.append(offsets[-1] + value)
+    widest = max(sizes)
+    chunk_rows = max(1, min(int(chunk_rows), max(widest, 1)))
+    chunks = (widest + chunk_rows - 1) // chunk_rows
+    if size > 1:
+        staging = [torch.empty((size, chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
+                   for _ in range(min(2, max(chunks, 1)))]
+        outgoing = [torch.zeros((chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
+                    for _ in range(len(staging))]
+
+    def start(chunk: int):
+        first = chunk * chunk_rows
+        have = max(0, min(rows - first, chunk_rows))
+        buffer = outgoing[chunk % len(outgoing)]
+        if have:
+            buffer[:have] = block[first:first + have]
+        return dist.all_gather_into_tensor(
+            staging[chunk % len(staging)].view(size * chunk_rows, block.shape[1]), buffer,
+            group=group, async_op=True)
+
+    def pieces():
+        pending = start(0) if size > 1 and chunks else None
+        for chunk in range(chunks):
+            first = chunk * chunk_rows
+            if size > 1:
+                arriving = pending
+                pending = start(chunk + 1) if chunk + 1 < chunks else None   # under the search
+                arriving.wait()
+            for other in range(size):
+                valid = max(0, min(sizes[other] - first, chunk_rows))
+                if valid == 0 or rows == 0:
+                    continue
+                yield other, first, (staging[chunk % len(staging)][other, :valid] if size > 1
+                                     else block[first:first + valid])
+
+    return rank, offsets, pieces()
+
+
 def _search_block(search, local: torch.Tensor, other: torch.Tensor, metric: str,
                   own_first: int | None, workspace=None) -> tuple[torch.Tensor, torch.Tensor]:
     """``search(local, other)``; when ``other`` is rows [own_first, own_first + len(other)) of
@@ -130,61 +194,19 @@ def cross_shard_nearest(block: torch.Tensor, *, metric: str = "l2", group=None,
         workspace = distance.NearestWorkspace()     # one set of buffers for every piece
     if metric not in ("l2", "cosine"):
         raise ValueError("metric must be 'l2' or 'cosine'")
-    rank, size = world(group)
+    rank, offsets, pieces = _exchange(block, group, chunk_rows)
     rows = int(block.shape[0])
-    device = block.device
-    if size > 1:
-        mine = torch.tensor([rows], dtype=torch.int64, device=device)
-        everyone = torch.empty(size, dtype=torch.int64, device=device)
-        dist.all_gather_into_tensor(everyone, mine, group=group)
-        sizes = [int(v) for v in everyone.tolist()]
-    else:
-        sizes = [rows]
-    offsets = [0]
-    for value in sizes:
-        offsets.append(offsets[-1] + value)
-    widest = max(sizes)
-    chunk_rows = max(1, min(int(chunk_rows), max(widest, 1)))
-    chunks = (widest + chunk_rows - 1) // chunk_rows
     worse = float("inf") if metric == "l2" else float("-inf")
-    best_value = torch.full((rows,), worse, dtype=torch.float32, device=device)
-    best_index = torch.full((rows,), -1, dtype=torch.int64, device=device)
-    if size > 1:
-        staging = [torch.empty((size, chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
-                   for _ in range(min(2, max(chunks, 1)))]
-        outgoing = [torch.zeros((chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
-                    for _ in range(len(staging))]
-
-    def start(chunk: int):
-        first = chunk * chunk_rows
-        have = max(0, min(rows - first, chunk_rows))
-        buffer = outgoing[chunk % len(outgoing)]
-        if have:
-            buffer[:have] = block[first:first + have]
-        return dist.all_gather_into_tensor(
-            staging[chunk % len(staging)].view(size * chunk_rows, block.shape[1]), buffer,
-            group=group, async_op=True)
-
-    pending = start(0) if size > 1 and chunks else None
-    for chunk in range(chunks):
-        first = chunk * chunk_rows
-        if size > 1:
-            arriving = pending
-            pending = start(chunk + 1) if chunk + 1 < chunks else None   # in flight under the search
-            arriving.wait()
-        for other in range(size):
-            valid = max(0, min(sizes[other] - first, chunk_rows))
-            if valid == 0 or rows == 0:
-                continue
-            piece = (staging[chunk % len(staging)][other, :valid] if size > 1
-                     else block[first:first + valid])
-            values, indices = _search_block(search, block, piece, metric,
-                                            first if other == rank else None, workspace)
-            indices = indices.to(torch.int64) + (offsets[other] + first)
-            better = (values < best_value) if metric == "l2" else (values > best_value)
-            better |= (values == best_value) & (indices < best_index)
-            best_value = torch.where(better, values, best_value)
-            best_index = torch.where(better, indices, best_index)
+    best_value = torch.full((rows,), worse, dtype=torch.float32, device=block.device)
+    best_index = torch.full((rows,), -1, dtype=torch.int64, device=block.device)
+    for other, first, piece in pieces:
+        values, indices = _search_block(search, block, piece, metric,
+                                        first if other == rank else None, workspace)
+        indices = indices.to(torch.int64) + (offsets[other] + first)
+        better = (values < best_value) if metric == "l2" else (values > best_value)
+        better |= (values == best_value) & (indices < best_index)
+        best_value = torch.where(better, values, best_value)
+        best_index = torch.where(better, indices, best_index)
     return best_value, best_index, offsets
 
 
@@ -208,8 +230,8 @@ def cross_shard_topk(block: torch.Tensor, k: int, *, metric: str = "l2", group=N
                      ) -> tuple[torch.Tensor, torch.Tensor, list[int]]:
     """The ``k`` nearest other embeddings, over ALL ranks' rows, of every local row.
 
-    The exchange is that of ``cross_shard_nearest``: chunks of ``chunk_rows`` rows per rank,
-    one equal-count ``all_gather_into_tensor`` per chunk into one of two staging buffers, chunk
+    The exchange is ``cross_shard_nearest``'s (``_exchange``): chunks of ``chunk_rows`` rows per
+    rank, one equal-count ``all_gather_into_tensor`` per chunk into one of two staging buffers, chunk
     c searched while chunk c+1 is in flight.  Per piece one ``distance.topk`` call (the rank's
     own piece with ``window_first``), whose ``[rows][k]`` lists are merged into the running
     ones on the device by (value, global row), keeping ``k``; ties go to the lowest global
@@ -243,69 +265,26 @@ def cross_shard_topk(block: torch.Tensor, k: int, *, metric: str = "l2", group=N
     if metric not in ("l2", "cosine"):
         raise ValueError("metric must be 'l2' or 'cosine'")
     k = distance.checked_k(k)                    # the check of distance.topk
-    rank, size = world(group)
     rows = int(block.shape[0])
-    device = block.device
     own = None
     if record_counts is not None:
-        own = distance.record_ranges(record_counts, device)    # once: every own piece shifts it
+        own = distance.record_ranges(record_counts, block.device)   # once: own pieces shift it
         if own[0].numel() != rows:
             raise ValueError(f"record_counts sums to {own[0].numel()} rows, the block has {rows}")
-    if size > 1:
-        mine = torch.tensor([rows], dtype=torch.int64, device=device)
-        everyone = torch.empty(size, dtype=torch.int64, device=device)
-        dist.all_gather_into_tensor(everyone, mine, group=group)
-        sizes = [int(v) for v in everyone.tolist()]
-    else:
-        sizes = [rows]
-    offsets = [0]
-    for value in sizes:
-        offsets.append(offsets[-1] + value)
-    widest = max(sizes)
-    chunk_rows = max(1, min(int(chunk_rows), max(widest, 1)))
-    chunks = (widest + chunk_rows - 1) // chunk_rows
+    rank, offsets, pieces = _exchange(block, group, chunk_rows)
     worse = float("inf") if metric == "l2" else float("-inf")
-    best_value = torch.full((rows, k), worse, dtype=torch.float32, device=device)
-    best_index = torch.full((rows, k), _NO_ROW, dtype=torch.int64, device=device)
-    if size > 1:
-        staging = [torch.empty((size, chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
-                   for _ in range(min(2, max(chunks, 1)))]
-        outgoing = [torch.zeros((chunk_rows, block.shape[1]), dtype=block.dtype, device=device)
-                    for _ in range(len(staging))]
-
-    def start(chunk: int):
-        first = chunk * chunk_rows
-        have = max(0, min(rows - first, chunk_rows))
-        buffer = outgoing[chunk % len(outgoing)]
-        if have:
-            buffer[:have] = block[first:first + have]
-        return dist.all_gather_into_tensor(
-            staging[chunk % len(staging)].view(size * chunk_rows, block.shape[1]), buffer,
-            group=group, async_op=True)
-
-    pending = start(0) if size > 1 and chunks else None
-    for chunk in range(chunks):
-        first = chunk * chunk_rows
-        if size > 1:
-            arriving = pending
-            pending = start(chunk + 1) if chunk + 1 < chunks else None   # in flight under the search
-            arriving.wait()
-        for other in range(size):
-            valid = max(0, min(sizes[other] - first, chunk_rows))
-            if valid == 0 or rows == 0:
-                continue
-            piece = (staging[chunk % len(staging)][other, :valid] if size > 1
-                     else block[first:first + valid])
-            extra = {} if workspace is None else {"workspace": workspace}
-            if other == rank and own is None:
-                extra["window_first"] = first
-            elif other == rank:      # in the piece's row numbers; subsumes the self-exclusion
-                extra["exclude_ranges"] = (own[0] - first, own[1] - first)
-            values, indices = search(block, piece, k=k, metric=metric, **extra)
-            indices = indices.to(torch.int64)
-            indices = torch.where(indices < 0, _NO_ROW, indices + (offsets[other] + first))
-            best_value, best_index = _merge_topk(best_value, best_index, values, indices, k,
-                                                 metric)
+    best_value = torch.full((rows, k), worse, dtype=torch.float32, device=block.device)
+    best_index = torch.full((rows, k), _NO_ROW, dtype=torch.int64, device=block.device)
+    for other, first, piece in pieces:
+        extra = {} if workspace is None else {"workspace": workspace}
+        if other == rank and own is None:
+            extra["window_first"] = first
+        elif other == rank:      # in the piece's row numbers; subsumes the self-exclusion
+            extra["exclude_ranges"] = (own[0] - first, own[1] - first)
+        values, indices = search(block, piece, k=k, metric=metric, **extra)
+        indices = indices.to(torch.int64)
+        indices = torch.where(indices < 0, _NO_ROW, indices + (offsets[other] + first))
+        best_value, best_index = _merge_topk(best_value, best_index, values, indices, k, metric)
     best_index = torch.where(best_index == _NO_ROW, -1, best_index)
     return best_value, best_index, offsets
 
