@@ -1,87 +1,13 @@
-// C ABI of libgfy (include/gfy.h): argument checking, weight-pack parsing and
-// the host-side derivation of everything the fp16 kernels consume.
-//
-// Reference behaviour reproduced here (host side, once per encoder):
-//   model.half()                       src/ginfinity/api.py:111-112
-//   edge_lin on a one-hot row          src/ginfinity/_model.py:43   -> 10-row table
-//   (1 + eps) formed in fp16           src/ginfinity/_model.py:46
-//   BatchNorm1d eval affine in fp32    src/ginfinity/_model.py:35
-// The rounding points follow SURVEY.md §8-A / oracle/gine_numpy.py.
-// Compiled with -ffp-contract=off: alpha/shift must round after every step.
-#include <cmath>
-#include <cstring>
-#include <initializer_list>
+// C ABI of libgfy (include/gfy.h): argument checking and the calls into the launchers.  The
+// weight pack is read by gfy_base.cpp (weight_pack.h) and turned into what the kernels consume
+// by weight_image.cpp; encoder creation here uploads that image and binds pointers to it.
+#include <memory>
 #include <string>
-#include <vector>
 
 #include "gfy_common.h"
 
 namespace gfy {
-
-// (error channel, ABI version, weight-pack size: gfy_base.cpp, shared with libgfy_host.so)
-size_t pack_floats(uint32_t in_dim, uint32_t h, uint32_t layers, uint32_t edge_dim,
-                   uint32_t out_dim);
-
-void pack_b_fragments(const f16* w, int n_out, int k_in, f16* frag) {
-  const int tiles = n_out / 32, ksteps = k_in / 16;
-  for (int tile = 0; tile < tiles; ++tile)
-    for (int ks = 0; ks < ksteps; ++ks)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j)
-          frag[(((size_t)tile * ksteps + ks) * 64 + lane) * 8 + j] =
-              w[(size_t)(32 * tile + (lane & 31)) * k_in + 16 * ks +
-                8 * (lane >> 5) + j];
-}
-
-void pack_k_chained(const f16* w, int n_out, int k_in, f16* frag) {
-  const int blocks = n_out / 32, ksteps = k_in / 16;
-  for (int blk = 0; blk < blocks; ++blk)
-    for (int s = 0; s < ksteps; ++s)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int j = 0; j < 8; ++j)
-          frag[(((size_t)blk * ksteps + s) * 64 + lane) * 8 + j] =
-              w[(size_t)(32 * blk + (lane & 31)) * k_in + 16 * s + 8 * (j >> 2) +
-                4 * (lane >> 5) + (j & 3)];
-}
-
-void pack_chain_fragments(const f16* w, int n_out, int k_in, f16* frag) {
-  const int blocks = n_out / 32, ksteps = k_in / 16;
-  for (int blk = 0; blk < blocks; ++blk)
-    for (int s = 0; s < ksteps; ++s)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int m = lane & 31, half = lane >> 5;
-        const int reg = (m & 3) + 4 * (m >> 3), row_half = (m >> 2) & 1;   // C/D row m
-        const int out_channel = 32 * blk + 16 * (reg >> 3) + 8 * row_half + (reg & 7);
-        for (int j = 0; j < 8; ++j) {
-          const int k = 16 * s + 8 * (j >> 2) + 4 * half + (j & 3);
-          frag[(((size_t)blk * ksteps + s) * 64 + lane) * 8 + j] =
-              w[(size_t)out_channel * k_in + k];
-        }
-      }
-}
-
 namespace {
-
-constexpr uint32_t kMagic = 0x31594647u;  // 'GFY1'
-
-struct PackHeader {
-  uint32_t magic, version, in_dim, hidden, layers, edge_dim, out_dim, flags;
-};
-static_assert(sizeof(PackHeader) == 32, "gfy_weight_pack_bytes (gfy_base.cpp) counts 32 bytes");
-
-// bump allocator over a host staging image of the device blob
-struct Blob {
-  std::vector<char> host;
-  size_t reserve(size_t bytes) {
-    const size_t at = align_up(host.size(), 256);
-    host.resize(at + bytes, 0);
-    return at;
-  }
-  template <typename T>
-  T* at(size_t off) { return reinterpret_cast<T*>(host.data() + off); }
-};
-
-inline f16 rh(float v) { return (f16)v; }  // RNE, as torch's .half()
 
 // Makes `device` current for the life of the guard and gives the caller's device back: the
 // library never leaves the calling thread on another device than it came with.
@@ -109,14 +35,35 @@ static int check_current_device(const gfy_encoder* enc, const char* who) {
   return GFY_OK;
 }
 
-struct Reader {
-  const float* p;
-  const float* take(size_t n) {
-    const float* r = p;
-    p += n;
-    return r;
+// One place per model where blob offsets (weight_image.h) become the pointers the launchers read
+void bind_f16(gfy_encoder* enc, const ImageF16& o) {
+  const char* base = static_cast<const char*>(enc->device_blob);
+  auto at = [&](size_t off) { return reinterpret_cast<const f16*>(base + off); };
+  enc->f16.w_in = at(o.input.w);
+  enc->f16.b_in = at(o.input.b);
+  for (int l = 0; l < enc->layers; ++l)
+    enc->f16.layer[l] = LayerF16{o.layer[l].scale, enc->edge_dim, at(o.layer[l].w01),
+                                 base + o.layer[l].image};
+  enc->f16.head = HeadF16{at(o.head.wa), at(o.head.ba), at(o.head.wb), at(o.head.bb),
+                          at(o.head.w_image), base + o.head.image};
+}
+
+void bind_f32(gfy_encoder* enc, const ImageF32& o) {
+  const char* base = static_cast<const char*>(enc->device_blob);
+  auto at = [&](size_t off) { return reinterpret_cast<const float*>(base + off); };
+  enc->f32.w_in_t = at(o.input.w);
+  enc->f32.b_in = at(o.input.b);
+  for (int l = 0; l < enc->layers; ++l) {
+    const LayerF32Off& from = o.layer[l];
+    enc->f32.layer[l] = LayerF32{at(from.table), from.one_plus_eps, at(from.w0t), at(from.b0),
+                                 at(from.alpha), at(from.shift), at(from.w1t), at(from.b1),
+                                 at(from.ln_g), at(from.ln_b)};
   }
-};
+  enc->f32.ha_wt = at(o.head.wa_t);
+  enc->f32.ha_b = at(o.head.ba);
+  enc->f32.hb_wt = at(o.head.wb_t);
+  enc->f32.hb_b = at(o.head.bb);
+}
 
 }  // namespace
 }  // namespace gfy
@@ -136,291 +83,46 @@ int gfy_encoder_create(const void* weight_pack_host, size_t bytes,
   clear_error();
   GFY_REQUIRE(out != nullptr, GFY_ERR_INVALID, "gfy_encoder_create: out is NULL");
   *out = nullptr;
-  GFY_REQUIRE(weight_pack_host && bytes >= sizeof(PackHeader), GFY_ERR_INVALID,
-              "gfy_encoder_create: weight pack missing or truncated");
-  PackHeader hd;
-  std::memcpy(&hd, weight_pack_host, sizeof hd);
-  GFY_REQUIRE(hd.magic == kMagic && hd.version == 1, GFY_ERR_INVALID,
-              "gfy_encoder_create: bad weight-pack magic/version");
-  GFY_REQUIRE(hd.hidden == (uint32_t)kHidden && hd.in_dim == (uint32_t)kInDim &&
-                  hd.out_dim == (uint32_t)kOutDim,
-              GFY_ERR_UNSUPPORTED,
-              "gfy_encoder_create: kernels are built for in_dim=7 hidden=128 "
-              "out_dim=128 (got %u/%u/%u)",
-              hd.in_dim, hd.hidden, hd.out_dim);
-  GFY_REQUIRE(hd.layers >= 1 && hd.layers <= (uint32_t)kMaxLayers,
-              GFY_ERR_UNSUPPORTED, "gfy_encoder_create: layers=%u outside 1..%d",
-              hd.layers, kMaxLayers);
-  GFY_REQUIRE(hd.edge_dim >= 1 && hd.edge_dim <= (uint32_t)kMaxEdgeTypes,
-              GFY_ERR_UNSUPPORTED, "gfy_encoder_create: edge_dim=%u outside 1..%d",
-              hd.edge_dim, kMaxEdgeTypes);
-  GFY_REQUIRE(bytes == gfy_weight_pack_bytes(hd.in_dim, hd.hidden, hd.layers,
-                                             hd.edge_dim, hd.out_dim),
-              GFY_ERR_INVALID, "gfy_encoder_create: weight pack is %zu bytes, expected %zu",
-              bytes,
-              gfy_weight_pack_bytes(hd.in_dim, hd.hidden, hd.layers, hd.edge_dim,
-                                    hd.out_dim));
-  GFY_REQUIRE(model_dtype == GFY_F16 || model_dtype == GFY_F32, GFY_ERR_INVALID,
-              "gfy_encoder_create: model_dtype must be GFY_F16 or GFY_F32");
+  PackView pack;
+  if (const int rc = read_weight_pack("gfy_encoder_create", weight_pack_host, bytes, model_dtype,
+                                      &pack))
+    return rc;
   DeviceGuard guard(device);   // the caller's current device is restored on every way out
   GFY_CHECK_HIP(guard.status);
   if (model_dtype == GFY_F16)
     if (const int rc = prepare_device_f16()) return rc;
 
-  const int H = kHidden, M = kMlp, L = (int)hd.layers, ED = (int)hd.edge_dim;
-  Reader rd{reinterpret_cast<const float*>((const char*)weight_pack_host +
-                                           sizeof(PackHeader))};
-  gfy_encoder* enc = new gfy_encoder();
+  std::unique_ptr<gfy_encoder> enc(new gfy_encoder());   // ours until *out is set
   enc->device = device;
   enc->model_dtype = model_dtype;
-  enc->layers = L;
-  enc->edge_dim = ED;
-  enc->residual = (int)(hd.flags & 1u);
-  {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
-        cus >= 8)
-      enc->cus = cus & ~7;
-  }
+  enc->layers = pack.layers;
+  enc->edge_dim = pack.edge_dim;
+  enc->residual = pack.residual;
+  int cus = 0;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess &&
+      cus >= 8)
+    enc->cus = cus & ~7;
 
+  // one host image of every derived tensor, one upload, then offsets become pointers
   Blob blob;
-  // offsets first (pointers are fixed up after the single upload)
-  struct LayerOff {
-    size_t w01, image;                                                // f16 mode
-    size_t ftable, fw0, fb0, falpha, fshift, fw1, fb1, flg, flb;      // f32 mode
-    float scale, one_plus_eps;
-  };
-  size_t o_win = 0, o_bin = 0, o_wa = 0, o_ba = 0, o_wb = 0, o_bb = 0, o_hchain = 0,
-         o_himage = 0;
-  std::vector<LayerOff> lo(L);
-
-  const float* w_in = rd.take((size_t)H * kInDim);
-  const float* b_in = rd.take(H);
-  if (model_dtype == GFY_F16) {
-    o_win = blob.reserve((size_t)H * 8 * sizeof(f16));
-    o_bin = blob.reserve(H * sizeof(f16));
-    for (int p = 0; p < H; ++p) {
-      // stored position p holds channel stored_channel(p); packed [p & 7][p >> 3][k]: see
-      // k_input_linear_f16
-      const int c = stored_channel(p);
-      for (int k = 0; k < kInDim; ++k)
-        blob.at<f16>(o_win)[((p & 7) * 16 + (p >> 3)) * 8 + k] = rh(w_in[c * kInDim + k]);
-      blob.at<f16>(o_bin)[p] = rh(b_in[c]);
-    }
-  } else {
-    o_win = blob.reserve((size_t)H * kInDim * 4);
-    o_bin = blob.reserve(H * 4);
-    for (int c = 0; c < H; ++c)
-      for (int k = 0; k < kInDim; ++k)
-        blob.at<float>(o_win)[k * H + c] = w_in[c * kInDim + k];  // [K][N]
-    std::memcpy(blob.at<float>(o_bin), b_in, H * 4);
-  }
-
-  std::vector<f16> tmp;
-  for (int l = 0; l < L; ++l) {
-    const float* eps = rd.take(1);
-    const float* ew = rd.take((size_t)H * ED);
-    const float* eb = rd.take(H);
-    const float* w0 = rd.take((size_t)M * H);
-    const float* b0 = rd.take(M);
-    const float* bg = rd.take(M);
-    const float* bb = rd.take(M);
-    const float* bm = rd.take(M);
-    const float* bv = rd.take(M);
-    const float* w1 = rd.take((size_t)H * M);
-    const float* b1 = rd.take(H);
-    const float* lg = rd.take(H);
-    const float* lb = rd.take(H);
-    LayerOff& o = lo[l];
-    if (model_dtype == GFY_F16) {
-      o.scale = (float)rh(1.0f + (float)rh(eps[0]));  // fp16 scalar (1 + eps)
-      // [W0 | W1] fragments: every B operand of the layer kernel is an MFMA result (or a
-      // stored row, which has the same order) used in place
-      o.w01 = blob.reserve((size_t)2 * M * H * sizeof(f16));
-      tmp.resize((size_t)M * H);
-      for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = rh(w0[i]);
-      pack_k_chained(tmp.data(), M, H, blob.at<f16>(o.w01));
-      for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = rh(w1[i]);
-      pack_k_chained(tmp.data(), H, M, blob.at<f16>(o.w01) + (size_t)M * H);
-      // LDS image of gine_layer.inc, in the order its lanes read it
-      o.image = blob.reserve(7680);
-      char* im = blob.at<char>(o.image);
-      f16* table = reinterpret_cast<f16*>(im);           // [17][128], stored order
-      for (int t = 0; t < ED; ++t)
-        for (int p = 0; p < H; ++p) {   // R(R(W[c][t]) + R(b[c]))  — one-hot Linear
-          const int c = stored_channel(p);
-          table[t * H + p] = rh((float)rh(ew[c * ED + t]) + (float)rh(eb[c]));
-        }
-      for (int p = 0; p < H; ++p) table[kMaxEdgeTypes * H + p] = (f16)(-INFINITY);
-      float* ia = reinterpret_cast<float*>(im + 4352);
-      float* is = reinterpret_cast<float*>(im + 4352 + 1024);
-      f16* ib0 = reinterpret_cast<f16*>(im + 4352 + 2048);
-      for (int blk = 0; blk < M / 32; ++blk)
-        for (int half = 0; half < 2; ++half)
-          for (int reg = 0; reg < 16; ++reg) {
-            const int c = gemm_result_channel(blk, half, reg);
-            const int at = (blk * 2 + half) * 16 + reg;
-            const float g = (float)rh(bg[c]), b = (float)rh(bb[c]);
-            const float mean = (float)rh(bm[c]), var = (float)rh(bv[c]);
-            const float invstd = 1.0f / std::sqrt(var + 1e-5f);
-            const float alpha = invstd * g;
-            const float prod = mean * alpha;  // separate rounding (no fma)
-            ia[at] = alpha;
-            is[at] = b - prod;
-          }
-      // b0 and b1 are added on the matrix cores (gine_layer.inc, mlp_pipe_step): natural channel
-      // order — row lane % 32 of A-operand block b is channel 32 b + row
-      for (int c = 0; c < M; ++c) ib0[c] = rh(b0[c]);
-      f16* ib1 = reinterpret_cast<f16*>(im + 4352 + 2048 + 512);
-      f16* ig = ib1 + H;
-      f16* ib = ig + H;
-      for (int blk = 0; blk < H / 32; ++blk)
-        for (int half = 0; half < 2; ++half)
-          for (int reg = 0; reg < 16; ++reg) {
-            const int c = gemm_result_channel(blk, half, reg);
-            const int at = (blk * 2 + half) * 16 + reg;
-            ib1[c] = rh(b1[c]);
-            ig[at] = rh(lg[c]);
-            ib[at] = rh(lb[c]);
-          }
-    } else {
-      auto put = [&](const float* src, size_t n) {
-        const size_t off = blob.reserve(n * 4);
-        std::memcpy(blob.at<float>(off), src, n * 4);
-        return off;
-      };
-      auto put_transposed = [&](const float* src, int rows, int cols) {
-        const size_t off = blob.reserve((size_t)rows * cols * 4);
-        for (int r = 0; r < rows; ++r)
-          for (int c = 0; c < cols; ++c)
-            blob.at<float>(off)[(size_t)c * rows + r] = src[(size_t)r * cols + c];
-        return off;
-      };
-      o.one_plus_eps = 1.0f + eps[0];
-      o.ftable = blob.reserve((size_t)kMaxEdgeTypes * H * 4);
-      for (int t = 0; t < ED; ++t)
-        for (int c = 0; c < H; ++c)
-          blob.at<float>(o.ftable)[t * H + c] = ew[c * ED + t] + eb[c];
-      o.fw0 = put_transposed(w0, M, H);   // -> [H][M]
-      o.fb0 = put(b0, M);
-      o.falpha = blob.reserve(M * 4);
-      o.fshift = blob.reserve(M * 4);
-      for (int c = 0; c < M; ++c) {
-        const float invstd = 1.0f / std::sqrt(bv[c] + 1e-5f);
-        const float alpha = invstd * bg[c];
-        const float prod = bm[c] * alpha;
-        blob.at<float>(o.falpha)[c] = alpha;
-        blob.at<float>(o.fshift)[c] = bb[c] - prod;
-      }
-      o.fw1 = put_transposed(w1, H, M);   // -> [M][H]
-      o.fb1 = put(b1, H);
-      o.flg = put(lg, H);
-      o.flb = put(lb, H);
-    }
-  }
-  const float* wa = rd.take((size_t)H * H);
-  const float* ba = rd.take(H);
-  const float* wb = rd.take((size_t)kOutDim * H);
-  const float* bbias = rd.take(kOutDim);
-  if (model_dtype == GFY_F16) {
-    // stand-alone head kernel: reads stored rows (k chained), writes natural rows
-    tmp.resize((size_t)H * H);
-    for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = rh(wa[i]);
-    o_wa = blob.reserve(tmp.size() * sizeof(f16));
-    pack_k_chained(tmp.data(), H, H, blob.at<f16>(o_wa));
-    // fused head: head.0 k-chained, head.2 chained with its rows dealt into natural chunks
-    o_hchain = blob.reserve((size_t)2 * H * H * sizeof(f16));
-    std::memcpy(blob.at<f16>(o_hchain), blob.at<f16>(o_wa), (size_t)H * H * sizeof(f16));
-    for (size_t i = 0; i < tmp.size(); ++i) tmp[i] = rh(wb[i]);
-    o_wb = blob.reserve(tmp.size() * sizeof(f16));
-    pack_b_fragments(tmp.data(), kOutDim, H, blob.at<f16>(o_wb));
-    pack_chain_fragments(tmp.data(), kOutDim, H, blob.at<f16>(o_hchain) + (size_t)H * H);
-    o_ba = blob.reserve(H * sizeof(f16));
-    o_bb = blob.reserve(kOutDim * sizeof(f16));
-    for (int c = 0; c < H; ++c) {
-      blob.at<f16>(o_ba)[c] = rh(ba[c]);
-      blob.at<f16>(o_bb)[c] = rh(bbias[c]);
-    }
-    o_himage = blob.reserve(512);
-    {
-      f16* iba = blob.at<f16>(o_himage);
-      f16* ibb = iba + H;
-      for (int blk = 0; blk < H / 32; ++blk)
-        for (int half = 0; half < 2; ++half)
-          for (int reg = 0; reg < 16; ++reg)
-            iba[(blk * 2 + half) * 16 + reg] =
-                blob.at<f16>(o_ba)[gemm_result_channel(blk, half, reg)];
-      for (int half = 0; half < 2; ++half)
-        for (int ks = 0; ks < 8; ++ks)
-          for (int j = 0; j < 8; ++j)
-            ibb[(half * 8 + ks) * 8 + j] =
-                blob.at<f16>(o_bb)[hidden_layout_channel(half, ks, j)];
-    }
-  } else {
-    o_wa = blob.reserve((size_t)H * H * 4);
-    o_wb = blob.reserve((size_t)kOutDim * H * 4);
-    for (int r = 0; r < H; ++r)
-      for (int c = 0; c < H; ++c) {
-        blob.at<float>(o_wa)[(size_t)c * H + r] = wa[(size_t)r * H + c];
-        blob.at<float>(o_wb)[(size_t)c * kOutDim + r] = wb[(size_t)r * H + c];
-      }
-    o_ba = blob.reserve(H * 4);
-    std::memcpy(blob.at<float>(o_ba), ba, H * 4);
-    o_bb = blob.reserve(kOutDim * 4);
-    std::memcpy(blob.at<float>(o_bb), bbias, kOutDim * 4);
-  }
-
+  ImageF16 f16_at{};
+  ImageF32 f32_at{};
+  if (model_dtype == GFY_F16) f16_at = build_image_f16(blob, pack);
+  else f32_at = build_image_f32(blob, pack);
   void* dev = nullptr;
   hipError_t err = hipMalloc(&dev, blob.host.size());
   if (err == hipSuccess)
     err = hipMemcpy(dev, blob.host.data(), blob.host.size(), hipMemcpyHostToDevice);
   if (err != hipSuccess) {
     if (dev) (void)hipFree(dev);
-    delete enc;
     set_error("gfy_encoder_create: device upload failed: %s", hipGetErrorString(err));
     return GFY_ERR_HIP;
   }
   enc->device_blob = dev;
   enc->device_blob_bytes = blob.host.size();
-  char* base = (char*)dev;
-  auto H16 = [&](size_t off) { return (const f16*)(base + off); };
-  auto F32p = [&](size_t off) { return (const float*)(base + off); };
-  if (model_dtype == GFY_F16) {
-    enc->f16.w_in = H16(o_win);
-    enc->f16.b_in = H16(o_bin);
-    for (int l = 0; l < L; ++l) {
-      LayerF16& d = enc->f16.layer[l];
-      const LayerOff& o = lo[l];
-      d.scale = o.scale;
-      d.edge_types = ED;
-      d.w01_image = H16(o.w01);
-      d.image = base + o.image;
-    }
-    enc->f16.head = HeadF16{H16(o_wa), H16(o_ba), H16(o_wb), H16(o_bb), H16(o_hchain),
-                            base + o_himage};
-  } else {
-    enc->f32.w_in_t = F32p(o_win);
-    enc->f32.b_in = F32p(o_bin);
-    for (int l = 0; l < L; ++l) {
-      LayerF32& d = enc->f32.layer[l];
-      const LayerOff& o = lo[l];
-      d.table = F32p(o.ftable);
-      d.one_plus_eps = o.one_plus_eps;
-      d.w0t = F32p(o.fw0);
-      d.b0 = F32p(o.fb0);
-      d.alpha = F32p(o.falpha);
-      d.shift = F32p(o.fshift);
-      d.w1t = F32p(o.fw1);
-      d.b1 = F32p(o.fb1);
-      d.ln_g = F32p(o.flg);
-      d.ln_b = F32p(o.flb);
-    }
-    enc->f32.ha_wt = F32p(o_wa);
-    enc->f32.ha_b = F32p(o_ba);
-    enc->f32.hb_wt = F32p(o_wb);
-    enc->f32.hb_b = F32p(o_bb);
-  }
-  *out = enc;
+  if (model_dtype == GFY_F16) bind_f16(enc.get(), f16_at);
+  else bind_f32(enc.get(), f32_at);
+  *out = enc.release();
   return GFY_OK;
 }
 

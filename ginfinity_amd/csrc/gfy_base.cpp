@@ -1,8 +1,8 @@
 // What BOTH shared objects need and no HIP call is in: the per-thread error channel, the ABI
-// version and the weight pack's size.  libgfy.so (HIP kernels + C ABI) links it, and so does
-// libgfy_host.so = this file + gine_host.cpp, built with the host compiler alone: the
-// reference's default device (Ginfinity.load(device="cpu"), src/ginfinity/api.py:64-76) then
-// works on a box that has no ROCm runtime at all.
+// version and the weight pack's reader (weight_pack.h).  libgfy.so (HIP kernels + C ABI) links
+// it, and so does libgfy_host.so = this file + gine_host.cpp, built with the host compiler
+// alone: the reference's default device (Ginfinity.load(device="cpu"),
+// src/ginfinity/api.py:64-76) then works on a box that has no ROCm runtime at all.
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -14,6 +14,7 @@
 #endif
 
 #include "../../include/gfy.h"
+#include "weight_pack.h"
 
 namespace gfy {
 
@@ -29,14 +30,101 @@ void set_error(const char* fmt, ...) {
 }
 void clear_error() { g_error.clear(); }
 
-// floats behind the 32-byte header of a weight pack (layout: ginfinity_amd/weights.py)
+// ---- the weight pack (weight_pack.h; layout: ginfinity_amd/weights.py, tensor_order) ---------
+namespace {
+
+// Walks the floats behind the header in pack order.  Without a pack it only counts.
+struct PackCursor {
+  const float* base;
+  size_t at = 0;
+  const float* take(size_t count) {
+    const float* here = base ? base + at : nullptr;
+    at += count;
+    return here;
+  }
+};
+
+void walk_input(PackCursor& c, size_t in_dim, size_t h, PackView& v) {
+  v.w_in = c.take(h * in_dim);
+  v.b_in = c.take(h);
+}
+
+void walk_layer(PackCursor& c, size_t h, size_t edge_dim, PackLayer& l) {
+  const size_t m = 2 * h;
+  l.eps = c.take(1);
+  l.edge_w = c.take(h * edge_dim);
+  l.edge_b = c.take(h);
+  l.w0 = c.take(m * h);
+  l.b0 = c.take(m);
+  l.bn_gamma = c.take(m);
+  l.bn_beta = c.take(m);
+  l.bn_mean = c.take(m);
+  l.bn_var = c.take(m);
+  l.w1 = c.take(h * m);
+  l.b1 = c.take(h);
+  l.ln_gamma = c.take(h);
+  l.ln_beta = c.take(h);
+}
+
+void walk_head(PackCursor& c, size_t h, size_t out_dim, PackView& v) {
+  v.wa = c.take(h * h);
+  v.ba = c.take(h);
+  v.wb = c.take(out_dim * h);
+  v.bb = c.take(out_dim);
+}
+
+}  // namespace
+
 size_t pack_floats(uint32_t in_dim, uint32_t h, uint32_t layers, uint32_t edge_dim,
                    uint32_t out_dim) {
-  const size_t per_layer = 1 + (size_t)h * edge_dim + h + (size_t)2 * h * h +
-                           2 * h + 4 * (size_t)(2 * h) + (size_t)h * 2 * h + h +
-                           2 * h;
-  return (size_t)h * in_dim + h + layers * per_layer + (size_t)h * h + h +
-         (size_t)out_dim * h + out_dim;
+  PackView nowhere;
+  PackCursor input{nullptr}, layer{nullptr}, head{nullptr};
+  walk_input(input, in_dim, h, nowhere);
+  walk_layer(layer, h, edge_dim, nowhere.layer[0]);
+  walk_head(head, h, out_dim, nowhere);
+  return input.at + layers * layer.at + head.at;
+}
+
+int read_weight_pack(const char* who, const void* pack, size_t bytes, int model_dtype,
+                     PackView* view) {
+  PackHeader hd;
+  if (!pack || bytes < sizeof hd) {
+    set_error("%s: weight pack missing or truncated", who);
+    return GFY_ERR_INVALID;
+  }
+  std::memcpy(&hd, pack, sizeof hd);
+  if (hd.magic != kPackMagic || hd.version != kPackVersion) {
+    set_error("%s: bad weight-pack magic/version", who);
+    return GFY_ERR_INVALID;
+  }
+  if (hd.in_dim != (uint32_t)kInDim || hd.hidden != (uint32_t)kHidden ||
+      hd.out_dim != (uint32_t)kOutDim || hd.layers < 1 || hd.layers > (uint32_t)kMaxLayers ||
+      hd.edge_dim < 1 || hd.edge_dim > (uint32_t)kMaxEdgeTypes) {
+    set_error("%s: built for in_dim=%d hidden=%d out_dim=%d, 1..%d layers, 1..%d edge types "
+              "(got in_dim=%u hidden=%u out_dim=%u, %u layers, %u edge types)",
+              who, kInDim, kHidden, kOutDim, kMaxLayers, kMaxEdgeTypes, hd.in_dim, hd.hidden,
+              hd.out_dim, hd.layers, hd.edge_dim);
+    return GFY_ERR_UNSUPPORTED;
+  }
+  const size_t expected =
+      gfy_weight_pack_bytes(hd.in_dim, hd.hidden, hd.layers, hd.edge_dim, hd.out_dim);
+  if (bytes != expected) {
+    set_error("%s: weight pack is %zu bytes, expected %zu", who, bytes, expected);
+    return GFY_ERR_INVALID;
+  }
+  if (model_dtype != GFY_F16 && model_dtype != GFY_F32) {
+    set_error("%s: model_dtype must be GFY_F16 or GFY_F32", who);
+    return GFY_ERR_INVALID;
+  }
+  *view = PackView{};
+  view->layers = (int)hd.layers;
+  view->edge_dim = (int)hd.edge_dim;
+  view->residual = (int)(hd.flags & 1u);
+  PackCursor c{reinterpret_cast<const float*>(static_cast<const char*>(pack) + sizeof hd)};
+  walk_input(c, hd.in_dim, hd.hidden, *view);
+  for (int l = 0; l < view->layers; ++l) walk_layer(c, hd.hidden, hd.edge_dim, view->layer[l]);
+  walk_head(c, hd.hidden, hd.out_dim, *view);
+  return GFY_OK;
 }
 
 // Copies into page-locked staging memory (gfy_pack_microbatch).  The destination is written
@@ -223,7 +311,7 @@ int gfy_pack_microbatch(const float* node_features, int feature_dim, const int32
 
 size_t gfy_weight_pack_bytes(uint32_t in_dim, uint32_t hidden, uint32_t layers,
                              uint32_t edge_dim, uint32_t out_dim) {
-  return 32 + 4 * gfy::pack_floats(in_dim, hidden, layers, edge_dim, out_dim);
+  return sizeof(gfy::PackHeader) + 4 * gfy::pack_floats(in_dim, hidden, layers, edge_dim, out_dim);
 }
 
 }  // extern "C"

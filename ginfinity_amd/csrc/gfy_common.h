@@ -10,6 +10,7 @@
 #include <utility>
 
 #include "../../include/gfy.h"
+#include "weight_image.h"
 
 namespace gfy {
 
@@ -35,15 +36,7 @@ void clear_error();
     }                                 \
   } while (0)
 
-// ---- model geometry compiled into the kernels -----------------------------------
-constexpr int kHidden = 128;   // data/model.json:12
-constexpr int kMlp = 256;      // 2 * hidden       (_model.py:34)
-constexpr int kInDim = 7;      // node features    (graph.py:91-93)
-constexpr int kOutDim = 128;
-constexpr int kMaxEdgeTypes = 16;
-constexpr int kMaxLayers = 8;
-
-typedef _Float16 f16;
+// (model geometry compiled into the kernels: weight_pack.h; f16: weight_image.h)
 typedef f16 f16x8 __attribute__((ext_vector_type(8)));
 typedef f16 f16x4 __attribute__((ext_vector_type(4)));
 typedef f16 f16x2 __attribute__((ext_vector_type(2)));
@@ -75,22 +68,13 @@ class PerDeviceOnce {
   unsigned long long done_[4] = {};
 };
 
-// ---- fp16 layer parameters on the device (layouts: gine_layer.inc, gfy_api.hip) ---------
-// Hidden rows are stored with the channel groups 4-7 and 8-11 of every 16 swapped: 16-byte
-// chunk 2 s + hq of a row is then the eight values lane half hq holds for k-step s in the
-// MFMA C/D layout, so activations move between memory, LDS and MFMA operands as whole chunks.
-inline int stored_channel(int position) {   // an involution: bits 2 and 3 trade places
-  return (position & ~12) | ((position & 4) << 1) | ((position & 8) >> 1);
-}
-inline int gemm_result_channel(int block, int half, int reg) {   // 32x32 C/D layout
-  return 32 * block + (reg & 3) + 8 * (reg >> 2) + 4 * half;
-}
-
+// ---- fp16 layer parameters on the device (layouts: layer_image.h, weight_image.h; derived
+// by weight_image.cpp, bound to the device blob by gfy_encoder_create) -------------------------
 struct LayerF16 {
   float scale;            // fp16 value R(1 + R(eps)) widened to fp32
   int edge_types;         // edge_dim: rows of the edge table; an edge of another type is ignored
   const f16* w01_image;   // 128 KB: mlp.0.weight | mlp.4.weight fragments (pack_k_chained)
-  const void* image;      // 7,680-byte LDS image: edge table R(W_edge[:,t] + b_edge) in stored
+  const void* image;      // kImageBytes LDS image: edge table R(W_edge[:,t] + b_edge) in stored
                           // order + the -inf row of idle slots; BatchNorm alpha = invstd*gamma,
                           // shift = beta - mean*alpha (fp32, from fp16-rounded buffers) and
                           // LayerNorm gamma, beta as [block][lane half][register] of an MFMA
@@ -103,7 +87,7 @@ struct HeadF16 {
   const f16* wb_frag;  // head.2.weight fragments, pack_b_fragments
   const f16* bb;       // [128]
   const f16* w_image;  // 64 KB: head.0 (pack_k_chained) | head.2 (pack_chain_fragments)
-  const void* image;   // 512 B: ba as [block][half][register] | bb as natural 16-byte chunks
+  const void* image;   // kHeadImageBytes: ba as [block][half][register] | bb as natural chunks
 };
 
 struct ModelF16 {
@@ -476,17 +460,5 @@ __device__ __forceinline__ void dma_wait_all() {
   __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0); expcnt, lgkmcnt untouched
   asm volatile("" ::: "memory");
 }
-
-// W[n_out][k_in] (row-major fp16) -> fragments of the MFMA 32x32x16 A operand (out^T = W . in^T):
-// frag[(block * ksteps + s) * 64 + lane][j] = W[row(block, lane & 31)][k(s, lane >> 5, j)]
-//   pack_b_fragments      natural:  row = 32 block + m,  k = 16 s + 8 half + j
-//   pack_k_chained        the B operand is an MFMA result used in place (gine_layer.inc):
-//                         k = 16 s + 8 (j >> 2) + 4 half + (j & 3), rows natural
-//   pack_chain_fragments  same k; rows dealt so that the result's registers are natural
-//                         16-byte chunks of the output row (head.2 -> embedding)
-void pack_b_fragments(const f16* w, int n_out, int k_in, f16* frag);
-void pack_k_chained(const f16* w, int n_out, int k_in, f16* frag);
-void pack_chain_fragments(const f16* w, int n_out, int k_in, f16* frag);
-inline int hidden_layout_channel(int half, int ks, int j) { return 16 * ks + 8 * half + j; }
 
 }  // namespace gfy

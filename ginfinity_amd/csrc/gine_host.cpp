@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/gfy.h"
+#include "weight_pack.h"
 
 namespace gfy {
 void set_error(const char* fmt, ...);
@@ -32,7 +33,8 @@ void clear_error();
 
 namespace {
 
-constexpr int kH = 128, kM = 256, kIn = 7, kOut = 128, kMaxTypes = 16, kMaxLayers = 8;
+constexpr int kH = gfy::kHidden, kM = gfy::kMlp, kIn = gfy::kInDim, kOut = gfy::kOutDim,
+              kMaxTypes = gfy::kMaxEdgeTypes, kMaxLayers = gfy::kMaxLayers;
 
 // ---- fp16 <-> fp32 / fp64 by bit manipulation (round-to-nearest-even; no F16C needed) -------
 inline float half_bits_to_float(uint16_t h) {
@@ -106,10 +108,6 @@ struct gfy_host_encoder {
 };
 
 namespace {
-
-struct PackHeader {
-  uint32_t magic, version, in_dim, hidden, layers, edge_dim, out_dim, flags;
-};
 
 std::vector<float> transposed(const float* w, int rows, int cols, bool half) {
   std::vector<float> out((size_t)rows * cols);
@@ -194,90 +192,53 @@ int gfy_host_encoder_create(const void* weight_pack_host, size_t bytes, int mode
     return GFY_ERR_INVALID;
   }
   *out = nullptr;
-  PackHeader hd;
-  if (!weight_pack_host || bytes < sizeof hd) {
-    gfy::set_error("gfy_host_encoder_create: weight pack missing or truncated");
-    return GFY_ERR_INVALID;
-  }
-  std::memcpy(&hd, weight_pack_host, sizeof hd);
-  if (hd.magic != 0x31594647u || hd.version != 1) {
-    gfy::set_error("gfy_host_encoder_create: bad weight-pack magic/version");
-    return GFY_ERR_INVALID;
-  }
-  if (hd.hidden != (uint32_t)kH || hd.in_dim != (uint32_t)kIn || hd.out_dim != (uint32_t)kOut ||
-      hd.layers < 1 || hd.layers > (uint32_t)kMaxLayers || hd.edge_dim < 1 ||
-      hd.edge_dim > (uint32_t)kMaxTypes) {
-    gfy::set_error("gfy_host_encoder_create: built for in_dim=7 hidden=128 out_dim=128, "
-                   "1..8 layers, 1..16 edge types");
-    return GFY_ERR_UNSUPPORTED;
-  }
-  if (bytes != gfy_weight_pack_bytes(hd.in_dim, hd.hidden, hd.layers, hd.edge_dim, hd.out_dim)) {
-    gfy::set_error("gfy_host_encoder_create: weight pack is %zu bytes, expected %zu", bytes,
-                   gfy_weight_pack_bytes(hd.in_dim, hd.hidden, hd.layers, hd.edge_dim, hd.out_dim));
-    return GFY_ERR_INVALID;
-  }
-  if (model_dtype != GFY_F16 && model_dtype != GFY_F32) {
-    gfy::set_error("gfy_host_encoder_create: model_dtype must be GFY_F16 or GFY_F32");
-    return GFY_ERR_INVALID;
-  }
+  gfy::PackView pack;
+  if (const int rc = gfy::read_weight_pack("gfy_host_encoder_create", weight_pack_host, bytes,
+                                           model_dtype, &pack))
+    return rc;
   const bool half = model_dtype == GFY_F16;   // model.half(): parameters AND BatchNorm buffers
-  const float* p = reinterpret_cast<const float*>((const char*)weight_pack_host + sizeof hd);
-  auto take = [&](size_t count) {
-    const float* r = p;
-    p += count;
-    return r;
-  };
   gfy_host_encoder* enc = new gfy_host_encoder();
   enc->model_dtype = model_dtype;
-  enc->layers = (int)hd.layers;
-  enc->edge_dim = (int)hd.edge_dim;
-  enc->residual = (int)(hd.flags & 1u);
-  enc->w_in_t = transposed(take((size_t)kH * kIn), kH, kIn, half);
-  enc->b_in = copied(take(kH), kH, half);
+  enc->layers = pack.layers;
+  enc->edge_dim = pack.edge_dim;
+  enc->residual = pack.residual;
+  enc->w_in_t = transposed(pack.w_in, kH, kIn, half);
+  enc->b_in = copied(pack.b_in, kH, half);
   const int ED = enc->edge_dim;
   for (int l = 0; l < enc->layers; ++l) {
     HostLayer& L = enc->layer[l];
-    const float* eps = take(1);
-    const float* ew = take((size_t)kH * ED);
-    const float* eb = take(kH);
-    const float* w0 = take((size_t)kM * kH);
-    const float* b0 = take(kM);
-    const float* bg = take(kM);
-    const float* bb = take(kM);
-    const float* bm = take(kM);
-    const float* bv = take(kM);
-    const float* w1 = take((size_t)kH * kM);
-    const float* b1 = take(kH);
-    const float* lg = take(kH);
-    const float* lb = take(kH);
-    L.scale = half ? R(1.0f + R(eps[0])) : 1.0f + eps[0];
+    const gfy::PackLayer& from = pack.layer[l];
+    L.scale = half ? R(1.0f + R(from.eps[0])) : 1.0f + from.eps[0];
     L.table.assign((size_t)kMaxTypes * kH, 0.f);
     for (int t = 0; t < ED; ++t)
-      for (int c = 0; c < kH; ++c)   // edge_lin on a one-hot row = one weight column + bias
-        L.table[(size_t)t * kH + c] =
-            half ? R(R(ew[(size_t)c * ED + t]) + R(eb[c])) : ew[(size_t)c * ED + t] + eb[c];
-    L.w0t = transposed(w0, kM, kH, half);
-    L.b0 = copied(b0, kM, half);
+      for (int c = 0; c < kH; ++c) {   // edge_lin on a one-hot row = one weight column + bias
+        const float w = from.edge_w[(size_t)c * ED + t], b = from.edge_b[c];
+        L.table[(size_t)t * kH + c] = half ? R(R(w) + R(b)) : w + b;
+      }
+    L.w0t = transposed(from.w0, kM, kH, half);
+    L.b0 = copied(from.b0, kM, half);
     L.alpha.resize(kM);
     L.shift.resize(kM);
     for (int c = 0; c < kM; ++c) {   // BatchNorm1d eval as torch's CPU kernel evaluates it
-      const float g = half ? R(bg[c]) : bg[c], b = half ? R(bb[c]) : bb[c];
-      const float mean = half ? R(bm[c]) : bm[c], var = half ? R(bv[c]) : bv[c];
+      const float g = half ? R(from.bn_gamma[c]) : from.bn_gamma[c];
+      const float b = half ? R(from.bn_beta[c]) : from.bn_beta[c];
+      const float mean = half ? R(from.bn_mean[c]) : from.bn_mean[c];
+      const float var = half ? R(from.bn_var[c]) : from.bn_var[c];
       const float invstd = 1.0f / std::sqrt(var + 1e-5f);
       const float alpha = invstd * g;
       const float prod = mean * alpha;
       L.alpha[c] = alpha;
       L.shift[c] = b - prod;
     }
-    L.w1t = transposed(w1, kH, kM, half);
-    L.b1 = copied(b1, kH, half);
-    L.gamma = copied(lg, kH, half);
-    L.beta = copied(lb, kH, half);
+    L.w1t = transposed(from.w1, kH, kM, half);
+    L.b1 = copied(from.b1, kH, half);
+    L.gamma = copied(from.ln_gamma, kH, half);
+    L.beta = copied(from.ln_beta, kH, half);
   }
-  enc->wa_t = transposed(take((size_t)kH * kH), kH, kH, half);
-  enc->ba = copied(take(kH), kH, half);
-  enc->wb_t = transposed(take((size_t)kOut * kH), kOut, kH, half);
-  enc->bb = copied(take(kOut), kOut, half);
+  enc->wa_t = transposed(pack.wa, kH, kH, half);
+  enc->ba = copied(pack.ba, kH, half);
+  enc->wb_t = transposed(pack.wb, kOut, kH, half);
+  enc->bb = copied(pack.bb, kOut, half);
   *out = enc;
   return GFY_OK;
 }

@@ -15,7 +15,7 @@
 //    half-swap, and nothing goes through LDS between the phases of a tile.  The k order this
 //    implies inside an MFMA is undone on the host (pack_k_chained).  Hidden rows are STORED in
 //    this order too (16-byte chunk 2 s + hq of a row = the lane's eight values: within every
-//    16 channels the groups 4-7 and 8-11 trade places, gfy_common.h stored_channel);
+//    16 channels the groups 4-7 and 8-11 trade places, weight_image.h stored_channel);
 //  * the gather-sum reads source rows (in-tile and out-of-tile alike) and edge-type rows out
 //    of LDS with ds_read_b128, forms relu(h + T) in packed fp16, and ACCUMULATES ON THE MATRIX
 //    CORES: one MFMA with a 0/1 selection matrix adds a slot's 16 channels x 32 nodes into an
@@ -66,21 +66,22 @@ constexpr int kLdsW1 = 64 * 1024;
 constexpr int kLdsWeightBytes = 128 * 1024;
 constexpr int kLdsStageBytes = kLStageRows * 256;    // 18,432: row q, 16-byte position p holds
                                                      // chunk p ^ (q & 15)
-constexpr int kLdsImage = kLWaves * kLdsStageBytes;  // per-layer constant image (gfy_api.hip):
-constexpr int kLdsTable = kLdsImage;                 //   17 x 256 B edge table, stored order
-constexpr int kLdsAlpha = kLdsImage + 4352;          //   f32 [8][2][16]   MFMA result order
-constexpr int kLdsShift = kLdsAlpha + 1024;
-constexpr int kLdsB0 = kLdsShift + 1024;             //   f16 [256]        natural channel order (bias MFMAs)
-constexpr int kLdsB1 = kLdsB0 + 512;                 //   f16 [128]        natural channel order
-constexpr int kLdsGamma = kLdsB1 + 256;
-constexpr int kLdsBeta = kLdsGamma + 256;
-constexpr int kLdsImageBytes = 4352 + 2 * 1024 + 512 + 3 * 256;   // 7,680
-constexpr int kLdsHeadBa = kLdsImage + kLdsImageBytes;   // f16 [4][2][16]  MFMA result order
-constexpr int kLdsHeadBb = kLdsHeadBa + 256;             // f16 [2][8][8]   natural 16-B chunks
-constexpr int kLdsBytes = kLdsHeadBb + 256;              // 155,648
+constexpr int kLdsImage = kLWaves * kLdsStageBytes;  // per-layer constant image, then the head's:
+constexpr int kLdsTable = kLdsImage + kImageTable;   // layer_image.h has the fields and their
+constexpr int kLdsAlpha = kLdsImage + kImageAlpha;   // layouts, weight_image.cpp writes them
+constexpr int kLdsShift = kLdsImage + kImageShift;
+constexpr int kLdsB0 = kLdsImage + kImageB0;
+constexpr int kLdsB1 = kLdsImage + kImageB1;
+constexpr int kLdsGamma = kLdsImage + kImageGamma;
+constexpr int kLdsBeta = kLdsImage + kImageBeta;
+constexpr int kLdsImageBytes = kImageBytes;                              // 7,680
+constexpr int kLdsHeadBa = kLdsImage + kImageBytes + kHeadImageBa;
+constexpr int kLdsHeadBb = kLdsImage + kImageBytes + kHeadImageBb;
+constexpr int kLdsBytes = kLdsImage + kImageBytes + kHeadImageBytes;     // 155,648
 static_assert(kLdsStageBytes * kLWaves >= kLdsWeightBytes, "the weights overlay the stages");
 static_assert(kLdsStageBytes % 1024 == 0, "a stage is refilled by whole 1-KB DMA instructions");
 static_assert(kLdsImageBytes == 480 * 16, "one 16-byte chunk per thread 0..479");
+static_assert(kHeadImageBytes == 32 * 16, "the head image: 32 more chunks (512 bytes of LDS)");
 static_assert(kLdsBytes <= 160 * 1024, "one workgroup per CU");
 
 // ---------------------------------------------------------------------------------
