@@ -48,6 +48,11 @@ class GfyShard(Structure):
 #: match_scale, match_shift, gap_open, gap_extend
 _ALIGN_CALL = [c_void_p, c_int64] * 5 + [c_float] * 4
 
+#: what the two run calls start with: offsets, n, indices, values, hits, ptr_a, records_a, ptr_b,
+#: records_b, m
+_HIT_RUNS_CALL = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
+                  c_int64, c_int64]
+
 #: every symbol include/gfy.h declares: (restype, argtypes)
 SIGNATURES: dict[str, tuple] = {
     "gfy_last_error": (c_char_p, []),
@@ -165,6 +170,12 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_align_global_trace": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t,
                                        c_void_p]),
+    "gfy_hit_runs_workspace_bytes": (c_size_t, [c_int64]),
+    "gfy_hit_runs_mark": (c_int, [*_HIT_RUNS_CALL, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
+    "gfy_hit_runs_emit": (c_int, [*_HIT_RUNS_CALL, c_void_p, c_void_p, c_int, c_int64, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                  c_void_p]),
 }
 
 

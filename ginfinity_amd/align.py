@@ -7,6 +7,15 @@ picks from that ranking, without the embeddings leaving the device:
     pairs = align.top_pairs(scores, 8, largest=True)
     score, end = align.local_align(rows, counts_a=counts, pairs=pairs, gap_open=1.0, gap_extend=0.25)
 
+The sparse chain needs no dense ``[Q, R]`` matrix: the radius search, its hits collapsed into
+diagonal runs, the best runs as seeds, alignment inside a band around each seed's diagonal:
+
+    hits = distance.within(rows, threshold=0.9, metric="cosine", exclude_records=counts)
+    runs = align.hit_runs(hits, counts_a=counts, min_length=8)
+    best = runs.best(64)                                    # host indices: longest, then heaviest
+    paths = align.local_paths(rows, counts_a=counts, pairs=runs.pairs[best],
+                              band=runs.bands(16)[best], gap_open=1.0, gap_extend=0.25)
+
 **This is not ``ginfinity-sw``.**  The reference delegates alignment to that external package,
 which is not in its tree; it holds the names of eight scoring parameters and no formula.  The
 semantics below are defined here and in include/gfy.h, as the whole distance path's are.
@@ -136,7 +145,9 @@ follows that
   path cell always has a positive value, so the walk never leaves the band;
 * re-scoring the ops gives ``score`` bit for bit, as without a band.
 
-``band_around`` makes bands from seed cells, such as the hits of ``distance.topk``.  The device
+``band_around`` makes bands from seed cells: ``hit_cells`` gives one seed per hit of
+``distance.topk`` or ``within``, ``hit_runs`` one per maximal diagonal run of ``within`` hits (its
+definition is in the function's docstring and in include/gfy.h).  The device
 does not do the work outside the band: a strip of 64 rows from row ``i0`` holds band cells in the
 columns ``c_lo = max(0, i0 + lo) .. c_hi = min(Lr - 1, i0 + rows - 1 + hi)`` only, a strip
 without any is skipped, and a strip takes ``c_hi - (c_lo & ~31) + rows`` steps against ``Lr + rows
@@ -148,7 +159,9 @@ Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIM
 and ``within`` modes (borders that leave the band, pairs with no admissible path at all),
 band-only storage of the direction words, a span-only kernel for the global and ``within`` modes,
 free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
-scores.  Measured cost: DESIGN.md §4.
+scores.  Out of scope for ``hit_runs``: gapped chaining of runs across neighbouring diagonals, a
+cross-shard form in ``parallel.py``, runs from ``topk`` results (a ``[n, k]`` block is not sorted
+by b-row), and a ``device="cpu"`` path.  Measured cost: DESIGN.md §4.
 """
 from __future__ import annotations
 
@@ -159,7 +172,7 @@ import numpy as np
 import torch
 
 from . import _native as native
-from .distance import _checked, _grown, _prepare, _record_ptr
+from .distance import _checked, _checked_counts, _grown, _prepare, _record_ptr, record_of
 
 
 class AlignWorkspace:
@@ -228,18 +241,10 @@ def band_around(seeds, half_width: int) -> np.ndarray:
     ``(j - i - half_width, j - i + half_width)`` for ``seeds``, an integer ``[P, 2]`` array (numpy
     or torch) of cells ``(i, j)`` inside the two records of each pair; ``half_width`` is a
     non-negative integer, 0 the seed's diagonal alone.  A pure function of its arguments: no
-    device is needed.  A hit of ``distance.topk`` (row ``x`` of ``a``, row ``idx[x, k]`` of ``b``)
-    becomes a seed by taking away each record's first row.  ``rows``, ``idx`` and the counts are
-    arrays of one library (torch: on one device) — the tuple of counts that
-    ``encode_graphs_device`` returns cannot be indexed by ``q``, so it is made a tensor first —
-    and ``stack`` and ``cumsum`` are that library's:
-
-        counts_a = torch.as_tensor(counts_a, device=idx.device)           # counts_b likewise;
-                                                                          # numpy: np.asarray(counts_a)
-        q, r = distance.record_of(rows, counts_a), distance.record_of(idx[rows, k], counts_b)
-        seeds = stack([rows - cumsum(counts_a)[q] + counts_a[q],          # minus the record's
-                       idx[rows, k] - cumsum(counts_b)[r] + counts_b[r]], 1)    # first row
-        band = align.band_around(seeds, 64)            # with pairs=stack([q, r], 1)
+    device is needed.  ``hit_cells`` turns the hits of ``distance.topk`` / ``within`` into seeds
+    (one per hit, by taking away each record's first row) and the ``pairs`` that go with them;
+    ``hit_runs`` makes one seed per diagonal run of ``within`` hits, and ``Runs.bands`` is this
+    function on them.
     """
     if isinstance(half_width, (bool, np.bool_)) or \
             not isinstance(half_width, (int, np.integer)) or half_width < 0:
@@ -259,6 +264,230 @@ def band_around(seeds, half_width: int) -> np.ndarray:
     limit = 2 * native.GFY_ALIGN_ROWS_MAX      # wider than any matrix: the values stay int32
     width = min(int(half_width), limit)
     return np.stack([diagonal - width, diagonal + width], axis=1).astype(np.int32)
+
+
+def hit_cells(rows, indices, counts_a, counts_b=None) -> tuple:
+    """Hits as seed cells: ``(q, r, cells)`` for the hits (row ``rows[x]`` of ``a``, row
+    ``indices[x]`` of ``b``) of ``distance.topk`` / ``nearest`` / ``within`` — ``q`` and ``r`` the
+    records of the two rows (``distance.record_of``: a row at a boundary belongs to the record
+    that starts there) and ``cells`` ``[P, 2]`` the rows minus each record's first row, which is
+    what ``band_around`` takes as seeds and ``stack([q, r], 1)`` what the aligners take as
+    ``pairs``.  One seed per hit; ``hit_runs`` makes one per stretch of collinear hits.
+
+    ``rows`` and ``indices`` are integer arrays of one shape and one library: torch tensors (on
+    one device; the results stay there, ``q`` and ``r`` int32, ``cells`` int64) or numpy arrays
+    (numpy results).  ``counts_a`` / ``counts_b`` are the row counts of the records of ``a`` /
+    ``b`` (any integer sequence, checked as ``record_of`` checks them; ``counts_b`` defaults to
+    ``counts_a``).  An index outside every record, ``-1`` included, gives record ``-1`` and a
+    cell coordinate of ``-1``."""
+    counts_a = _checked_counts(counts_a)
+    counts_b = counts_a if counts_b is None else _checked_counts(counts_b)
+    as_torch = isinstance(rows, torch.Tensor)
+    if as_torch != isinstance(indices, torch.Tensor):
+        raise ValueError("rows and indices must both be torch tensors or both numpy arrays")
+    if not as_torch:
+        rows, indices = (torch.from_numpy(np.ascontiguousarray(x)) for x in (rows, indices))
+    if rows.shape != indices.shape or rows.dim() != 1 or rows.device != indices.device or \
+            rows.dtype.is_floating_point or indices.dtype.is_floating_point or \
+            torch.bool in (rows.dtype, indices.dtype):
+        raise ValueError("rows and indices must be one-dimensional integer arrays of one length "
+                         "(torch: on one device)")
+    found, inside = [], []
+    for index, counts in ((rows, counts_a), (indices, counts_b)):
+        record = record_of(index, counts)
+        first = torch.from_numpy(np.concatenate(([0], np.cumsum(counts)))).to(index.device)
+        outside = record < 0
+        start = first[torch.where(outside, torch.zeros_like(record), record).to(torch.int64)]
+        found.append(record)
+        inside.append(torch.where(outside, torch.full_like(start, -1),
+                                  index.to(torch.int64) - start))
+    cells = torch.stack(inside, dim=1)
+    if as_torch:
+        return found[0], found[1], cells
+    return found[0].numpy(), found[1].numpy(), cells.numpy()
+
+
+class Runs(NamedTuple):
+    """What ``hit_runs`` returns, all on the device: run s lies in the record pair ``pairs[s]``,
+    starts at the cell ``cells[s]`` inside the two records, and is ``lengths[s]`` hits long on
+    the diagonal ``cells[s, 1] - cells[s, 0]``; ``weights[s]`` is the sum of its values."""
+    pairs: torch.Tensor     # int32 [S, 2] of (record of a, record of b)
+    cells: torch.Tensor     # int32 [S, 2] of the head (i, j) inside the two records
+    lengths: torch.Tensor   # int32 [S]
+    weights: torch.Tensor   # float32 [S]
+
+    def bands(self, half_width: int) -> np.ndarray:
+        """``band_around(self.cells, half_width)``: the band of every run's diagonal for
+        ``local_align`` / ``local_spans`` / ``local_paths`` with ``pairs=self.pairs``."""
+        return band_around(self.cells, half_width)
+
+    def best(self, k: int) -> np.ndarray:
+        """The indices (int64 host array, at most ``k``) of the ``k`` runs that come first in the
+        order ``lengths`` descending, then ``weights`` descending, then position ascending; a NaN
+        weight ranks behind every number of its length.  A pure function of ``lengths`` and
+        ``weights``, which come to the host for it."""
+        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+            raise ValueError("k must be a positive integer")
+        lengths, weights = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor)
+                            else np.asarray(x) for x in (self.lengths, self.weights))
+        missing = np.isnan(weights)
+        # by (length, NaN or not, weight, position): lexsort is stable and takes its last key first
+        order = np.lexsort((np.where(missing, 0, -weights.astype(np.float64)), missing,
+                            -lengths.astype(np.int64)))
+        return order[:int(k)].astype(np.int64)
+
+
+class RunsWorkspace:
+    """Scratch memory, marks and slots of ``hit_runs`` kept across calls (the runs are always new
+    tensors)."""
+
+    def __init__(self) -> None:
+        self.scratch: torch.Tensor | None = None
+        self.marks: torch.Tensor | None = None
+        self.slots: torch.Tensor | None = None
+
+    def buffers(self, device, hits: int, scratch_bytes: int):
+        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
+        self.marks = _grown(self.marks, device, hits, torch.int32)
+        self.slots = _grown(self.slots, device, hits, torch.int64)
+        return self.scratch, self.marks[:hits], self.slots[:hits]
+
+
+def _checked_hits(hits) -> tuple:
+    """``(offsets, indices, values)`` of a ``distance.Hits`` (or any triple of torch tensors or
+    numpy arrays) with the dtypes and shapes of ``within``'s result, wherever they live."""
+    if not isinstance(hits, tuple) or len(hits) != 3:
+        raise ValueError("hits must be a distance.Hits (offsets, indices, values)")
+    parts = []
+    for part, name, dtype in zip(hits, ("offsets", "indices", "values"),
+                                 (torch.int64, torch.int32, torch.float32)):
+        if isinstance(part, np.ndarray):
+            part = torch.from_numpy(np.ascontiguousarray(part))
+        if not isinstance(part, torch.Tensor) or part.dtype != dtype or part.dim() != 1:
+            raise ValueError(f"hits.{name} must be a one-dimensional "
+                             f"{str(dtype).replace('torch.', '')} array")
+        parts.append(part)
+    offsets, indices, values = parts
+    if offsets.numel() < 1:
+        raise ValueError("hits.offsets must hold n + 1 entries")
+    if indices.numel() != values.numel():
+        raise ValueError(f"hits.indices has {indices.numel()} entries, hits.values "
+                         f"{values.numel()}")
+    if indices.numel() >= 2 ** 31 - 1:
+        raise ValueError("hits must hold fewer than 2^31 - 1 hits")
+    return offsets, indices, values
+
+
+def hit_runs(hits, *, counts_a, counts_b=None, min_length: int = 1,
+             workspace: RunsWorkspace | None = None) -> Runs:
+    """The maximal diagonal runs of the hits of ``distance.within``: ``Runs(pairs int32 [S, 2],
+    cells int32 [S, 2], lengths int32 [S], weights float32 [S])`` on the device.  A stretch that
+    two records share is one hit per row on one diagonal; this collapses each into one seed with
+    the evidence behind it, and ``pairs`` says which records are worth aligning at all without a
+    dense ``record_scores``.
+
+    Definition (include/gfy.h has it too).  ``hits = Hits(offsets int64 [n + 1], indices int32
+    [H], values float32 [H])``: row i's hits are ``indices[offsets[i]:offsets[i + 1]]``, strictly
+    ascending, the contract of ``within``.  ``counts_a`` are the rows of ``a`` in contiguous
+    records (``sum == n``, zero counts allowed), ``counts_b`` those of ``b`` (``sum == m``;
+    default ``counts_a``, the self-search form), ``ptr_a`` / ``ptr_b`` their running sums.  A row
+    at a boundary belongs to the record that starts there, a record of zero rows owns nothing
+    (``distance.record_of``).  For a hit ``(i, j)`` let ``q``, ``r`` be the records of ``i`` and
+    ``j``.  Its predecessor is ``(i - 1, j - 1)``; it counts only if it is a hit, ``i - 1 >=
+    ptr_a[q]`` and ``j - 1 >= ptr_b[r]``, so that it lies in the same two records.  A hit without
+    a predecessor is a head; the run of a head is the hits ``(i + t, j + t)``, ``t = 0 .. L - 1``,
+    for the largest ``L`` for which all of them are hits inside records ``q`` and ``r``.  Every
+    hit belongs to exactly one run, and a run never crosses a record boundary on either side.
+    Run s has ``pairs[s] = (q, r)``, ``cells[s] = (i - ptr_a[q], j - ptr_b[r])`` (its head inside
+    the two records), ``lengths[s] = L`` and ``weights[s]`` = the sum of its ``L`` values,
+    accumulated in float64 in ascending ``t``, each addition one rounded operation, and rounded
+    to float32 once (the rule of ``record_scores``).  Runs come in the order of their heads
+    inside ``hits``: ``i`` ascending, then ``j`` ascending.  ``min_length`` (an integer >= 1)
+    drops the shorter runs and keeps the order of the rest.
+
+    A run is a function of the hits and the counts alone, bit for bit.  So the lengths sum to
+    ``H`` at ``min_length=1``; ``min_length=k`` is that result filtered by length; and a record
+    that is a bit-identical copy of another gives, under a threshold its rows pass, exactly one
+    run ``(q, r, (0, 0), rows of the record)`` on the pair's main diagonal, whatever else hits.
+
+    Every argument error is a ``ValueError`` before a device is touched: dtypes, shapes,
+    ``min_length``, the counts (checked as ``record_scores`` checks them), ``offsets.numel() ==
+    sum(counts_a) + 1``.  Three more need the data and are made on the device in front of the
+    launch — ``offsets[0] == 0``; ``offsets`` non-decreasing with ``offsets[-1] == H``; ``0 <=
+    indices < sum(counts_b)`` — so that no hand-made ``Hits`` makes a kernel read outside its
+    arrays.  Ascending order inside a row is a precondition and is not checked.  Hits on the
+    host are moved to the device, as rows are; there is no CPU path.
+
+    Two launches with a running sum between them (``torch.cumsum``: plumbing, as in ``within``),
+    whose total comes to the host, which waits for the device as ``within`` does.  One lane per
+    hit; a head walks its run serially, so a run of ``L`` hits is ``L`` steps of one lane
+    (DESIGN.md §4).  ``H == 0`` or ``n == 0`` returns four empty tensors without a launch."""
+    offsets, indices, values = _checked_hits(hits)
+    if isinstance(min_length, (bool, np.bool_)) or \
+            not isinstance(min_length, (int, np.integer)) or min_length < 1:
+        raise ValueError("min_length must be a positive integer")
+    if workspace is not None and not isinstance(workspace, RunsWorkspace):
+        raise ValueError("workspace must be a RunsWorkspace")
+    n, total = offsets.numel() - 1, indices.numel()
+    ptr_a = _record_ptr(counts_a, n, "counts_a", "hits")
+    if counts_b is None:
+        ptr_b = ptr_a
+    else:
+        ptr_b = _record_ptr(counts_b, int(_checked_counts(counts_b).sum()), "counts_b", "b")
+    m = int(ptr_b[-1])
+    devices = {part.device for part in (offsets, indices, values) if part.device.type == "cuda"}
+    if len(devices) > 1:
+        raise ValueError("hits must live on one device")
+    device = devices.pop() if devices else torch.device("cuda")
+    offsets, indices, values = (part.to(device).contiguous()
+                                for part in (offsets, indices, values))
+    device = offsets.device
+    with torch.cuda.device(device):
+        # every entry at or above its predecessor, the first 0, the last H; every index a row of b
+        sound = (offsets[0] == 0) & (offsets[-1] == total) & \
+            (offsets[1:] >= offsets[:-1]).all()
+        if total:
+            sound = sound & (indices.min() >= 0) & (indices.max() < m)
+        if not bool(sound.item()):
+            raise ValueError(
+                "hits are not those of a search: offsets must start at 0, never decrease and end "
+                f"at {total} = the number of hits, and indices must lie in 0..{m - 1}")
+        empty = Runs(torch.zeros((0, 2), dtype=torch.int32, device=device),
+                     torch.zeros((0, 2), dtype=torch.int32, device=device),
+                     torch.zeros(0, dtype=torch.int32, device=device),
+                     torch.zeros(0, dtype=torch.float32, device=device))
+        if total == 0 or n == 0:
+            return empty
+        lib = native.library()
+        scratch, marks, slots = (workspace or RunsWorkspace()).buffers(
+            device, total, lib.gfy_hit_runs_workspace_bytes(total))
+        ptr_a_dev = torch.from_numpy(ptr_a.astype(np.int32)).to(device)
+        ptr_b_dev = ptr_a_dev if ptr_b is ptr_a else \
+            torch.from_numpy(ptr_b.astype(np.int32)).to(device)
+        status = torch.zeros(2, dtype=torch.int32, device=device)
+        front = (offsets.data_ptr(), n, indices.data_ptr(), values.data_ptr(), total,
+                 ptr_a_dev.data_ptr(), ptr_a.size - 1, ptr_b_dev.data_ptr(), ptr_b.size - 1, m,
+                 marks.data_ptr())
+        back = (scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(device).cuda_stream)
+        native.check(lib.gfy_hit_runs_mark(*front, status[0:].data_ptr(), *back),
+                     "gfy_hit_runs_mark")
+        torch.cumsum(marks >= int(min_length), 0, dtype=torch.int64, out=slots)
+        count = int(slots[-1].item())   # waits for the device
+        if count == 0:
+            runs = empty
+        else:
+            runs = Runs(torch.empty((count, 2), dtype=torch.int32, device=device),
+                        torch.empty((count, 2), dtype=torch.int32, device=device),
+                        torch.empty(count, dtype=torch.int32, device=device),
+                        torch.empty(count, dtype=torch.float32, device=device))
+            native.check(lib.gfy_hit_runs_emit(
+                *front, slots.data_ptr(), min(int(min_length), 2 ** 31 - 1), count,
+                *(out.data_ptr() for out in runs), status[1:].data_ptr(), *back),
+                "gfy_hit_runs_emit")
+        if bool(status.any().item()):
+            raise native.NativeLibraryError(
+                "gfy_hit_runs: the hits contradicted the sizes of the call")
+        return runs
 
 
 def _checked_parameter(value, name: str) -> float:
@@ -647,4 +876,5 @@ def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
 
 
 __all__ = ["local_align", "local_spans", "local_paths", "global_align", "global_paths",
-           "path_cells", "AlignedPaths", "AlignWorkspace", "top_pairs", "band_around"]
+           "path_cells", "AlignedPaths", "AlignWorkspace", "top_pairs", "band_around",
+           "hit_cells", "hit_runs", "Runs", "RunsWorkspace"]

@@ -946,6 +946,75 @@ int gfy_align_global_trace(const void* a, int64_t n, const int32_t* ptr_a, int64
                            int64_t max_rows_a, int64_t max_rows_b,
                            void* workspace, size_t workspace_bytes, void* stream);
 
+/* Seeds from radius-search hits: the MAXIMAL DIAGONAL RUNS of the hits of
+ * gfy_pairwise_within_fill, the step between that search and the gfy_align_*_band calls.  A
+ * stretch that two records share is one hit per row on one diagonal; this call collapses every
+ * such stretch into one seed with the evidence behind it.
+ *   Hits        offsets int64 [n + 1], indices int32 [hits], values float32 [hits], device
+ *               memory, as gfy_pairwise_within_fill leaves them: row i's hits are the b-rows
+ *               indices[offsets[i] .. offsets[i + 1]), STRICTLY ASCENDING (a precondition; a
+ *               segment in another order gives runs of no meaning and no stray access),
+ *               offsets[0] = 0, offsets non-decreasing, offsets[n] = hits, 0 <= indices < m.
+ *   Records     rows of a in records_a contiguous records by ptr_a (int32 running sums,
+ *               [records_a + 1], device memory, ptr_a[records_a] = n), rows of b in records_b by
+ *               ptr_b (ptr_b[records_b] = m), as the alignment calls take them.  A row at a
+ *               boundary belongs to the record that starts there; a record of zero rows owns
+ *               nothing.  For a hit (i, j) let q, r be the records of i and j.
+ *   Runs        The predecessor of (i, j) is (i - 1, j - 1); it counts only if it is a hit, i - 1
+ *               >= ptr_a[q] and j - 1 >= ptr_b[r], so that it lies in the same two records.  A
+ *               hit without a predecessor is a HEAD.  The run of a head is the hits (i + t, j +
+ *               t), t = 0 .. L - 1, for the largest L for which all of them are hits inside
+ *               records q and r.  Every hit belongs to exactly one run, and a run never crosses a
+ *               record boundary on either side.
+ *   gfy_hit_runs_mark   marks int32 [hits]: L at a head, 0 at every other hit.  The float64 sums
+ *               of the heads go to the workspace.
+ *   gfy_hit_runs_emit   slots int64 [hits], device memory: the running sums of (marks[h] >=
+ *               min_length), the entry of h included; runs = slots[hits - 1] >= 1; min_length >=
+ *               1.  The head h with marks[h] >= min_length is run s = slots[h] - 1 — the runs come
+ *               in the order of their heads, i ascending, then j ascending — and gets
+ *                 out_pairs[s]   = (q, r)                               int32 [runs][2]
+ *                 out_cells[s]   = (i - ptr_a[q], j - ptr_b[r])         int32 [runs][2]: the head
+ *                                  inside the two records; its diagonal is the run's
+ *                 out_lengths[s] = L                                    int32 [runs]
+ *                 out_weights[s] = the sum of the run's L values, accumulated in float64 in
+ *                                  ascending t, each addition one rounded operation, rounded to
+ *                                  float32 once (the rule of gfy_pairwise_record_scores)
+ *               with the SAME workspace, untouched since the mark call on the same hits.
+ *   It follows  A run is a function of the hits and the records alone: it depends neither on how
+ *               the call is cut into workgroups nor on the run of the program, bit for bit.  The
+ *               lengths of all runs sum to hits at min_length = 1, and min_length = k gives the
+ *               runs of min_length = 1 with L >= k, in the same order.
+ *   Safety      *status (int32, one word, device memory, zeroed by each call) is set non-zero
+ *               when offsets, indices or the pointers contradict the sizes of the call, or slots
+ *               does not number the kept heads: every index read from memory is clipped or
+ *               checked in front of its use, so whatever the arrays hold, no access leaves them
+ *               and a hit that does not fit is left out.
+ *   Cost        one lane per hit and binary searches: a hit finds its a-row in offsets, its
+ *               records in ptr_a / ptr_b, its predecessor in the row above; a head then walks
+ *               its diagonal with one binary search per step, so a run of L hits is L serial
+ *               steps of one lane (no pointer jumping).  No atomics on the results, no sort.
+ *               Measured cost: DESIGN.md §4.
+ *   Workspace   gfy_hit_runs_workspace_bytes(hits): one float64 per hit.
+ *   A NULL pointer, n, m or hits outside 1..2^31 - 2, records_a or records_b outside
+ *   1..GFY_PAIRWISE_RECORDS_MAX, min_length < 1 and runs outside 1..hits are GFY_ERR_INVALID, a
+ *   short workspace is GFY_ERR_WORKSPACE; all of it before any launch and without a device.   */
+size_t gfy_hit_runs_workspace_bytes(int64_t hits);
+int gfy_hit_runs_mark(const int64_t* offsets /* [n + 1] */, int64_t n,
+                      const int32_t* indices /* [hits] */, const float* values /* [hits] */,
+                      int64_t hits, const int32_t* ptr_a, int64_t records_a,
+                      const int32_t* ptr_b, int64_t records_b, int64_t m,
+                      int32_t* marks /* [hits] */, int32_t* status,
+                      void* workspace, size_t workspace_bytes, void* stream);
+int gfy_hit_runs_emit(const int64_t* offsets /* [n + 1] */, int64_t n,
+                      const int32_t* indices /* [hits] */, const float* values /* [hits] */,
+                      int64_t hits, const int32_t* ptr_a, int64_t records_a,
+                      const int32_t* ptr_b, int64_t records_b, int64_t m,
+                      const int32_t* marks /* [hits] */, const int64_t* slots /* [hits] */,
+                      int min_length, int64_t runs,
+                      int32_t* out_pairs /* [runs][2] */, int32_t* out_cells /* [runs][2] */,
+                      int32_t* out_lengths /* [runs] */, float* out_weights /* [runs] */,
+                      int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
