@@ -911,6 +911,95 @@ __device__ __forceinline__ void layer_norm_residual(const f16x8 (&wrow)[8], cons
   layer_norm_affine<kResidual>(wrow, m, h, hn, gamma, beta, hq);
 }
 
+// ---------------------------------------------------------------------------------
+// What every layer kernel (this file, gine_layer_q.inc, _w.inc, _x.inc) and k_head_d do around
+// the pipelines, once.  A kernel whose loop re-derives its lane pieces per phase (opaque,
+// gine_layer_q.inc) hands (r, hq) of that phase in: nothing here looks at threadIdx.
+// Each of these compiles to the instructions of the code it replaced.  Two blocks that every
+// kernel still carries do not when they are wrapped — the gather dispatch (gather_tile<3..8> |
+// gather_direct | zeros) and the bracketed normalise behind head_row_square_sum — and stay
+// where they are, as do the three call sites that say so (profiles/layer_shared_refactor.txt).
+// ---------------------------------------------------------------------------------
+// Raise the wave to s_setprio level 1..3 (the builtin takes an immediate); level 0 leaves the
+// priority as it is — going back to 0 is the caller's own s_setprio(0)
+__device__ __forceinline__ void raise_wave_priority(int level) {
+  if (level == 1) __builtin_amdgcn_s_setprio(1);
+  else if (level == 2) __builtin_amdgcn_s_setprio(2);
+  else if (level == 3) __builtin_amdgcn_s_setprio(3);
+}
+
+// the eight slot words (stage row | type << 8) of row r of a tile plan
+__device__ __forceinline__ void load_plan_words(const char* plan, int r, uint32_t (&word)[8]) {
+  const u32x4 wa = reinterpret_cast<const u32x4*>(plan + kPlanWords + r * 32)[0];
+  const u32x4 wb = reinterpret_cast<const u32x4*>(plan + kPlanWords + r * 32)[1];
+  word[0] = wa[0], word[1] = wa[1], word[2] = wa[2], word[3] = wa[3];
+  word[4] = wb[0], word[5] = wb[1], word[6] = wb[2], word[7] = wb[3];
+}
+
+// kSteps k-steps of lane (., hq) -> row `row` of a tensor in stored order: 16-byte chunk
+// 2 ks + hq of the row (hidden rows, z, w, y, the embeddings: eight, 256 B; v: sixteen, 512 B)
+template <int kSteps>
+__device__ __forceinline__ void store_row(void* base, size_t row, int hq,
+                                          const f16x8 (&regs)[kSteps]) {
+  char* rowp = reinterpret_cast<char*>(base) + (row * (32 * kSteps) + hq * 16);
+#pragma unroll
+  for (int ks = 0; ks < kSteps; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = regs[ks];
+}
+
+// kTap (parity tests only, gfy_debug_layer): the instantiation of a persistent kernel that also
+// writes one of the layer's phase tensors, rows in stored order — tap 1: z (after the gather),
+// 2: v (after BatchNorm + ReLU, 256 channels), 3: w (second product + bias), 4: y (LayerNorm,
+// before the residual; stored by the kernel, which knows how it normalises).  The production
+// instantiation (kTap = false) has none of this code.
+enum { kTapNone = 0, kTapZ = 1, kTapV = 2, kTapW = 3, kTapY = 4 };
+__device__ __forceinline__ void store_taps_zvw(int tap, f16* tap_out, bool active, int row, int hq,
+                                               const f16x8 (&z)[8], const f16x8 (&v)[16],
+                                               const f16x8 (&wrow)[8]) {
+  if (active && tap == kTapZ) store_row(tap_out, (size_t)row, hq, z);
+  if (active && tap == kTapV) store_row(tap_out, (size_t)row, hq, v);
+  if (active && tap == kTapW) store_row(tap_out, (size_t)row, hq, wrow);
+}
+
+// Where row r of a tile goes in the head's output: its shard's block and the row there (the
+// caller's out_rows compaction, else the shard-local row); dest = -1: no store — a wave without
+// a tile, padding behind the shard's last node (for which out_rows has no entry and is not
+// read), or a row out_rows itself leaves out
+struct HeadRowDest {
+  char* out;
+  int dest;
+};
+__device__ __forceinline__ HeadRowDest head_row_dest(const ShardTable& shards, int tile, int r,
+                                                     bool active) {
+  HeadRowDest d{nullptr, -1};
+  if (active) {
+    const int shard = shards.shard_of_tile(tile);
+    const int local = tile * kLTile + r - shards.tile_base[shard] * kLTile;
+    if (local < shards.nodes[shard]) {
+      const int32_t* rows = shards.out_rows[shard];
+      d.dest = rows ? rows[local] : local;
+      d.out = reinterpret_cast<char*>(shards.out[shard]);
+    }
+  }
+  return d;
+}
+
+// The cross-lane half of the head's tail (api.py:250-259): sum of squares of a row of o in float64 
+// (each square is exact in fp32: 22 significant bits, one v_fma_mix_f32 from the packed pair).  The order of the additions is part of the result,
+// and ALL 64 lanes execute the exchange of the two half-waves: call outside any per-lane guard.
+__device__ __forceinline__ double head_row_square_sum(const f16x8 (&o)[8]) {
+  double ss[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int ks = 0; ks < 8; ++ks) {
+    const u32x4 w4 = __builtin_bit_cast(u32x4, o[ks]);
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      ss[q] += (double)square_half<0>(w4[q]);
+      ss[q] += (double)square_half<1>(w4[q]);
+    }
+  }
+  return add_other_half((ss[0] + ss[1]) + (ss[2] + ss[3]));
+}
+
 // kHead: the launch also runs head + float64 normalise on the tile's new hidden state
 // (fp16 output), straight from the registers; h_out is then not written at all.
 template <bool kResidual, bool kHead>
@@ -1012,28 +1101,12 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_f16(
   }
   // the rest of the plan (slot words) and the per-launch constants ride behind both hops
   uint32_t word[8];
-  {
-    const u32x4 wa = reinterpret_cast<const u32x4*>(plan + kPlanWords + r * 32)[0];
-    const u32x4 wb = reinterpret_cast<const u32x4*>(plan + kPlanWords + r * 32)[1];
-    word[0] = wa[0], word[1] = wa[1], word[2] = wa[2], word[3] = wa[3];
-    word[4] = wb[0], word[5] = wb[1], word[6] = wb[2], word[7] = wb[3];
-  }
+  load_plan_words(plan, r, word);
   u32x4 image_chunk;
   if (t < 480) image_chunk = reinterpret_cast<const u32x4*>(p.image)[t];
   else image_chunk = reinterpret_cast<const u32x4*>(head.image)[t - 480];
-  int dest = -1;                 // kHead: output row of this lane's node, -1 = none
-  char* out = nullptr;           //        ... in its shard's output block
-  if constexpr (kHead) {
-    if (active) {
-      const int shard = shards.shard_of_tile(tile);
-      const int local = node - shards.tile_base[shard] * kLTile;
-      if (local < shards.nodes[shard]) {
-        const int32_t* rows = shards.out_rows[shard];
-        dest = rows ? rows[local] : local;
-        out = reinterpret_cast<char*>(shards.out[shard]);
-      }
-    }
-  }
+  HeadRowDest to{nullptr, -1};   // kHead: where the output row of this lane's node goes
+  if constexpr (kHead) to = head_row_dest(shards, tile, r, active);
   reinterpret_cast<u32x4*>(smem + kLdsImage)[t] = image_chunk;
   dma_wait_all();                                   // this wave's stage is complete
   STAMP_L(1);
@@ -1087,7 +1160,7 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_f16(
   f16x8 hn[8];
   layer_norm_residual<kResidual>(wrow, h, hn, smem + kLdsGamma, smem + kLdsBeta, hq);
   if constexpr (!kHead) {
-    if (node_ok) {
+    if (node_ok) {   // (not store_row: this site adds row and chunk to the base one after the other)
       char* rowp = reinterpret_cast<char*>(h_out) + (size_t)node * 256 + hq * 16;
 #pragma unroll
       for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = hn[ks];
@@ -1115,21 +1188,9 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_f16(
     STAMP_L(6);
     head_pipeline(smem, lds0, lane, hq, hn, o);
     STAMP_L(7);
-    // sum of squares in float64 (each square is exact in fp32: 22 significant bits, one
-    // v_fma_mix_f32 from the packed pair)
-    double ss[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const u32x4 w4 = __builtin_bit_cast(u32x4, o[ks]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        ss[q] += (double)square_half<0>(w4[q]);
-        ss[q] += (double)square_half<1>(w4[q]);
-      }
-    }
-    const double total = add_other_half((ss[0] + ss[1]) + (ss[2] + ss[3]));
-    if (dest >= 0) {
-      char* rowp = out + (size_t)dest * (kOutDim * 2) + hq * 16;
+    const double total = head_row_square_sum(o);
+    if (to.dest >= 0) {
+      char* rowp = to.out + (size_t)to.dest * (kOutDim * 2) + hq * 16;
       if (normalise) {
         const double nrm = __builtin_sqrt(total);
         const double inv = 1.0 / (nrm > 1e-12 ? nrm : 1e-12);

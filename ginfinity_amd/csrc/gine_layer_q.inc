@@ -1,7 +1,8 @@
 // Persistent form of the fused layer kernel of gine_layer.inc (included by gine_f16.hip):
 // one 512-thread workgroup per CU walks ROUNDS of eight tiles (one per wave), same phases, same
-// LDS overlay ([W0 | W1] over the eight spent gather stages), with what a round can hide of the
-// next one hidden:
+// LDS overlay ([W0 | W1] over the eight spent gather stages) and the shared pieces around the
+// pipelines (load_plan_words, store_row, store_taps_zvw, head_row_dest, head_row_square_sum),
+// with what a round can hide of the next one hidden:
 //
 //   round r:  stage(r) landed -> gather -> [W0 | W1] over the stages -> barrier -> products
 //             -> plan head of round r+1 requested -> barrier (every wave is done with the
@@ -80,11 +81,7 @@ __device__ __forceinline__ PlanHeadQ plan_head_read(const char* slot, int lane) 
   return q;
 }
 
-// kTap (parity tests only, gfy_debug_layer): the instantiation that also writes one of the
-// layer's phase tensors, rows in stored order — tap 1: z (after the gather), 2: v (after
-// BatchNorm + ReLU, 256 channels), 3: w (second product + bias), 4: y (LayerNorm, before the
-// residual).  The production instantiation (kTap = false) has none of this code.
-enum { kTapNone = 0, kTapZ = 1, kTapV = 2, kTapW = 3, kTapY = 4 };
+// kTap: see store_taps_zvw (gine_layer.inc).
 // kHead: the launch also runs head + float64 normalise on every tile's new hidden state (fp16
 // output), straight from the registers: h_out is not written at all, the head's 64-KB image
 // replaces W0 under the second product (as in k_gine_layer_f16), and the NORMALISE of round r
@@ -163,10 +160,7 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_q(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     count = head.count, deepest = head.deepest;
     stage_dma(h_in, tile, n, lds_stage, lane, count, head.far4);
-    const u32x4 wa = reinterpret_cast<const u32x4*>(plan + kPlanWords + (lane & 31) * 32)[0];
-    const u32x4 wb = reinterpret_cast<const u32x4*>(plan + kPlanWords + (lane & 31) * 32)[1];
-    word[0] = wa[0], word[1] = wa[1], word[2] = wa[2], word[3] = wa[3];
-    word[4] = wb[0], word[5] = wb[1], word[6] = wb[2], word[7] = wb[3];
+    load_plan_words(plan, lane & 31, word);
   }
   dma_wait_all();
   lds_barrier();                                    // constants visible
@@ -225,21 +219,7 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_q(
       const int lane_t = opaque(lane), row_t = tile * kLTile + (lane_t & 31), hq_t = lane_t >> 5;
       f16x8 v[16];
       mlp_pipeline<false>(smem, lds0, wave, lane_t, hq_t, z, v, wrow, no_head);
-      if (active && tap == kTapZ) {
-        char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 256 + hq_t * 16);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = z[ks];
-      }
-      if (active && tap == kTapV) {
-        char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 512 + hq_t * 16);
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = v[ks];
-      }
-      if (active && tap == kTapW) {
-        char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 256 + hq_t * 16);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = wrow[ks];
-      }
+      store_taps_zvw(tap, tap_out, active, row_t, hq_t, z, v, wrow);
     } else {
       const int lane_c = opaque(lane);
       mlp_pipeline<kHead>(smem, lds0, wave, lane_c, lane_c >> 5, z, wrow,
@@ -255,10 +235,7 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_q(
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         count = next.count, deepest = next.deepest;
         stage_dma(h_in, tile_of(next_first), n, lds_stage, lane_b, count, next.far4);
-        const u32x4 wa = reinterpret_cast<const u32x4*>(next_plan + kPlanWords + (lane_b & 31) * 32)[0];
-        const u32x4 wb = reinterpret_cast<const u32x4*>(next_plan + kPlanWords + (lane_b & 31) * 32)[1];
-        word[0] = wa[0], word[1] = wa[1], word[2] = wa[2], word[3] = wa[3];
-        word[4] = wb[0], word[5] = wb[1], word[6] = wb[2], word[7] = wb[3];
+        load_plan_words(next_plan, lane_b & 31, word);
       } else {   // nothing of this round is carried into a round that does not gather
 #pragma unroll
         for (int i = 0; i < 8; ++i) word[i] = 0;
@@ -278,18 +255,11 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_q(
         if (active && tap == kTapY) {
           f16x8 y[8];
           layer_norm_residual<false>(wrow, h, y, smem + kLdsGamma, smem + kLdsBeta, lane_d >> 5);
-          char* rowp = reinterpret_cast<char*>(tap_out) +
-                       ((size_t)(tile * kLTile + (lane_d & 31)) * 256 + (lane_d >> 5) * 16);
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = y[ks];
+          store_row(tap_out, (size_t)(tile * kLTile + (lane_d & 31)), lane_d >> 5, y);
         }
       }
-      if (active) {   // every row of an active tile has storage (padded hidden-state buffers)
-        char* rowp = reinterpret_cast<char*>(h_out) +
-                     ((size_t)(tile * kLTile + (lane_d & 31)) * 256 + (lane_d >> 5) * 16);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = hn[ks];
-      }
+      // every row of an active tile has storage (padded hidden-state buffers)
+      if (active) store_row(h_out, (size_t)(tile * kLTile + (lane_d & 31)), lane_d >> 5, hn);
       STAMP_Q(6);
       // the next stage (and its slot words) have landed; this round's stores may still fly
       if (active && !kTap) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -301,18 +271,7 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_q(
       const int lane_d = opaque(lane), r_d = lane_d & 31, hq_d = lane_d >> 5;
       layer_norm_residual<kResidual>(wrow, h, hn, smem + kLdsGamma, smem + kLdsBeta, hq_d);
       STAMP_Q(6);
-      int dest = -1;
-      char* out = nullptr;
-      if (active) {
-        const ShardTable& shards = head_out.shards;
-        const int shard = shards.shard_of_tile(tile);
-        const int local = tile * kLTile + r_d - shards.tile_base[shard] * kLTile;
-        if (local < shards.nodes[shard]) {
-          const int32_t* rows = shards.out_rows[shard];
-          dest = rows ? rows[local] : local;
-          out = reinterpret_cast<char*>(shards.out[shard]);
-        }
-      }
+      const HeadRowDest to = head_row_dest(head_out.shards, tile, r_d, active);
       dma_wait_all();
       lds_barrier();                                  // head.0 | head.2 resident over W0
       f16x8 o[8];
@@ -321,20 +280,10 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_q(
       STAMP_Q(4);
       start_next_round();
       STAMP_Q(5);
-      double ss[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const u32x4 w4 = __builtin_bit_cast(u32x4, o[ks]);
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          ss[qq] += (double)square_half<0>(w4[qq]);
-          ss[qq] += (double)square_half<1>(w4[qq]);
-        }
-      }
-      const double total = add_other_half((ss[0] + ss[1]) + (ss[2] + ss[3]));
-      const bool stores = __ballot(dest >= 0) != 0;   // wave-uniform: eight store instructions
-      if (dest >= 0) {
-        char* rowp = out + (size_t)dest * (kOutDim * 2) + hq_d * 16;
+      const double total = head_row_square_sum(o);
+      const bool stores = __ballot(to.dest >= 0) != 0;   // wave-uniform: eight store instructions
+      if (to.dest >= 0) {
+        char* rowp = to.out + (size_t)to.dest * (kOutDim * 2) + hq_d * 16;
         if (head_out.normalise) {   // see the head pass of k_gine_layer_f16
           const double nrm = __builtin_sqrt(total);
           const double inv = 1.0 / (nrm > 1e-12 ? nrm : 1e-12);
@@ -347,11 +296,11 @@ __global__ __launch_bounds__(kLThreads) void k_gine_layer_q(
             u32x4 up;
             uint32_t differ = 0;
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-              up[qq] = cvt_pk_f16(fma_half<0>(w4[qq], inv_up, sign_keeping_zero),
-                                  fma_half<1>(w4[qq], inv_up, sign_keeping_zero));
-              differ |= up[qq] ^ cvt_pk_f16(fma_half<0>(w4[qq], inv_dn, sign_keeping_zero),
-                                            fma_half<1>(w4[qq], inv_dn, sign_keeping_zero));
+            for (int q = 0; q < 4; ++q) {
+              up[q] = cvt_pk_f16(fma_half<0>(w4[q], inv_up, sign_keeping_zero),
+                                 fma_half<1>(w4[q], inv_up, sign_keeping_zero));
+              differ |= up[q] ^ cvt_pk_f16(fma_half<0>(w4[q], inv_dn, sign_keeping_zero),
+                                           fma_half<1>(w4[q], inv_dn, sign_keeping_zero));
             }
             f16x8 scaled = __builtin_bit_cast(f16x8, up);
             if (differ) {
@@ -421,6 +370,8 @@ __global__ __launch_bounds__(kLThreads) void k_head_d(
   while (exists(local)) {
     const int tile = xbase + local;
     const int lane_a = opaque(lane), r = lane_a & 31, hq = lane_a >> 5;
+    // (not head_row_dest: this kernel has no wave without a tile and fetches the shard's output
+    // block before it knows whether the row is stored)
     const int node = tile * kLTile + r;
     const int shard = shards.shard_of_tile(tile);
     const int row = node - shards.tile_base[shard] * kLTile;          // shard-local
@@ -433,22 +384,10 @@ __global__ __launch_bounds__(kLThreads) void k_head_d(
     for (int ks = 0; ks < 8; ++ks) hn[ks] = ahead[ks];
     if (exists(local + stride)) load_rows(local + stride, ahead);
     head_pipeline(smem, lds0, lane_a, hq, hn, o);
-    double ss[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const u32x4 w4 = __builtin_bit_cast(u32x4, o[ks]);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        ss[q] += (double)square_half<0>(w4[q]);
-        ss[q] += (double)square_half<1>(w4[q]);
-      }
-    }
-    const double total = add_other_half((ss[0] + ss[1]) + (ss[2] + ss[3]));
+    const double total = head_row_square_sum(o);
     if (node_ok && dest >= 0) {
       char* rowp = reinterpret_cast<char*>(out) + (size_t)dest * (kOutDim * 2) + hq * 16;
-      if (normalise) {
-        // see the head pass of k_gine_layer_f16: fp16(o * inv) rounded ONCE from the float64
-        // product, found by bracketing it with two fp32 products
+      if (normalise) {   // see the head pass of k_gine_layer_f16
         const double nrm = __builtin_sqrt(total);
         const double inv = 1.0 / (nrm > 1e-12 ? nrm : 1e-12);
         const float invf = (float)inv, sign_keeping_zero = -0.0f;

@@ -1,6 +1,8 @@
 // The fused layer as TWO 4-wave workgroups per CU with the weights STREAMED through a window
-// (included by gine_f16.hip behind gine_layer_q.inc; same tile plans, gather, pipelines,
-// LayerNorm and head code: results are bit-identical to k_gine_layer_f16 / k_gine_layer_q).
+// (included by gine_f16.hip behind gine_layer_q.inc; same tile plans, gather_tile / gather_direct,
+// pipelines, layer_norm_*, and around them load_plan_words, store_row, store_taps_zvw,
+// head_row_dest, head_row_square_sum and raise_wave_priority of gine_layer.inc: results are
+// bit-identical to k_gine_layer_f16 / k_gine_layer_q).
 //
 // Why.  In k_gine_layer_q the eight waves of a CU are one workgroup and walk the phases of a
 // round together, because [W0 | W1] (128 KB) overlay the eight gather stages (144 KB): what
@@ -227,6 +229,7 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
   const int per_xcd = (int)(gridDim.x >> 3), half = (per_xcd + 1) >> 1;
   const int slot_in_xcd = (int)(blockIdx.x >> 3);
   const bool second = slot_in_xcd >= half;
+  // (not raise_wave_priority: every form of it that folds `second` in reschedules the kernel)
   if (second && ((priority >> 4) & 3) == 1) __builtin_amdgcn_s_setprio(1);
   else if (second && ((priority >> 4) & 3) == 2) __builtin_amdgcn_s_setprio(2);
   else if (second && ((priority >> 4) & 3) == 3) __builtin_amdgcn_s_setprio(3);
@@ -292,10 +295,7 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     count = head.count, deepest = head.deepest;
     stage_dma(h_in, tile, n, lds_stage, lane, count, head.far4);
-    const u32x4 wa = reinterpret_cast<const u32x4*>(plan + kPlanWords + (lane & 31) * 32)[0];
-    const u32x4 wb = reinterpret_cast<const u32x4*>(plan + kPlanWords + (lane & 31) * 32)[1];
-    word[0] = wa[0], word[1] = wa[1], word[2] = wa[2], word[3] = wa[3];
-    word[4] = wb[0], word[5] = wb[1], word[6] = wb[2], word[7] = wb[3];
+    load_plan_words(plan, lane & 31, word);
   }
   dma_wait_all();
   STAMP_W(0);
@@ -374,10 +374,7 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
           count = next.count, deepest = next.deepest;
           stage_dma(h_in, tile_of(next_first), n, lds_stage, lane_b, count, next.far4);
         }
-        const u32x4 wa = reinterpret_cast<const u32x4*>(next_plan + kPlanWords + (lane_b & 31) * 32)[0];
-        const u32x4 wb = reinterpret_cast<const u32x4*>(next_plan + kPlanWords + (lane_b & 31) * 32)[1];
-        word[0] = wa[0], word[1] = wa[1], word[2] = wa[2], word[3] = wa[3];
-        word[4] = wb[0], word[5] = wb[1], word[6] = wb[2], word[7] = wb[3];
+        load_plan_words(next_plan, lane_b & 31, word);
       } else {   // nothing of this round is carried into a round that does not gather
 #pragma unroll
         for (int i = 0; i < 8; ++i) word[i] = 0;
@@ -397,29 +394,13 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
     // 5:4 the second one's level everywhere else
     const int raise = second ? (priority >> 2) & 3 : priority & 3;
     const int rest = second ? (priority >> 4) & 3 : 0;
-    if (raise == 1) __builtin_amdgcn_s_setprio(1);
-    else if (raise == 2) __builtin_amdgcn_s_setprio(2);
-    else if (raise == 3) __builtin_amdgcn_s_setprio(3);
+    raise_wave_priority(raise);
     f16x8 wrow[8];
     if constexpr (kTap) {
       const int lane_t = opaque(lane), row_t = tile * kLTile + (lane_t & 31), hq_t = lane_t >> 5;
       f16x8 v[16];
       mlp_pipeline_on<WindowLayout>(smem, lds0, lane_t, hq_t, z, v, wrow, hooks);
-      if (active && tap == kTapZ) {
-        char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 256 + hq_t * 16);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = z[ks];
-      }
-      if (active && tap == kTapV) {
-        char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 512 + hq_t * 16);
-#pragma unroll
-        for (int ks = 0; ks < 16; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = v[ks];
-      }
-      if (active && tap == kTapW) {
-        char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 256 + hq_t * 16);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = wrow[ks];
-      }
+      store_taps_zvw(tap, tap_out, active, row_t, hq_t, z, v, wrow);
     } else {
       const int lane_c = opaque(lane);
       f16x8 v[16];
@@ -427,9 +408,7 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
     }
     if (raise != rest) {
       if (rest == 0) __builtin_amdgcn_s_setprio(0);
-      else if (rest == 1) __builtin_amdgcn_s_setprio(1);
-      else if (rest == 2) __builtin_amdgcn_s_setprio(2);
-      else __builtin_amdgcn_s_setprio(3);
+      else raise_wave_priority(rest);
     }
     STAMP_W(3);
     f16x8 hn[8];
@@ -444,18 +423,11 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
           f16x8 y[8];
           layer_norm_residual<false>(wrow, h, y, smem + kWLdsImage + (kLdsGamma - kLdsImage),
                                      smem + kWLdsImage + (kLdsBeta - kLdsImage), lane_d >> 5);
-          char* rowp = reinterpret_cast<char*>(tap_out) +
-                       ((size_t)(tile * kLTile + (lane_d & 31)) * 256 + (lane_d >> 5) * 16);
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = y[ks];
+          store_row(tap_out, (size_t)(tile * kLTile + (lane_d & 31)), lane_d >> 5, y);
         }
       }
-      if (active) {   // every row of an active tile has storage (padded hidden-state buffers)
-        char* rowp = reinterpret_cast<char*>(h_out) +
-                     ((size_t)(tile * kLTile + (lane_d & 31)) * 256 + (lane_d >> 5) * 16);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = hn[ks];
-      }
+      // every row of an active tile has storage (padded hidden-state buffers)
+      if (active) store_row(h_out, (size_t)(tile * kLTile + (lane_d & 31)), lane_d >> 5, hn);
       STAMP_W(6);
       // the next stage (and its slot words) have landed; this round's stores may still fly
       if (active && !kTap) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -468,18 +440,7 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
       layer_norm_residual<kResidual>(wrow, h, hn, smem + kWLdsImage + (kLdsGamma - kLdsImage),
                                      smem + kWLdsImage + (kLdsBeta - kLdsImage), hq_d);
       STAMP_W(6);
-      int dest = -1;
-      char* out = nullptr;
-      if (active) {
-        const ShardTable& shards = head_out.shards;
-        const int shard = shards.shard_of_tile(tile);
-        const int local = tile * kLTile + r_d - shards.tile_base[shard] * kLTile;
-        if (local < shards.nodes[shard]) {
-          const int32_t* rows = shards.out_rows[shard];
-          dest = rows ? rows[local] : local;
-          out = reinterpret_cast<char*>(shards.out[shard]);
-        }
-      }
+      const HeadRowDest to = head_row_dest(head_out.shards, tile, r_d, active);
       dma_wait_all();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       window_barrier();                               // head.0 | head.2 resident in the window
@@ -497,20 +458,10 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
       STAMP_W(4);
       start_next_round();
       STAMP_W(5);
-      double ss[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const u32x4 w4 = __builtin_bit_cast(u32x4, o[ks]);
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          ss[qq] += (double)square_half<0>(w4[qq]);
-          ss[qq] += (double)square_half<1>(w4[qq]);
-        }
-      }
-      const double total = add_other_half((ss[0] + ss[1]) + (ss[2] + ss[3]));
-      const bool stores = __ballot(dest >= 0) != 0;   // wave-uniform: eight store instructions
-      if (dest >= 0) {
-        char* rowp = out + (size_t)dest * (kOutDim * 2) + hq_d * 16;
+      const double total = head_row_square_sum(o);
+      const bool stores = __ballot(to.dest >= 0) != 0;   // wave-uniform: eight store instructions
+      if (to.dest >= 0) {
+        char* rowp = to.out + (size_t)to.dest * (kOutDim * 2) + hq_d * 16;
         if (head_out.normalise) {   // see the head pass of k_gine_layer_f16
           const double nrm = __builtin_sqrt(total);
           const double inv = 1.0 / (nrm > 1e-12 ? nrm : 1e-12);
@@ -523,11 +474,11 @@ __global__ __launch_bounds__(kWThreads, 2) void k_gine_layer_w(
             u32x4 up;
             uint32_t differ = 0;
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-              up[qq] = cvt_pk_f16(fma_half<0>(w4[qq], inv_up, sign_keeping_zero),
-                                  fma_half<1>(w4[qq], inv_up, sign_keeping_zero));
-              differ |= up[qq] ^ cvt_pk_f16(fma_half<0>(w4[qq], inv_dn, sign_keeping_zero),
-                                            fma_half<1>(w4[qq], inv_dn, sign_keeping_zero));
+            for (int q = 0; q < 4; ++q) {
+              up[q] = cvt_pk_f16(fma_half<0>(w4[q], inv_up, sign_keeping_zero),
+                                 fma_half<1>(w4[q], inv_up, sign_keeping_zero));
+              differ |= up[q] ^ cvt_pk_f16(fma_half<0>(w4[q], inv_dn, sign_keeping_zero),
+                                           fma_half<1>(w4[q], inv_dn, sign_keeping_zero));
             }
             f16x8 scaled = __builtin_bit_cast(f16x8, up);
             if (differ) {

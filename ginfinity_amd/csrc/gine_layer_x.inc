@@ -1,7 +1,9 @@
 // The fused layer with THREE waves per SIMD: three 4-wave workgroups per CU, <= 168 registers
 // and 48 KB of LDS each (included by gine_f16.hip behind gine_block_pipe.inc; same tile plans,
 // gather arithmetic, epilogue slices, LayerNorm and head arithmetic in the same order as
-// k_gine_layer_f16 / _q / _w: results are bit-identical).
+// k_gine_layer_f16 / _q / _w — layer_norm_moments / _affine, store_row, store_taps_zvw,
+// head_row_dest, head_row_square_sum and raise_wave_priority are gine_layer.inc's own: results
+// are bit-identical).
 //
 // Why.  Round 4's counters for k_gine_layer_w: matrix pipe busy 44.6 % of a launch, vector work
 // 41.8 % at a lone wave's issue pace, and the two ADD UP — two in-order 250-register waves per
@@ -433,9 +435,7 @@ __global__ __launch_bounds__(kXThreads, 3) void k_gine_layer_x(
     };
     const XWindowHooks<kHead, decltype(fetch_residual), decltype(start_next_round)> hooks{
         p, head_out.head, lds_stage, wave, opaque(lane), fetch_residual, start_next_round};
-    if (raise == 1) __builtin_amdgcn_s_setprio(1);
-    else if (raise == 2) __builtin_amdgcn_s_setprio(2);
-    else if (raise == 3) __builtin_amdgcn_s_setprio(3);
+    raise_wave_priority(raise);
     f16x8 wrow[8];
     {
       const int lane_p = opaque(lane);
@@ -443,21 +443,7 @@ __global__ __launch_bounds__(kXThreads, 3) void k_gine_layer_x(
       block_mlp_pipeline<XWindowLayout>(lds0, lane_p, lane_p >> 5, z, v, wrow, hooks);
       if constexpr (kTap) {
         const int row_t = tile * kLTile + (lane_p & 31), hq_t = lane_p >> 5;
-        if (active && tap == kTapZ) {
-          char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 256 + hq_t * 16);
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = z[ks];
-        }
-        if (active && tap == kTapV) {
-          char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 512 + hq_t * 16);
-#pragma unroll
-          for (int ks = 0; ks < 16; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = v[ks];
-        }
-        if (active && tap == kTapW) {
-          char* rowp = reinterpret_cast<char*>(tap_out) + ((size_t)row_t * 256 + hq_t * 16);
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = wrow[ks];
-        }
+        store_taps_zvw(tap, tap_out, active, row_t, hq_t, z, v, wrow);
       }
     }
     if (raise != 0) __builtin_amdgcn_s_setprio(0);
@@ -501,21 +487,14 @@ __global__ __launch_bounds__(kXThreads, 3) void k_gine_layer_x(
         if (active && tap == kTapY) {
           f16x8 y[8];
           layer_norm_affine<false>(wrow, moments, h, y, gamma, beta, hq_d);
-          char* rowp = reinterpret_cast<char*>(tap_out) +
-                       ((size_t)(tile * kLTile + r_d) * 256 + hq_d * 16);
-#pragma unroll
-          for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = y[ks];
+          store_row(tap_out, (size_t)(tile * kLTile + r_d), hq_d, y);
         }
       }
     }
     if constexpr (!kHead) {
       const int lane_e = opaque(lane);
-      if (active) {   // every row of an active tile has storage (padded hidden-state buffers)
-        char* rowp = reinterpret_cast<char*>(h_out) +
-                     ((size_t)(tile * kLTile + (lane_e & 31)) * 256 + (lane_e >> 5) * 16);
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) *reinterpret_cast<f16x8*>(rowp + 32 * ks) = hn[ks];
-      }
+      // every row of an active tile has storage (padded hidden-state buffers)
+      if (active) store_row(h_out, (size_t)(tile * kLTile + (lane_e & 31)), lane_e >> 5, hn);
       STAMP_X(6);
       // the next stage half (and its slot words) have landed; this round's stores may still fly
       if (active && !kTap) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
@@ -525,18 +504,7 @@ __global__ __launch_bounds__(kXThreads, 3) void k_gine_layer_x(
       // ---- the head from the registers (its chunks 0 | 1 have been landing since the last
       //      steps of the products); the next round's rows stream in under the normalise -------
       const int lane_e = opaque(lane), r_e = lane_e & 31, hq_e = lane_e >> 5;
-      int dest = -1;
-      char* out = nullptr;
-      if (active) {
-        const ShardTable& shards = head_out.shards;
-        const int shard = shards.shard_of_tile(tile);
-        const int local = tile * kLTile + r_e - shards.tile_base[shard] * kLTile;
-        if (local < shards.nodes[shard]) {
-          const int32_t* rows = shards.out_rows[shard];
-          dest = rows ? rows[local] : local;
-          out = reinterpret_cast<char*>(shards.out[shard]);
-        }
-      }
+      const HeadRowDest to = head_row_dest(head_out.shards, tile, r_e, active);
       STAMP_X(6);
       dma_wait_all();
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -544,20 +512,10 @@ __global__ __launch_bounds__(kXThreads, 3) void k_gine_layer_x(
       f16x8 o[8];
       block_head_pipeline<XWindowLayout>(lds0, lane_e, hq_e, hn, o, hooks);
       STAMP_X(8);
-      double ss[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int ks = 0; ks < 8; ++ks) {
-        const u32x4 w4 = __builtin_bit_cast(u32x4, o[ks]);
-#pragma unroll
-        for (int qq = 0; qq < 4; ++qq) {
-          ss[qq] += (double)square_half<0>(w4[qq]);
-          ss[qq] += (double)square_half<1>(w4[qq]);
-        }
-      }
-      const double total = add_other_half((ss[0] + ss[1]) + (ss[2] + ss[3]));
-      const bool stores = __ballot(dest >= 0) != 0;   // wave-uniform: eight store instructions
-      if (dest >= 0) {
-        char* rowp = out + (size_t)dest * (kOutDim * 2) + hq_e * 16;
+      const double total = head_row_square_sum(o);
+      const bool stores = __ballot(to.dest >= 0) != 0;   // wave-uniform: eight store instructions
+      if (to.dest >= 0) {
+        char* rowp = to.out + (size_t)to.dest * (kOutDim * 2) + hq_e * 16;
         if (head_out.normalise) {   // see the head pass of k_gine_layer_f16
           const double nrm = __builtin_sqrt(total);
           const double inv = 1.0 / (nrm > 1e-12 ? nrm : 1e-12);
@@ -570,11 +528,11 @@ __global__ __launch_bounds__(kXThreads, 3) void k_gine_layer_x(
             u32x4 up;
             uint32_t differ = 0;
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-              up[qq] = cvt_pk_f16(fma_half<0>(w4[qq], inv_up, sign_keeping_zero),
-                                  fma_half<1>(w4[qq], inv_up, sign_keeping_zero));
-              differ |= up[qq] ^ cvt_pk_f16(fma_half<0>(w4[qq], inv_dn, sign_keeping_zero),
-                                            fma_half<1>(w4[qq], inv_dn, sign_keeping_zero));
+            for (int q = 0; q < 4; ++q) {
+              up[q] = cvt_pk_f16(fma_half<0>(w4[q], inv_up, sign_keeping_zero),
+                                 fma_half<1>(w4[q], inv_up, sign_keeping_zero));
+              differ |= up[q] ^ cvt_pk_f16(fma_half<0>(w4[q], inv_dn, sign_keeping_zero),
+                                           fma_half<1>(w4[q], inv_dn, sign_keeping_zero));
             }
             f16x8 scaled = __builtin_bit_cast(f16x8, up);
             if (differ) {
