@@ -53,6 +53,9 @@ _ALIGN_CALL = [c_void_p, c_int64] * 5 + [c_float] * 4
 _HIT_RUNS_CALL = [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p,
                   c_int64, c_int64]
 
+#: what the two chain calls start with: pairs, cells, lengths, weights, runs
+_CHAIN_RUNS_CALL = [c_void_p, c_void_p, c_void_p, c_void_p, c_int64]
+
 #: every symbol include/gfy.h declares: (restype, argtypes)
 SIGNATURES: dict[str, tuple] = {
     "gfy_last_error": (c_char_p, []),
@@ -176,6 +179,12 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_hit_runs_emit": (c_int, [*_HIT_RUNS_CALL, c_void_p, c_void_p, c_int, c_int64, c_void_p,
                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),
+    "gfy_chain_runs_workspace_bytes": (c_size_t, [c_int64]),
+    "gfy_chain_runs_link": (c_int, [*_CHAIN_RUNS_CALL, c_void_p, c_void_p, c_int64, c_int64,
+                                    c_int64, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
+    "gfy_chain_runs_emit": (c_int, [*_CHAIN_RUNS_CALL, c_void_p, c_void_p, c_int64,
+                                    *[c_void_p] * 8, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 

@@ -159,9 +159,71 @@ Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIM
 and ``within`` modes (borders that leave the band, pairs with no admissible path at all),
 band-only storage of the direction words, a span-only kernel for the global and ``within`` modes,
 free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
-scores.  Out of scope for ``hit_runs``: gapped chaining of runs across neighbouring diagonals, a
-cross-shard form in ``parallel.py``, runs from ``topk`` results (a ``[n, k]`` block is not sorted
-by b-row), and a ``device="cpu"`` path.  Measured cost: DESIGN.md §4.
+scores.  Out of scope for ``hit_runs``: a cross-shard form in ``parallel.py``, runs from ``topk``
+results (a ``[n, k]`` block is not sorted by b-row), and a ``device="cpu"`` path.  Measured cost:
+DESIGN.md §4.
+
+Chains of runs (``chain_runs``).  A run is a gapless stretch on one diagonal, so two records that
+share a region with one inserted or deleted row give two runs on two diagonals.  ``chain_runs``
+links such pieces and returns, per chain, the band of diagonals that holds all of it:
+
+    chains = align.chain_runs(runs, max_gap=8)              # max_shift defaults to max_gap
+    best = chains.best(64)                                  # most hits, then heaviest
+    paths = align.local_paths(rows, counts_a=counts, pairs=chains.pairs[best],
+                              band=chains.bands(4)[best], gap_open=1.0, gap_extend=0.25)
+
+It is a fixed function of the ``Runs`` and two integers, bit for bit, and needs no counts.
+
+Inputs.  ``runs = Runs(pairs int32 [S, 2], cells int32 [S, 2], lengths int32 [S], weights float32
+[S])``, in the order ``hit_runs`` emits them: the key ``(q, cell_i, r, cell_j)`` is strictly
+ascending lexicographically from run to run (this follows from "i ascending, then j ascending"
+over contiguous records).  A boolean-mask subset of a ``Runs`` keeps this order; a ``best()``
+permutation does not.
+
+Terms.  Run s has pair ``(q_s, r_s)``, head ``(i_s, j_s)``, length ``L_s >= 1`` and diagonal ``d_s
+= j_s - i_s``.  Its tail is the cell ``(i_s + L_s - 1, j_s + L_s - 1)``.
+
+Linking rule.  s may precede t (``s -> t``) if and only if all of these hold: the pairs are equal;
+``gi = i_t - (i_s + L_s) >= 0``; ``gj = j_t - (j_s + L_s) >= 0``; ``max(gi, gj) <= max_gap``;
+``|d_t - d_s| = |gj - gi| <= max_shift``.  ``max_shift=None`` means ``max_gap``.  There is no
+overlap in either coordinate, and ``s -> t`` implies ``s < t`` in Runs order.
+
+Forward pass.  ``C[t] = L_t + max(0, max over s -> t of C[s])``, computed in int64.  ``pred[t]`` is
+the s that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then to the largest s;
+``pred[t] = -1`` when no s precedes t.
+
+Backward pass.  The mirror image: ``D[s] = L_s + max(0, max over s -> t of D[t])``.  ``succ[s]`` is
+the t that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then to the smallest t.
+
+Links and chains.  A link ``s - t`` is kept if and only if ``pred[t] == s`` and ``succ[s] == t``:
+both ends must choose each other.  Every run therefore has at most one kept predecessor and at
+most one kept successor.  The chains are the maximal paths; every run belongs to exactly one
+chain, and a chain lies in one record pair.  The rule was chosen because it is symmetric (the
+runs read backwards give the same chains) and needs no serial "take the best chain, remove its
+runs, repeat" step: two passes and a comparison decide every link.  What it guarantees: where a
+record pair's maximum-hit chain is unique, including all its prefixes and suffixes, that chain is
+one of the chains returned.
+
+Output.  ``Chains`` is a NamedTuple of device tensors; chains come in the order of their first
+runs.  ``pairs`` int32 ``[K, 2]``; ``starts`` int32 ``[K, 2]``, the head of the first run; ``ends``
+int32 ``[K, 2]``, the tail of the last run; ``diagonals`` int32 ``[K, 2]``, ``(min d, max d)`` over
+the chain's runs; ``counts`` int32 ``[K]``, the number of runs; ``lengths`` int32 ``[K]``, the sum
+of ``L``, which is the number of hits; ``weights`` float32 ``[K]``, the runs' float32 weights
+added in float64 in chain order, each addition one rounded operation, rounded to float32 once;
+``members`` int32 ``[S]``, the chain of every run: a chain's runs are ``flatnonzero(members ==
+c)``, ascending.  ``Chains.bands(half_width)`` gives ``(diagonals[:, 0] - half_width,
+diagonals[:, 1] + half_width)`` as an int32 host array, which is what ``local_align`` /
+``local_spans`` / ``local_paths`` take with ``pairs=chains.pairs``; ``Chains.best(k)`` is the rule
+of ``Runs.best``: lengths descending, then weights descending with NaN last, then position.
+
+Consequences.  ``max_gap=0`` links nothing, because two such runs would have been one maximal
+run: then ``K == S``, ``starts == cells``, ``lengths`` are equal, ``weights`` are the same bytes
+and ``members == arange(S)``.  ``counts.sum() == S`` and ``lengths.sum() == runs.lengths.sum()``,
+whatever the two integers.
+
+Out of scope for ``chain_runs``: overlapping runs (two runs that share a row or a column never
+link), a gap or shift penalty in the chain score (``C`` counts hits alone), chains across record
+pairs or shards, and a ``device="cpu"`` path.
 """
 from __future__ import annotations
 
@@ -326,15 +388,21 @@ class Runs(NamedTuple):
         order ``lengths`` descending, then ``weights`` descending, then position ascending; a NaN
         weight ranks behind every number of its length.  A pure function of ``lengths`` and
         ``weights``, which come to the host for it."""
-        if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
-            raise ValueError("k must be a positive integer")
-        lengths, weights = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor)
-                            else np.asarray(x) for x in (self.lengths, self.weights))
-        missing = np.isnan(weights)
-        # by (length, NaN or not, weight, position): lexsort is stable and takes its last key first
-        order = np.lexsort((np.where(missing, 0, -weights.astype(np.float64)), missing,
-                            -lengths.astype(np.int64)))
-        return order[:int(k)].astype(np.int64)
+        return _best(self.lengths, self.weights, k)
+
+
+def _best(lengths, weights, k) -> np.ndarray:
+    """The rule of ``Runs.best`` and ``Chains.best``: the first ``k`` positions in the order
+    ``lengths`` descending, then ``weights`` descending with NaN last, then position."""
+    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
+        raise ValueError("k must be a positive integer")
+    lengths, weights = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor)
+                        else np.asarray(x) for x in (lengths, weights))
+    missing = np.isnan(weights)
+    # by (length, NaN or not, weight, position): lexsort is stable and takes its last key first
+    order = np.lexsort((np.where(missing, 0, -weights.astype(np.float64)), missing,
+                        -lengths.astype(np.int64)))
+    return order[:int(k)].astype(np.int64)
 
 
 class RunsWorkspace:
@@ -488,6 +556,235 @@ def hit_runs(hits, *, counts_a, counts_b=None, min_length: int = 1,
             raise native.NativeLibraryError(
                 "gfy_hit_runs: the hits contradicted the sizes of the call")
         return runs
+
+
+class Chains(NamedTuple):
+    """What ``chain_runs`` returns, all on the device: chain c lies in the record pair
+    ``pairs[c]``, reaches from the cell ``starts[c]`` (the head of its first run) to the cell
+    ``ends[c]`` (the tail of its last run) on the diagonals ``diagonals[c, 0] .. diagonals[c, 1]``,
+    and is ``counts[c]`` runs of ``lengths[c]`` hits in all; ``weights[c]`` is the sum of their
+    weights.  ``members[s]`` is the chain of run s: a chain's runs are
+    ``flatnonzero(members == c)``, ascending."""
+    pairs: torch.Tensor       # int32 [K, 2] of (record of a, record of b)
+    starts: torch.Tensor      # int32 [K, 2]
+    ends: torch.Tensor        # int32 [K, 2]
+    diagonals: torch.Tensor   # int32 [K, 2] of (min d, max d)
+    counts: torch.Tensor      # int32 [K]
+    lengths: torch.Tensor     # int32 [K]
+    weights: torch.Tensor     # float32 [K]
+    members: torch.Tensor     # int32 [S]
+
+    def bands(self, half_width: int) -> np.ndarray:
+        """``(diagonals[:, 0] - half_width, diagonals[:, 1] + half_width)`` as an int32 ``[K, 2]``
+        host array: the band that holds every run of a chain, for ``local_align`` /
+        ``local_spans`` / ``local_paths`` with ``pairs=self.pairs``.  ``half_width`` is a
+        non-negative integer, 0 the chain's own diagonals alone; like ``band_around`` it is cut
+        at twice ``GFY_ALIGN_ROWS_MAX``, wider than any matrix."""
+        if isinstance(half_width, (bool, np.bool_)) or \
+                not isinstance(half_width, (int, np.integer)) or half_width < 0:
+            raise ValueError("half_width must be a non-negative integer")
+        diagonals = self.diagonals.detach().cpu().numpy() \
+            if isinstance(self.diagonals, torch.Tensor) else np.asarray(self.diagonals)
+        diagonals = diagonals.astype(np.int64).reshape(-1, 2)
+        width = min(int(half_width), 2 * native.GFY_ALIGN_ROWS_MAX)
+        limit = np.iinfo(np.int32)
+        return np.clip(np.stack([diagonals[:, 0] - width, diagonals[:, 1] + width], axis=1),
+                       limit.min, limit.max).astype(np.int32)
+
+    def best(self, k: int) -> np.ndarray:
+        """The indices (int64 host array, at most ``k``) of the ``k`` chains that come first by
+        the rule of ``Runs.best``: ``lengths`` (hits) descending, then ``weights`` descending with
+        NaN last, then position ascending."""
+        return _best(self.lengths, self.weights, k)
+
+
+class ChainsWorkspace:
+    """Scratch memory, marks and slots of ``chain_runs`` kept across calls (the chains are always
+    new tensors).  ``plain_scan=True`` makes the link kernel look at every earlier (later) run of
+    a pair instead of stopping at the first one too far away to link; the chains are the same
+    bytes, which is what the switch is there to show."""
+
+    def __init__(self, plain_scan: bool = False) -> None:
+        if not isinstance(plain_scan, (bool, np.bool_)):
+            raise ValueError("plain_scan must be a bool")
+        self.plain_scan = bool(plain_scan)
+        self.scratch: torch.Tensor | None = None
+        self.marks: torch.Tensor | None = None
+        self.slots: torch.Tensor | None = None
+
+    def buffers(self, device, runs: int, scratch_bytes: int):
+        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
+        self.marks = _grown(self.marks, device, runs, torch.int32)
+        self.slots = _grown(self.slots, device, runs, torch.int64)
+        return self.scratch, self.marks[:runs], self.slots[:runs]
+
+
+def _checked_runs(runs) -> tuple:
+    """``(pairs, cells, lengths, weights)`` of a ``Runs`` (or any 4-tuple of torch tensors or
+    numpy arrays) with the dtypes and shapes of ``hit_runs``' result, wherever they live."""
+    if not isinstance(runs, tuple) or len(runs) != 4:
+        raise ValueError("runs must be an align.Runs (pairs, cells, lengths, weights)")
+    parts = []
+    for part, name, dtype, dim in zip(runs, Runs._fields, (torch.int32, torch.int32, torch.int32,
+                                                           torch.float32), (2, 2, 1, 1)):
+        if isinstance(part, np.ndarray):
+            part = torch.from_numpy(np.ascontiguousarray(part))
+        if not isinstance(part, torch.Tensor) or part.dtype != dtype or part.dim() != dim or \
+                (dim == 2 and part.shape[1] != 2):
+            raise ValueError(f"runs.{name} must be a {str(dtype).replace('torch.', '')} array "
+                             f"of shape {'(S, 2)' if dim == 2 else '(S,)'}")
+        parts.append(part)
+    count = parts[2].shape[0]
+    for part, name in zip(parts, Runs._fields):
+        if part.shape[0] != count:
+            raise ValueError(f"runs.{name} has {part.shape[0]} entries, runs.lengths {count}")
+    if count >= 2 ** 31 - 1:
+        raise ValueError("runs must hold fewer than 2^31 - 1 runs")
+    return tuple(parts)
+
+
+def _checked_reach(value, name: str) -> int:
+    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 0:
+        raise ValueError(f"{name} must be a non-negative integer")
+    return min(int(value), 2 ** 31 - 1)     # coordinates are int32: nothing lies farther apart
+
+
+def chain_runs(runs, *, max_gap: int, max_shift: int | None = None,
+               workspace: ChainsWorkspace | None = None) -> Chains:
+    """The runs of ``hit_runs`` linked across neighbouring diagonals: ``Chains(pairs, starts,
+    ends, diagonals, counts, lengths, weights, members)`` on the device.  An inserted or deleted
+    row cuts a shared region into two runs on two diagonals; a chain is the region again, with
+    the band ``Chains.bands`` that holds all of it.  A fixed function of the ``Runs`` and two
+    integers, bit for bit; it needs no counts.
+
+    Definition (the head of this module and include/gfy.h have it too).
+
+    Inputs.  ``runs = Runs(pairs int32 [S, 2], cells int32 [S, 2], lengths int32 [S], weights
+    float32 [S])``, in the order ``hit_runs`` emits them: the key ``(q, cell_i, r, cell_j)`` is
+    strictly ascending lexicographically from run to run (this follows from "i ascending, then j
+    ascending" over contiguous records).  A boolean-mask subset of a ``Runs`` keeps this order; a
+    ``best()`` permutation does not.
+
+    Terms.  Run s has pair ``(q_s, r_s)``, head ``(i_s, j_s)``, length ``L_s >= 1`` and diagonal
+    ``d_s = j_s - i_s``.  Its tail is the cell ``(i_s + L_s - 1, j_s + L_s - 1)``.
+
+    Linking rule.  s may precede t (``s -> t``) if and only if all of these hold: the pairs are
+    equal; ``gi = i_t - (i_s + L_s) >= 0``; ``gj = j_t - (j_s + L_s) >= 0``; ``max(gi, gj) <=
+    max_gap``; ``|d_t - d_s| = |gj - gi| <= max_shift``.  ``max_shift=None`` means ``max_gap``.
+    There is no overlap in either coordinate, and ``s -> t`` implies ``s < t`` in Runs order.
+
+    Forward pass.  ``C[t] = L_t + max(0, max over s -> t of C[s])``, computed in int64.
+    ``pred[t]`` is the s that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then
+    to the largest s; ``pred[t] = -1`` when no s precedes t.
+
+    Backward pass.  The mirror image: ``D[s] = L_s + max(0, max over s -> t of D[t])``.
+    ``succ[s]`` is the t that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then
+    to the smallest t.
+
+    Links and chains.  A link ``s - t`` is kept if and only if ``pred[t] == s`` and ``succ[s] ==
+    t``: both ends must choose each other.  Every run therefore has at most one kept predecessor
+    and at most one kept successor.  The chains are the maximal paths; every run belongs to
+    exactly one chain, and a chain lies in one record pair.  The rule was chosen because it is
+    symmetric (the runs read backwards give the same chains) and needs no serial "take the best
+    chain, remove its runs, repeat" step: two passes and a comparison decide every link.  What it
+    guarantees: where a record pair's maximum-hit chain is unique, including all its prefixes and
+    suffixes, that chain is one of the chains returned.
+
+    Output.  Chains come in the order of their first runs.  ``pairs`` int32 ``[K, 2]``; ``starts``
+    int32 ``[K, 2]``, the head of the first run; ``ends`` int32 ``[K, 2]``, the tail of the last
+    run; ``diagonals`` int32 ``[K, 2]``, ``(min d, max d)`` over the chain's runs; ``counts`` int32
+    ``[K]``, the number of runs; ``lengths`` int32 ``[K]``, the sum of ``L``, which is the number
+    of hits; ``weights`` float32 ``[K]``, the runs' float32 weights added in float64 in chain
+    order, each addition one rounded operation, rounded to float32 once; ``members`` int32
+    ``[S]``, the chain of every run: a chain's runs are ``flatnonzero(members == c)``, ascending.
+
+    Consequences.  ``max_gap=0`` links nothing, because two such runs would have been one maximal
+    run: then ``K == S``, ``starts == cells``, ``lengths`` are equal, ``weights`` are the same
+    bytes and ``members == arange(S)``.  ``counts.sum() == S`` and ``lengths.sum() ==
+    runs.lengths.sum()``, whatever the two integers.
+
+    Every argument error is a ``ValueError`` before a device is touched: ``runs`` that is not a
+    4-tuple of tensors or arrays with ``Runs``' dtypes and shapes, ``S >= 2^31 - 1``, a
+    ``max_gap`` or ``max_shift`` that is not a non-negative integer (a bool is none), a
+    ``workspace`` that is not a ``ChainsWorkspace``.  The checks that need the data are made on
+    the device in front of the launch, as ``hit_runs`` makes its own, and raise ``ValueError``
+    "runs are not those of hit_runs": ``lengths >= 1``, ``cells >= 0``, ``pairs >= 0``,
+    ``lengths.sum() < 2^31``, no tail beyond int32, the key strictly ascending.  Runs on the host
+    are moved to the device; there is no CPU path.  ``S == 0`` returns empty tensors without a
+    launch.
+
+    Two launches with torch plumbing around them, as in ``hit_runs``: a stable sort of the runs
+    by the key ``q * 2^31 + r`` in int64 and the group boundaries in front of the link launch (one
+    wave per record pair; include/gfy.h says what it does), the running sum of chain-head marks
+    behind it, whose total K comes to the host, then the emit launch.  Not built: overlapping
+    runs, a gap or shift penalty in the chain score, chains across record pairs or shards, a CPU
+    path."""
+    pairs, cells, lengths, weights = _checked_runs(runs)
+    max_gap = _checked_reach(max_gap, "max_gap")
+    max_shift = max_gap if max_shift is None else _checked_reach(max_shift, "max_shift")
+    if workspace is not None and not isinstance(workspace, ChainsWorkspace):
+        raise ValueError("workspace must be a ChainsWorkspace")
+    count = lengths.shape[0]
+    devices = {part.device for part in (pairs, cells, lengths, weights)
+               if part.device.type == "cuda"}
+    if len(devices) > 1:
+        raise ValueError("runs must live on one device")
+    device = devices.pop() if devices else torch.device("cuda")
+    pairs, cells, lengths, weights = (part.to(device).contiguous()
+                                      for part in (pairs, cells, lengths, weights))
+    device = pairs.device
+    with torch.cuda.device(device):
+        def fresh(*shape, dtype=torch.int32):
+            return torch.empty(shape, dtype=dtype, device=device)
+        if count == 0:
+            return Chains(*(fresh(0, 2) for _ in range(4)), fresh(0), fresh(0),
+                          fresh(0, dtype=torch.float32), fresh(0))
+        # (q, i, r, j) strictly ascending from run to run, in lexicographic order
+        keys = torch.stack([pairs[:, 0], cells[:, 0], pairs[:, 1], cells[:, 1]], dim=1)
+        below, equal = keys[:-1] < keys[1:], keys[:-1] == keys[1:]
+        ascending = below[:, 3]
+        for column in (2, 1, 0):
+            ascending = below[:, column] | (equal[:, column] & ascending)
+        sound = (lengths >= 1).all() & (cells >= 0).all() & (pairs >= 0).all() & \
+            (lengths.sum(dtype=torch.int64) < 2 ** 31) & ascending.all() & \
+            ((cells.to(torch.int64) + lengths[:, None]).max() <= 2 ** 31)
+        if not bool(sound.item()):
+            raise ValueError(
+                "runs are not those of hit_runs: lengths must be >= 1 and sum to less than 2^31, "
+                "cells and pairs must be >= 0, and (q, cell_i, r, cell_j) must ascend strictly "
+                "from run to run (a best() permutation does not)")
+        lib = native.library()
+        workspace = workspace or ChainsWorkspace()
+        scratch, marks, slots = workspace.buffers(
+            device, count, lib.gfy_chain_runs_workspace_bytes(count))
+        # the runs of one record pair side by side, in their own order: plumbing, as the scan is
+        key, order = torch.sort((pairs[:, 0].to(torch.int64) << 31) | pairs[:, 1].to(torch.int64),
+                                stable=True)
+        edge = torch.ones(count + 1, dtype=torch.bool, device=device)
+        edge[1:-1] = key[1:] != key[:-1]
+        bounds = torch.nonzero(edge).flatten()      # waits for the device
+        status = torch.zeros(2, dtype=torch.int32, device=device)
+        front = (pairs.data_ptr(), cells.data_ptr(), lengths.data_ptr(), weights.data_ptr(), count)
+        back = (scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(device).cuda_stream)
+        native.check(lib.gfy_chain_runs_link(
+            *front, order.data_ptr(), bounds.data_ptr(), bounds.numel() - 1, max_gap, max_shift,
+            int(workspace.plain_scan), marks.data_ptr(), status[0:].data_ptr(), *back),
+            "gfy_chain_runs_link")
+        torch.cumsum(marks > 0, 0, dtype=torch.int64, out=slots)
+        total = int(slots[-1].item())   # waits for the device
+        if total < 1:
+            raise native.NativeLibraryError("gfy_chain_runs_link: no run starts a chain")
+        chains = Chains(fresh(total, 2), fresh(total, 2), fresh(total, 2), fresh(total, 2),
+                        fresh(total), fresh(total), fresh(total, dtype=torch.float32),
+                        fresh(count))
+        native.check(lib.gfy_chain_runs_emit(
+            *front, marks.data_ptr(), slots.data_ptr(), total,
+            *(out.data_ptr() for out in chains), status[1:].data_ptr(), *back),
+            "gfy_chain_runs_emit")
+        if bool(status.any().item()):
+            raise native.NativeLibraryError(
+                "gfy_chain_runs: the sorted order contradicted the sizes of the call")
+        return chains
 
 
 def _checked_parameter(value, name: str) -> float:
@@ -877,4 +1174,5 @@ def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
 
 __all__ = ["local_align", "local_spans", "local_paths", "global_align", "global_paths",
            "path_cells", "AlignedPaths", "AlignWorkspace", "top_pairs", "band_around",
-           "hit_cells", "hit_runs", "Runs", "RunsWorkspace"]
+           "hit_cells", "hit_runs", "Runs", "RunsWorkspace", "chain_runs", "Chains",
+           "ChainsWorkspace"]

@@ -1015,6 +1015,99 @@ int gfy_hit_runs_emit(const int64_t* offsets /* [n + 1] */, int64_t n,
                       int32_t* out_lengths /* [runs] */, float* out_weights /* [runs] */,
                       int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
+/* Chains of runs: the runs of gfy_hit_runs_emit LINKED ACROSS NEIGHBOURING DIAGONALS.  A run is a
+ * gapless stretch on one diagonal, so a region that two records share with one inserted or
+ * deleted row is two runs on two diagonals; this call joins such pieces into one chain and gives
+ * the band of diagonals that holds all of it, which is what the gfy_align_*_band calls take.  It
+ * is a fixed function of the runs and two integers, bit for bit, and needs no counts.
+ *   Inputs      runs = (pairs int32 [S][2], cells int32 [S][2], lengths int32 [S], weights
+ *               float32 [S]), device memory, in the order gfy_hit_runs_emit writes them: the key
+ *               (q, cell_i, r, cell_j) is strictly ascending lexicographically from run to run
+ *               (this follows from "i ascending, then j ascending" over contiguous records).  A
+ *               subset of the runs in their order keeps this property; a permutation does not.
+ *   Terms       Run s has pair (q_s, r_s), head (i_s, j_s), length L_s >= 1 and diagonal d_s =
+ *               j_s - i_s.  Its tail is the cell (i_s + L_s - 1, j_s + L_s - 1).
+ *   Linking     s may precede t (s -> t) if and only if all of these hold: the pairs are equal;
+ *               gi = i_t - (i_s + L_s) >= 0; gj = j_t - (j_s + L_s) >= 0; max(gi, gj) <= max_gap;
+ *               |d_t - d_s| = |gj - gi| <= max_shift.  There is no overlap in either coordinate,
+ *               and s -> t implies s < t in the order of the runs.
+ *   Forward     C[t] = L_t + max(0, max over s -> t of C[s]), computed in int64.  pred[t] is the s
+ *               that attains the maximum; ties go to the smallest |d_t - d_s|, then to the largest
+ *               s; pred[t] = -1 when no s precedes t.
+ *   Backward    The mirror image: D[s] = L_s + max(0, max over s -> t of D[t]).  succ[s] is the t
+ *               that attains the maximum; ties go to the smallest |d_t - d_s|, then to the
+ *               smallest t; succ[s] = -1 when s precedes no t.
+ *   Chains      A link s - t is kept if and only if pred[t] == s and succ[s] == t: both ends must
+ *               choose each other.  Every run therefore has at most one kept predecessor and at
+ *               most one kept successor.  The chains are the maximal paths; every run belongs to
+ *               exactly one chain, and a chain lies in one record pair.  The rule was chosen
+ *               because it is symmetric (the runs read backwards give the same chains) and needs
+ *               no serial "take the best chain, remove its runs, repeat" step: two passes and a
+ *               comparison decide every link.  What it guarantees: where a record pair's
+ *               maximum-hit chain is unique, including all its prefixes and suffixes, that chain
+ *               is one of the chains returned.
+ *   Output      Chains come in the order of their first runs; chain c gets
+ *                 out_pairs[c]     = (q, r)                             int32 [chains][2]
+ *                 out_starts[c]    = the head of the first run          int32 [chains][2]
+ *                 out_ends[c]      = the tail of the last run           int32 [chains][2]
+ *                 out_diagonals[c] = (min d, max d) over its runs       int32 [chains][2]
+ *                 out_counts[c]    = the number of its runs             int32 [chains]
+ *                 out_lengths[c]   = the sum of L: the number of hits   int32 [chains]
+ *                 out_weights[c]   = the runs' float32 weights added in float64 in chain order,
+ *                                    each addition one rounded operation, rounded to float32 once
+ *               and every run s out_members[s] = its chain (int32 [S]): a chain's runs are the s
+ *               with out_members[s] == c, ascending.
+ *   It follows  max_gap = 0 links nothing, because two such runs would have been one maximal run:
+ *               then chains == S, starts == cells, the lengths are equal, the weights are the same
+ *               bytes and members[s] == s.  The counts sum to S and the lengths to the sum of the
+ *               runs' lengths, whatever the two integers.
+ *   Calls       The caller sorts the runs by record pair with a STABLE sort (any key that is
+ *               equal exactly where the pairs are: q * 2^31 + r in int64 cannot overflow) and
+ *               passes order int64 [S], the permutation, and bounds int64 [groups + 1], ascending
+ *               from 0 to S: group g is order[bounds[g] .. bounds[g + 1]), the runs of one pair.
+ *               gfy_chain_runs_link writes marks int32 [S]: the count of its chain at a chain's
+ *               first run, 0 at every other run; everything else goes to the workspace.
+ *               gfy_chain_runs_emit takes slots int64 [S], the running sums of (marks > 0), the
+ *               entry of s included, chains = slots[S - 1] >= 1, and the SAME workspace, untouched
+ *               since the link call on the same runs.
+ *   Safety      The preconditions that need the data (L >= 1, cells >= 0, pairs >= 0, the sum of L
+ *               and every i + L, j + L at most 2^31 - 1 resp. 2^31, the ascending key) are the
+ *               caller's; without them the chains have no meaning, and still no access leaves an
+ *               array and no loop runs on.  *status (int32, one word, device memory, zeroed by
+ *               each call) is set non-zero when order, bounds, a group that mixes pairs, or slots
+ *               contradict the sizes of the call: every index read from memory is clipped or
+ *               checked in front of its use, and a walk along a chain only moves forward.
+ *   Cost        One wave per record pair.  A pass is serial in its runs; the 64 lanes share the
+ *               candidates of one run, and because a pair's runs ascend in i a lane stops at the
+ *               first one too far away to link, so a step costs the runs within max_gap + the
+ *               pair's longest run of rows, not the pair.  plain != 0 scans every candidate; the
+ *               result is the same (it exists to show that).  A group of up to 1,024 runs is
+ *               held in LDS, a larger one in the workspace, by the same code.  A chain is walked
+ *               by one lane.  Measured cost: DESIGN.md §4.
+ *   Workspace   gfy_chain_runs_workspace_bytes(runs): 64 bytes per run.
+ *   A NULL pointer, runs outside 1..2^31 - 2, groups or chains outside 1..runs and max_gap or
+ *   max_shift outside 0..2^31 - 1 are GFY_ERR_INVALID, a short workspace is GFY_ERR_WORKSPACE; all
+ *   of it before any launch and without a device.  Not built: overlapping runs, a gap or shift
+ *   penalty in the chain score, chains across record pairs or shards, a host path.            */
+size_t gfy_chain_runs_workspace_bytes(int64_t runs);
+int gfy_chain_runs_link(const int32_t* pairs /* [runs][2] */, const int32_t* cells /* [runs][2] */,
+                        const int32_t* lengths /* [runs] */, const float* weights /* [runs] */,
+                        int64_t runs, const int64_t* order /* [runs] */,
+                        const int64_t* bounds /* [groups + 1] */, int64_t groups,
+                        int64_t max_gap, int64_t max_shift, int plain,
+                        int32_t* marks /* [runs] */, int32_t* status,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int gfy_chain_runs_emit(const int32_t* pairs /* [runs][2] */, const int32_t* cells /* [runs][2] */,
+                        const int32_t* lengths /* [runs] */, const float* weights /* [runs] */,
+                        int64_t runs, const int32_t* marks /* [runs] */,
+                        const int64_t* slots /* [runs] */, int64_t chains,
+                        int32_t* out_pairs /* [chains][2] */, int32_t* out_starts /* [chains][2] */,
+                        int32_t* out_ends /* [chains][2] */,
+                        int32_t* out_diagonals /* [chains][2] */,
+                        int32_t* out_counts /* [chains] */, int32_t* out_lengths /* [chains] */,
+                        float* out_weights /* [chains] */, int32_t* out_members /* [runs] */,
+                        int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
