@@ -145,10 +145,12 @@ follows that
   path cell always has a positive value, so the walk never leaves the band;
 * re-scoring the ops gives ``score`` bit for bit, as without a band.
 
-``band_around`` makes bands from seed cells: ``hit_cells`` gives one seed per hit of
-``distance.topk`` or ``within``, ``hit_runs`` one per maximal diagonal run of ``within`` hits (its
-definition is in the function's docstring and in include/gfy.h).  The device
-does not do the work outside the band: a strip of 64 rows from row ``i0`` holds band cells in the
+Seeds and their bands come from ``seeds.py``, whose names this module exports: ``band_around``
+makes bands from seed cells, ``hit_cells`` gives one seed per hit of ``distance.topk`` or
+``within``, ``hit_runs`` one per maximal diagonal run of ``within`` hits, and ``chain_runs``
+links the runs that an inserted or deleted row cut apart into one band (``chains.pairs`` and
+``chains.bands(4)`` in place of the runs' in the recipe above).  Their definitions are at the
+head of that module.  The device does not do the work outside the band: a strip of 64 rows from row ``i0`` holds band cells in the
 columns ``c_lo = max(0, i0 + lo) .. c_hi = min(Lr - 1, i0 + rows - 1 + hi)`` only, a strip
 without any is skipped, and a strip takes ``c_hi - (c_lo & ~31) + rows`` steps against ``Lr + rows
 - 1`` (arithmetic, not a measurement; two records of 4,096 rows and a band of 129 diagonals:
@@ -159,71 +161,7 @@ Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIM
 and ``within`` modes (borders that leave the band, pairs with no admissible path at all),
 band-only storage of the direction words, a span-only kernel for the global and ``within`` modes,
 free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
-scores.  Out of scope for ``hit_runs``: a cross-shard form in ``parallel.py``, runs from ``topk``
-results (a ``[n, k]`` block is not sorted by b-row), and a ``device="cpu"`` path.  Measured cost:
-DESIGN.md §4.
-
-Chains of runs (``chain_runs``).  A run is a gapless stretch on one diagonal, so two records that
-share a region with one inserted or deleted row give two runs on two diagonals.  ``chain_runs``
-links such pieces and returns, per chain, the band of diagonals that holds all of it:
-
-    chains = align.chain_runs(runs, max_gap=8)              # max_shift defaults to max_gap
-    best = chains.best(64)                                  # most hits, then heaviest
-    paths = align.local_paths(rows, counts_a=counts, pairs=chains.pairs[best],
-                              band=chains.bands(4)[best], gap_open=1.0, gap_extend=0.25)
-
-It is a fixed function of the ``Runs`` and two integers, bit for bit, and needs no counts.
-
-Inputs.  ``runs = Runs(pairs int32 [S, 2], cells int32 [S, 2], lengths int32 [S], weights float32
-[S])``, in the order ``hit_runs`` emits them: the key ``(q, cell_i, r, cell_j)`` is strictly
-ascending lexicographically from run to run (this follows from "i ascending, then j ascending"
-over contiguous records).  A boolean-mask subset of a ``Runs`` keeps this order; a ``best()``
-permutation does not.
-
-Terms.  Run s has pair ``(q_s, r_s)``, head ``(i_s, j_s)``, length ``L_s >= 1`` and diagonal ``d_s
-= j_s - i_s``.  Its tail is the cell ``(i_s + L_s - 1, j_s + L_s - 1)``.
-
-Linking rule.  s may precede t (``s -> t``) if and only if all of these hold: the pairs are equal;
-``gi = i_t - (i_s + L_s) >= 0``; ``gj = j_t - (j_s + L_s) >= 0``; ``max(gi, gj) <= max_gap``;
-``|d_t - d_s| = |gj - gi| <= max_shift``.  ``max_shift=None`` means ``max_gap``.  There is no
-overlap in either coordinate, and ``s -> t`` implies ``s < t`` in Runs order.
-
-Forward pass.  ``C[t] = L_t + max(0, max over s -> t of C[s])``, computed in int64.  ``pred[t]`` is
-the s that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then to the largest s;
-``pred[t] = -1`` when no s precedes t.
-
-Backward pass.  The mirror image: ``D[s] = L_s + max(0, max over s -> t of D[t])``.  ``succ[s]`` is
-the t that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then to the smallest t.
-
-Links and chains.  A link ``s - t`` is kept if and only if ``pred[t] == s`` and ``succ[s] == t``:
-both ends must choose each other.  Every run therefore has at most one kept predecessor and at
-most one kept successor.  The chains are the maximal paths; every run belongs to exactly one
-chain, and a chain lies in one record pair.  The rule was chosen because it is symmetric (the
-runs read backwards give the same chains) and needs no serial "take the best chain, remove its
-runs, repeat" step: two passes and a comparison decide every link.  What it guarantees: where a
-record pair's maximum-hit chain is unique, including all its prefixes and suffixes, that chain is
-one of the chains returned.
-
-Output.  ``Chains`` is a NamedTuple of device tensors; chains come in the order of their first
-runs.  ``pairs`` int32 ``[K, 2]``; ``starts`` int32 ``[K, 2]``, the head of the first run; ``ends``
-int32 ``[K, 2]``, the tail of the last run; ``diagonals`` int32 ``[K, 2]``, ``(min d, max d)`` over
-the chain's runs; ``counts`` int32 ``[K]``, the number of runs; ``lengths`` int32 ``[K]``, the sum
-of ``L``, which is the number of hits; ``weights`` float32 ``[K]``, the runs' float32 weights
-added in float64 in chain order, each addition one rounded operation, rounded to float32 once;
-``members`` int32 ``[S]``, the chain of every run: a chain's runs are ``flatnonzero(members ==
-c)``, ascending.  ``Chains.bands(half_width)`` gives ``(diagonals[:, 0] - half_width,
-diagonals[:, 1] + half_width)`` as an int32 host array, which is what ``local_align`` /
-``local_spans`` / ``local_paths`` take with ``pairs=chains.pairs``; ``Chains.best(k)`` is the rule
-of ``Runs.best``: lengths descending, then weights descending with NaN last, then position.
-
-Consequences.  ``max_gap=0`` links nothing, because two such runs would have been one maximal
-run: then ``K == S``, ``starts == cells``, ``lengths`` are equal, ``weights`` are the same bytes
-and ``members == arange(S)``.  ``counts.sum() == S`` and ``lengths.sum() == runs.lengths.sum()``,
-whatever the two integers.
-
-Out of scope for ``chain_runs``: overlapping runs (two runs that share a row or a column never
-link), a gap or shift penalty in the chain score (``C`` counts hits alone), chains across record
-pairs or shards, and a ``device="cpu"`` path.
+scores.  Measured cost: DESIGN.md §4.
 """
 from __future__ import annotations
 
@@ -234,7 +172,10 @@ import numpy as np
 import torch
 
 from . import _native as native
-from .distance import _checked, _checked_counts, _grown, _prepare, _record_ptr, record_of
+from .distance import (_checked, _checked_integer, _grown, _host_array, _prepare, _record_ptr,
+                       _scratch_tail)
+from .seeds import (Chains, ChainsWorkspace, Runs, RunsWorkspace, band_around, chain_runs,
+                    hit_cells, hit_runs)
 
 
 class AlignWorkspace:
@@ -252,9 +193,7 @@ class AlignWorkspace:
 
 def _checked_pairs(pairs, records_a: int, records_b: int) -> np.ndarray:
     """``pairs`` as an int32 ``[P, 2]`` host array with every index inside its side's records."""
-    if isinstance(pairs, torch.Tensor):
-        pairs = pairs.detach().cpu().numpy()
-    pairs = np.asarray(pairs)
+    pairs = _host_array(pairs)
     if pairs.size == 0 and pairs.ndim in (1, 2):
         pairs = np.zeros((0, 2), dtype=np.int64)
     if pairs.ndim != 2 or pairs.shape[1] != 2 or pairs.dtype.kind not in "iu":
@@ -276,11 +215,9 @@ def _checked_band(band, count: int) -> np.ndarray | None:
     into ``[-GFY_ALIGN_ROWS_MAX, GFY_ALIGN_ROWS_MAX]``; ``None`` stays ``None`` (no band)."""
     if band is None:
         return None
-    if isinstance(band, torch.Tensor):
-        band = band.detach().cpu().numpy()
-    elif isinstance(band, (tuple, list)) and any(isinstance(x, (bool, np.bool_)) for x in band):
+    if isinstance(band, (tuple, list)) and any(isinstance(x, (bool, np.bool_)) for x in band):
         raise ValueError("band must hold integers (lo, hi)")
-    band = np.asarray(band)
+    band = _host_array(band)
     if band.size == 0 and count == 0 and band.ndim in (1, 2):
         band = np.zeros((0, 2), dtype=np.int64)
     if band.dtype.kind not in "iu":
@@ -296,495 +233,6 @@ def _checked_band(band, count: int) -> np.ndarray | None:
                          "lo <= hi is required")
     limit = native.GFY_ALIGN_ROWS_MAX
     return np.ascontiguousarray(np.clip(band, -limit, limit).astype(np.int32))
-
-
-def band_around(seeds, half_width: int) -> np.ndarray:
-    """The bands of ``half_width`` diagonals on either side of seed cells: int32 ``[P, 2]`` of
-    ``(j - i - half_width, j - i + half_width)`` for ``seeds``, an integer ``[P, 2]`` array (numpy
-    or torch) of cells ``(i, j)`` inside the two records of each pair; ``half_width`` is a
-    non-negative integer, 0 the seed's diagonal alone.  A pure function of its arguments: no
-    device is needed.  ``hit_cells`` turns the hits of ``distance.topk`` / ``within`` into seeds
-    (one per hit, by taking away each record's first row) and the ``pairs`` that go with them;
-    ``hit_runs`` makes one seed per diagonal run of ``within`` hits, and ``Runs.bands`` is this
-    function on them.
-    """
-    if isinstance(half_width, (bool, np.bool_)) or \
-            not isinstance(half_width, (int, np.integer)) or half_width < 0:
-        raise ValueError("half_width must be a non-negative integer")
-    if isinstance(seeds, torch.Tensor):
-        seeds = seeds.detach().cpu().numpy()
-    seeds = np.asarray(seeds)
-    if seeds.size == 0 and seeds.ndim in (1, 2):
-        return np.zeros((0, 2), dtype=np.int32)
-    if seeds.ndim != 2 or seeds.shape[1] != 2 or seeds.dtype.kind not in "iu":
-        raise ValueError("seeds must be an integer array of shape (P, 2) of cells (i, j)")
-    seeds = seeds.astype(np.int64)
-    if seeds.min() < 0 or seeds.max() >= native.GFY_ALIGN_ROWS_MAX:
-        raise ValueError(f"seeds must be cells inside records: 0 <= i, j < "
-                         f"{native.GFY_ALIGN_ROWS_MAX}")
-    diagonal = seeds[:, 1] - seeds[:, 0]
-    limit = 2 * native.GFY_ALIGN_ROWS_MAX      # wider than any matrix: the values stay int32
-    width = min(int(half_width), limit)
-    return np.stack([diagonal - width, diagonal + width], axis=1).astype(np.int32)
-
-
-def hit_cells(rows, indices, counts_a, counts_b=None) -> tuple:
-    """Hits as seed cells: ``(q, r, cells)`` for the hits (row ``rows[x]`` of ``a``, row
-    ``indices[x]`` of ``b``) of ``distance.topk`` / ``nearest`` / ``within`` — ``q`` and ``r`` the
-    records of the two rows (``distance.record_of``: a row at a boundary belongs to the record
-    that starts there) and ``cells`` ``[P, 2]`` the rows minus each record's first row, which is
-    what ``band_around`` takes as seeds and ``stack([q, r], 1)`` what the aligners take as
-    ``pairs``.  One seed per hit; ``hit_runs`` makes one per stretch of collinear hits.
-
-    ``rows`` and ``indices`` are integer arrays of one shape and one library: torch tensors (on
-    one device; the results stay there, ``q`` and ``r`` int32, ``cells`` int64) or numpy arrays
-    (numpy results).  ``counts_a`` / ``counts_b`` are the row counts of the records of ``a`` /
-    ``b`` (any integer sequence, checked as ``record_of`` checks them; ``counts_b`` defaults to
-    ``counts_a``).  An index outside every record, ``-1`` included, gives record ``-1`` and a
-    cell coordinate of ``-1``."""
-    counts_a = _checked_counts(counts_a)
-    counts_b = counts_a if counts_b is None else _checked_counts(counts_b)
-    as_torch = isinstance(rows, torch.Tensor)
-    if as_torch != isinstance(indices, torch.Tensor):
-        raise ValueError("rows and indices must both be torch tensors or both numpy arrays")
-    if not as_torch:
-        rows, indices = (torch.from_numpy(np.ascontiguousarray(x)) for x in (rows, indices))
-    if rows.shape != indices.shape or rows.dim() != 1 or rows.device != indices.device or \
-            rows.dtype.is_floating_point or indices.dtype.is_floating_point or \
-            torch.bool in (rows.dtype, indices.dtype):
-        raise ValueError("rows and indices must be one-dimensional integer arrays of one length "
-                         "(torch: on one device)")
-    found, inside = [], []
-    for index, counts in ((rows, counts_a), (indices, counts_b)):
-        record = record_of(index, counts)
-        first = torch.from_numpy(np.concatenate(([0], np.cumsum(counts)))).to(index.device)
-        outside = record < 0
-        start = first[torch.where(outside, torch.zeros_like(record), record).to(torch.int64)]
-        found.append(record)
-        inside.append(torch.where(outside, torch.full_like(start, -1),
-                                  index.to(torch.int64) - start))
-    cells = torch.stack(inside, dim=1)
-    if as_torch:
-        return found[0], found[1], cells
-    return found[0].numpy(), found[1].numpy(), cells.numpy()
-
-
-class Runs(NamedTuple):
-    """What ``hit_runs`` returns, all on the device: run s lies in the record pair ``pairs[s]``,
-    starts at the cell ``cells[s]`` inside the two records, and is ``lengths[s]`` hits long on
-    the diagonal ``cells[s, 1] - cells[s, 0]``; ``weights[s]`` is the sum of its values."""
-    pairs: torch.Tensor     # int32 [S, 2] of (record of a, record of b)
-    cells: torch.Tensor     # int32 [S, 2] of the head (i, j) inside the two records
-    lengths: torch.Tensor   # int32 [S]
-    weights: torch.Tensor   # float32 [S]
-
-    def bands(self, half_width: int) -> np.ndarray:
-        """``band_around(self.cells, half_width)``: the band of every run's diagonal for
-        ``local_align`` / ``local_spans`` / ``local_paths`` with ``pairs=self.pairs``."""
-        return band_around(self.cells, half_width)
-
-    def best(self, k: int) -> np.ndarray:
-        """The indices (int64 host array, at most ``k``) of the ``k`` runs that come first in the
-        order ``lengths`` descending, then ``weights`` descending, then position ascending; a NaN
-        weight ranks behind every number of its length.  A pure function of ``lengths`` and
-        ``weights``, which come to the host for it."""
-        return _best(self.lengths, self.weights, k)
-
-
-def _best(lengths, weights, k) -> np.ndarray:
-    """The rule of ``Runs.best`` and ``Chains.best``: the first ``k`` positions in the order
-    ``lengths`` descending, then ``weights`` descending with NaN last, then position."""
-    if isinstance(k, (bool, np.bool_)) or not isinstance(k, (int, np.integer)) or k < 1:
-        raise ValueError("k must be a positive integer")
-    lengths, weights = (x.detach().cpu().numpy() if isinstance(x, torch.Tensor)
-                        else np.asarray(x) for x in (lengths, weights))
-    missing = np.isnan(weights)
-    # by (length, NaN or not, weight, position): lexsort is stable and takes its last key first
-    order = np.lexsort((np.where(missing, 0, -weights.astype(np.float64)), missing,
-                        -lengths.astype(np.int64)))
-    return order[:int(k)].astype(np.int64)
-
-
-class RunsWorkspace:
-    """Scratch memory, marks and slots of ``hit_runs`` kept across calls (the runs are always new
-    tensors)."""
-
-    def __init__(self) -> None:
-        self.scratch: torch.Tensor | None = None
-        self.marks: torch.Tensor | None = None
-        self.slots: torch.Tensor | None = None
-
-    def buffers(self, device, hits: int, scratch_bytes: int):
-        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
-        self.marks = _grown(self.marks, device, hits, torch.int32)
-        self.slots = _grown(self.slots, device, hits, torch.int64)
-        return self.scratch, self.marks[:hits], self.slots[:hits]
-
-
-def _checked_hits(hits) -> tuple:
-    """``(offsets, indices, values)`` of a ``distance.Hits`` (or any triple of torch tensors or
-    numpy arrays) with the dtypes and shapes of ``within``'s result, wherever they live."""
-    if not isinstance(hits, tuple) or len(hits) != 3:
-        raise ValueError("hits must be a distance.Hits (offsets, indices, values)")
-    parts = []
-    for part, name, dtype in zip(hits, ("offsets", "indices", "values"),
-                                 (torch.int64, torch.int32, torch.float32)):
-        if isinstance(part, np.ndarray):
-            part = torch.from_numpy(np.ascontiguousarray(part))
-        if not isinstance(part, torch.Tensor) or part.dtype != dtype or part.dim() != 1:
-            raise ValueError(f"hits.{name} must be a one-dimensional "
-                             f"{str(dtype).replace('torch.', '')} array")
-        parts.append(part)
-    offsets, indices, values = parts
-    if offsets.numel() < 1:
-        raise ValueError("hits.offsets must hold n + 1 entries")
-    if indices.numel() != values.numel():
-        raise ValueError(f"hits.indices has {indices.numel()} entries, hits.values "
-                         f"{values.numel()}")
-    if indices.numel() >= 2 ** 31 - 1:
-        raise ValueError("hits must hold fewer than 2^31 - 1 hits")
-    return offsets, indices, values
-
-
-def hit_runs(hits, *, counts_a, counts_b=None, min_length: int = 1,
-             workspace: RunsWorkspace | None = None) -> Runs:
-    """The maximal diagonal runs of the hits of ``distance.within``: ``Runs(pairs int32 [S, 2],
-    cells int32 [S, 2], lengths int32 [S], weights float32 [S])`` on the device.  A stretch that
-    two records share is one hit per row on one diagonal; this collapses each into one seed with
-    the evidence behind it, and ``pairs`` says which records are worth aligning at all without a
-    dense ``record_scores``.
-
-    Definition (include/gfy.h has it too).  ``hits = Hits(offsets int64 [n + 1], indices int32
-    [H], values float32 [H])``: row i's hits are ``indices[offsets[i]:offsets[i + 1]]``, strictly
-    ascending, the contract of ``within``.  ``counts_a`` are the rows of ``a`` in contiguous
-    records (``sum == n``, zero counts allowed), ``counts_b`` those of ``b`` (``sum == m``;
-    default ``counts_a``, the self-search form), ``ptr_a`` / ``ptr_b`` their running sums.  A row
-    at a boundary belongs to the record that starts there, a record of zero rows owns nothing
-    (``distance.record_of``).  For a hit ``(i, j)`` let ``q``, ``r`` be the records of ``i`` and
-    ``j``.  Its predecessor is ``(i - 1, j - 1)``; it counts only if it is a hit, ``i - 1 >=
-    ptr_a[q]`` and ``j - 1 >= ptr_b[r]``, so that it lies in the same two records.  A hit without
-    a predecessor is a head; the run of a head is the hits ``(i + t, j + t)``, ``t = 0 .. L - 1``,
-    for the largest ``L`` for which all of them are hits inside records ``q`` and ``r``.  Every
-    hit belongs to exactly one run, and a run never crosses a record boundary on either side.
-    Run s has ``pairs[s] = (q, r)``, ``cells[s] = (i - ptr_a[q], j - ptr_b[r])`` (its head inside
-    the two records), ``lengths[s] = L`` and ``weights[s]`` = the sum of its ``L`` values,
-    accumulated in float64 in ascending ``t``, each addition one rounded operation, and rounded
-    to float32 once (the rule of ``record_scores``).  Runs come in the order of their heads
-    inside ``hits``: ``i`` ascending, then ``j`` ascending.  ``min_length`` (an integer >= 1)
-    drops the shorter runs and keeps the order of the rest.
-
-    A run is a function of the hits and the counts alone, bit for bit.  So the lengths sum to
-    ``H`` at ``min_length=1``; ``min_length=k`` is that result filtered by length; and a record
-    that is a bit-identical copy of another gives, under a threshold its rows pass, exactly one
-    run ``(q, r, (0, 0), rows of the record)`` on the pair's main diagonal, whatever else hits.
-
-    Every argument error is a ``ValueError`` before a device is touched: dtypes, shapes,
-    ``min_length``, the counts (checked as ``record_scores`` checks them), ``offsets.numel() ==
-    sum(counts_a) + 1``.  Three more need the data and are made on the device in front of the
-    launch — ``offsets[0] == 0``; ``offsets`` non-decreasing with ``offsets[-1] == H``; ``0 <=
-    indices < sum(counts_b)`` — so that no hand-made ``Hits`` makes a kernel read outside its
-    arrays.  Ascending order inside a row is a precondition and is not checked.  Hits on the
-    host are moved to the device, as rows are; there is no CPU path.
-
-    Two launches with a running sum between them (``torch.cumsum``: plumbing, as in ``within``),
-    whose total comes to the host, which waits for the device as ``within`` does.  One lane per
-    hit; a head walks its run serially, so a run of ``L`` hits is ``L`` steps of one lane
-    (DESIGN.md §4).  ``H == 0`` or ``n == 0`` returns four empty tensors without a launch."""
-    offsets, indices, values = _checked_hits(hits)
-    if isinstance(min_length, (bool, np.bool_)) or \
-            not isinstance(min_length, (int, np.integer)) or min_length < 1:
-        raise ValueError("min_length must be a positive integer")
-    if workspace is not None and not isinstance(workspace, RunsWorkspace):
-        raise ValueError("workspace must be a RunsWorkspace")
-    n, total = offsets.numel() - 1, indices.numel()
-    ptr_a = _record_ptr(counts_a, n, "counts_a", "hits")
-    if counts_b is None:
-        ptr_b = ptr_a
-    else:
-        ptr_b = _record_ptr(counts_b, int(_checked_counts(counts_b).sum()), "counts_b", "b")
-    m = int(ptr_b[-1])
-    devices = {part.device for part in (offsets, indices, values) if part.device.type == "cuda"}
-    if len(devices) > 1:
-        raise ValueError("hits must live on one device")
-    device = devices.pop() if devices else torch.device("cuda")
-    offsets, indices, values = (part.to(device).contiguous()
-                                for part in (offsets, indices, values))
-    device = offsets.device
-    with torch.cuda.device(device):
-        # every entry at or above its predecessor, the first 0, the last H; every index a row of b
-        sound = (offsets[0] == 0) & (offsets[-1] == total) & \
-            (offsets[1:] >= offsets[:-1]).all()
-        if total:
-            sound = sound & (indices.min() >= 0) & (indices.max() < m)
-        if not bool(sound.item()):
-            raise ValueError(
-                "hits are not those of a search: offsets must start at 0, never decrease and end "
-                f"at {total} = the number of hits, and indices must lie in 0..{m - 1}")
-        empty = Runs(torch.zeros((0, 2), dtype=torch.int32, device=device),
-                     torch.zeros((0, 2), dtype=torch.int32, device=device),
-                     torch.zeros(0, dtype=torch.int32, device=device),
-                     torch.zeros(0, dtype=torch.float32, device=device))
-        if total == 0 or n == 0:
-            return empty
-        lib = native.library()
-        scratch, marks, slots = (workspace or RunsWorkspace()).buffers(
-            device, total, lib.gfy_hit_runs_workspace_bytes(total))
-        ptr_a_dev = torch.from_numpy(ptr_a.astype(np.int32)).to(device)
-        ptr_b_dev = ptr_a_dev if ptr_b is ptr_a else \
-            torch.from_numpy(ptr_b.astype(np.int32)).to(device)
-        status = torch.zeros(2, dtype=torch.int32, device=device)
-        front = (offsets.data_ptr(), n, indices.data_ptr(), values.data_ptr(), total,
-                 ptr_a_dev.data_ptr(), ptr_a.size - 1, ptr_b_dev.data_ptr(), ptr_b.size - 1, m,
-                 marks.data_ptr())
-        back = (scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(device).cuda_stream)
-        native.check(lib.gfy_hit_runs_mark(*front, status[0:].data_ptr(), *back),
-                     "gfy_hit_runs_mark")
-        torch.cumsum(marks >= int(min_length), 0, dtype=torch.int64, out=slots)
-        count = int(slots[-1].item())   # waits for the device
-        if count == 0:
-            runs = empty
-        else:
-            runs = Runs(torch.empty((count, 2), dtype=torch.int32, device=device),
-                        torch.empty((count, 2), dtype=torch.int32, device=device),
-                        torch.empty(count, dtype=torch.int32, device=device),
-                        torch.empty(count, dtype=torch.float32, device=device))
-            native.check(lib.gfy_hit_runs_emit(
-                *front, slots.data_ptr(), min(int(min_length), 2 ** 31 - 1), count,
-                *(out.data_ptr() for out in runs), status[1:].data_ptr(), *back),
-                "gfy_hit_runs_emit")
-        if bool(status.any().item()):
-            raise native.NativeLibraryError(
-                "gfy_hit_runs: the hits contradicted the sizes of the call")
-        return runs
-
-
-class Chains(NamedTuple):
-    """What ``chain_runs`` returns, all on the device: chain c lies in the record pair
-    ``pairs[c]``, reaches from the cell ``starts[c]`` (the head of its first run) to the cell
-    ``ends[c]`` (the tail of its last run) on the diagonals ``diagonals[c, 0] .. diagonals[c, 1]``,
-    and is ``counts[c]`` runs of ``lengths[c]`` hits in all; ``weights[c]`` is the sum of their
-    weights.  ``members[s]`` is the chain of run s: a chain's runs are
-    ``flatnonzero(members == c)``, ascending."""
-    pairs: torch.Tensor       # int32 [K, 2] of (record of a, record of b)
-    starts: torch.Tensor      # int32 [K, 2]
-    ends: torch.Tensor        # int32 [K, 2]
-    diagonals: torch.Tensor   # int32 [K, 2] of (min d, max d)
-    counts: torch.Tensor      # int32 [K]
-    lengths: torch.Tensor     # int32 [K]
-    weights: torch.Tensor     # float32 [K]
-    members: torch.Tensor     # int32 [S]
-
-    def bands(self, half_width: int) -> np.ndarray:
-        """``(diagonals[:, 0] - half_width, diagonals[:, 1] + half_width)`` as an int32 ``[K, 2]``
-        host array: the band that holds every run of a chain, for ``local_align`` /
-        ``local_spans`` / ``local_paths`` with ``pairs=self.pairs``.  ``half_width`` is a
-        non-negative integer, 0 the chain's own diagonals alone; like ``band_around`` it is cut
-        at twice ``GFY_ALIGN_ROWS_MAX``, wider than any matrix."""
-        if isinstance(half_width, (bool, np.bool_)) or \
-                not isinstance(half_width, (int, np.integer)) or half_width < 0:
-            raise ValueError("half_width must be a non-negative integer")
-        diagonals = self.diagonals.detach().cpu().numpy() \
-            if isinstance(self.diagonals, torch.Tensor) else np.asarray(self.diagonals)
-        diagonals = diagonals.astype(np.int64).reshape(-1, 2)
-        width = min(int(half_width), 2 * native.GFY_ALIGN_ROWS_MAX)
-        limit = np.iinfo(np.int32)
-        return np.clip(np.stack([diagonals[:, 0] - width, diagonals[:, 1] + width], axis=1),
-                       limit.min, limit.max).astype(np.int32)
-
-    def best(self, k: int) -> np.ndarray:
-        """The indices (int64 host array, at most ``k``) of the ``k`` chains that come first by
-        the rule of ``Runs.best``: ``lengths`` (hits) descending, then ``weights`` descending with
-        NaN last, then position ascending."""
-        return _best(self.lengths, self.weights, k)
-
-
-class ChainsWorkspace:
-    """Scratch memory, marks and slots of ``chain_runs`` kept across calls (the chains are always
-    new tensors).  ``plain_scan=True`` makes the link kernel look at every earlier (later) run of
-    a pair instead of stopping at the first one too far away to link; the chains are the same
-    bytes, which is what the switch is there to show."""
-
-    def __init__(self, plain_scan: bool = False) -> None:
-        if not isinstance(plain_scan, (bool, np.bool_)):
-            raise ValueError("plain_scan must be a bool")
-        self.plain_scan = bool(plain_scan)
-        self.scratch: torch.Tensor | None = None
-        self.marks: torch.Tensor | None = None
-        self.slots: torch.Tensor | None = None
-
-    def buffers(self, device, runs: int, scratch_bytes: int):
-        self.scratch = _grown(self.scratch, device, scratch_bytes, torch.uint8)
-        self.marks = _grown(self.marks, device, runs, torch.int32)
-        self.slots = _grown(self.slots, device, runs, torch.int64)
-        return self.scratch, self.marks[:runs], self.slots[:runs]
-
-
-def _checked_runs(runs) -> tuple:
-    """``(pairs, cells, lengths, weights)`` of a ``Runs`` (or any 4-tuple of torch tensors or
-    numpy arrays) with the dtypes and shapes of ``hit_runs``' result, wherever they live."""
-    if not isinstance(runs, tuple) or len(runs) != 4:
-        raise ValueError("runs must be an align.Runs (pairs, cells, lengths, weights)")
-    parts = []
-    for part, name, dtype, dim in zip(runs, Runs._fields, (torch.int32, torch.int32, torch.int32,
-                                                           torch.float32), (2, 2, 1, 1)):
-        if isinstance(part, np.ndarray):
-            part = torch.from_numpy(np.ascontiguousarray(part))
-        if not isinstance(part, torch.Tensor) or part.dtype != dtype or part.dim() != dim or \
-                (dim == 2 and part.shape[1] != 2):
-            raise ValueError(f"runs.{name} must be a {str(dtype).replace('torch.', '')} array "
-                             f"of shape {'(S, 2)' if dim == 2 else '(S,)'}")
-        parts.append(part)
-    count = parts[2].shape[0]
-    for part, name in zip(parts, Runs._fields):
-        if part.shape[0] != count:
-            raise ValueError(f"runs.{name} has {part.shape[0]} entries, runs.lengths {count}")
-    if count >= 2 ** 31 - 1:
-        raise ValueError("runs must hold fewer than 2^31 - 1 runs")
-    return tuple(parts)
-
-
-def _checked_reach(value, name: str) -> int:
-    if isinstance(value, (bool, np.bool_)) or not isinstance(value, (int, np.integer)) or value < 0:
-        raise ValueError(f"{name} must be a non-negative integer")
-    return min(int(value), 2 ** 31 - 1)     # coordinates are int32: nothing lies farther apart
-
-
-def chain_runs(runs, *, max_gap: int, max_shift: int | None = None,
-               workspace: ChainsWorkspace | None = None) -> Chains:
-    """The runs of ``hit_runs`` linked across neighbouring diagonals: ``Chains(pairs, starts,
-    ends, diagonals, counts, lengths, weights, members)`` on the device.  An inserted or deleted
-    row cuts a shared region into two runs on two diagonals; a chain is the region again, with
-    the band ``Chains.bands`` that holds all of it.  A fixed function of the ``Runs`` and two
-    integers, bit for bit; it needs no counts.
-
-    Definition (the head of this module and include/gfy.h have it too).
-
-    Inputs.  ``runs = Runs(pairs int32 [S, 2], cells int32 [S, 2], lengths int32 [S], weights
-    float32 [S])``, in the order ``hit_runs`` emits them: the key ``(q, cell_i, r, cell_j)`` is
-    strictly ascending lexicographically from run to run (this follows from "i ascending, then j
-    ascending" over contiguous records).  A boolean-mask subset of a ``Runs`` keeps this order; a
-    ``best()`` permutation does not.
-
-    Terms.  Run s has pair ``(q_s, r_s)``, head ``(i_s, j_s)``, length ``L_s >= 1`` and diagonal
-    ``d_s = j_s - i_s``.  Its tail is the cell ``(i_s + L_s - 1, j_s + L_s - 1)``.
-
-    Linking rule.  s may precede t (``s -> t``) if and only if all of these hold: the pairs are
-    equal; ``gi = i_t - (i_s + L_s) >= 0``; ``gj = j_t - (j_s + L_s) >= 0``; ``max(gi, gj) <=
-    max_gap``; ``|d_t - d_s| = |gj - gi| <= max_shift``.  ``max_shift=None`` means ``max_gap``.
-    There is no overlap in either coordinate, and ``s -> t`` implies ``s < t`` in Runs order.
-
-    Forward pass.  ``C[t] = L_t + max(0, max over s -> t of C[s])``, computed in int64.
-    ``pred[t]`` is the s that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then
-    to the largest s; ``pred[t] = -1`` when no s precedes t.
-
-    Backward pass.  The mirror image: ``D[s] = L_s + max(0, max over s -> t of D[t])``.
-    ``succ[s]`` is the t that attains the maximum; ties go to the smallest ``|d_t - d_s|``, then
-    to the smallest t.
-
-    Links and chains.  A link ``s - t`` is kept if and only if ``pred[t] == s`` and ``succ[s] ==
-    t``: both ends must choose each other.  Every run therefore has at most one kept predecessor
-    and at most one kept successor.  The chains are the maximal paths; every run belongs to
-    exactly one chain, and a chain lies in one record pair.  The rule was chosen because it is
-    symmetric (the runs read backwards give the same chains) and needs no serial "take the best
-    chain, remove its runs, repeat" step: two passes and a comparison decide every link.  What it
-    guarantees: where a record pair's maximum-hit chain is unique, including all its prefixes and
-    suffixes, that chain is one of the chains returned.
-
-    Output.  Chains come in the order of their first runs.  ``pairs`` int32 ``[K, 2]``; ``starts``
-    int32 ``[K, 2]``, the head of the first run; ``ends`` int32 ``[K, 2]``, the tail of the last
-    run; ``diagonals`` int32 ``[K, 2]``, ``(min d, max d)`` over the chain's runs; ``counts`` int32
-    ``[K]``, the number of runs; ``lengths`` int32 ``[K]``, the sum of ``L``, which is the number
-    of hits; ``weights`` float32 ``[K]``, the runs' float32 weights added in float64 in chain
-    order, each addition one rounded operation, rounded to float32 once; ``members`` int32
-    ``[S]``, the chain of every run: a chain's runs are ``flatnonzero(members == c)``, ascending.
-
-    Consequences.  ``max_gap=0`` links nothing, because two such runs would have been one maximal
-    run: then ``K == S``, ``starts == cells``, ``lengths`` are equal, ``weights`` are the same
-    bytes and ``members == arange(S)``.  ``counts.sum() == S`` and ``lengths.sum() ==
-    runs.lengths.sum()``, whatever the two integers.
-
-    Every argument error is a ``ValueError`` before a device is touched: ``runs`` that is not a
-    4-tuple of tensors or arrays with ``Runs``' dtypes and shapes, ``S >= 2^31 - 1``, a
-    ``max_gap`` or ``max_shift`` that is not a non-negative integer (a bool is none), a
-    ``workspace`` that is not a ``ChainsWorkspace``.  The checks that need the data are made on
-    the device in front of the launch, as ``hit_runs`` makes its own, and raise ``ValueError``
-    "runs are not those of hit_runs": ``lengths >= 1``, ``cells >= 0``, ``pairs >= 0``,
-    ``lengths.sum() < 2^31``, no tail beyond int32, the key strictly ascending.  Runs on the host
-    are moved to the device; there is no CPU path.  ``S == 0`` returns empty tensors without a
-    launch.
-
-    Two launches with torch plumbing around them, as in ``hit_runs``: a stable sort of the runs
-    by the key ``q * 2^31 + r`` in int64 and the group boundaries in front of the link launch (one
-    wave per record pair; include/gfy.h says what it does), the running sum of chain-head marks
-    behind it, whose total K comes to the host, then the emit launch.  Not built: overlapping
-    runs, a gap or shift penalty in the chain score, chains across record pairs or shards, a CPU
-    path."""
-    pairs, cells, lengths, weights = _checked_runs(runs)
-    max_gap = _checked_reach(max_gap, "max_gap")
-    max_shift = max_gap if max_shift is None else _checked_reach(max_shift, "max_shift")
-    if workspace is not None and not isinstance(workspace, ChainsWorkspace):
-        raise ValueError("workspace must be a ChainsWorkspace")
-    count = lengths.shape[0]
-    devices = {part.device for part in (pairs, cells, lengths, weights)
-               if part.device.type == "cuda"}
-    if len(devices) > 1:
-        raise ValueError("runs must live on one device")
-    device = devices.pop() if devices else torch.device("cuda")
-    pairs, cells, lengths, weights = (part.to(device).contiguous()
-                                      for part in (pairs, cells, lengths, weights))
-    device = pairs.device
-    with torch.cuda.device(device):
-        def fresh(*shape, dtype=torch.int32):
-            return torch.empty(shape, dtype=dtype, device=device)
-        if count == 0:
-            return Chains(*(fresh(0, 2) for _ in range(4)), fresh(0), fresh(0),
-                          fresh(0, dtype=torch.float32), fresh(0))
-        # (q, i, r, j) strictly ascending from run to run, in lexicographic order
-        keys = torch.stack([pairs[:, 0], cells[:, 0], pairs[:, 1], cells[:, 1]], dim=1)
-        below, equal = keys[:-1] < keys[1:], keys[:-1] == keys[1:]
-        ascending = below[:, 3]
-        for column in (2, 1, 0):
-            ascending = below[:, column] | (equal[:, column] & ascending)
-        sound = (lengths >= 1).all() & (cells >= 0).all() & (pairs >= 0).all() & \
-            (lengths.sum(dtype=torch.int64) < 2 ** 31) & ascending.all() & \
-            ((cells.to(torch.int64) + lengths[:, None]).max() <= 2 ** 31)
-        if not bool(sound.item()):
-            raise ValueError(
-                "runs are not those of hit_runs: lengths must be >= 1 and sum to less than 2^31, "
-                "cells and pairs must be >= 0, and (q, cell_i, r, cell_j) must ascend strictly "
-                "from run to run (a best() permutation does not)")
-        lib = native.library()
-        workspace = workspace or ChainsWorkspace()
-        scratch, marks, slots = workspace.buffers(
-            device, count, lib.gfy_chain_runs_workspace_bytes(count))
-        # the runs of one record pair side by side, in their own order: plumbing, as the scan is
-        key, order = torch.sort((pairs[:, 0].to(torch.int64) << 31) | pairs[:, 1].to(torch.int64),
-                                stable=True)
-        edge = torch.ones(count + 1, dtype=torch.bool, device=device)
-        edge[1:-1] = key[1:] != key[:-1]
-        bounds = torch.nonzero(edge).flatten()      # waits for the device
-        status = torch.zeros(2, dtype=torch.int32, device=device)
-        front = (pairs.data_ptr(), cells.data_ptr(), lengths.data_ptr(), weights.data_ptr(), count)
-        back = (scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(device).cuda_stream)
-        native.check(lib.gfy_chain_runs_link(
-            *front, order.data_ptr(), bounds.data_ptr(), bounds.numel() - 1, max_gap, max_shift,
-            int(workspace.plain_scan), marks.data_ptr(), status[0:].data_ptr(), *back),
-            "gfy_chain_runs_link")
-        torch.cumsum(marks > 0, 0, dtype=torch.int64, out=slots)
-        total = int(slots[-1].item())   # waits for the device
-        if total < 1:
-            raise native.NativeLibraryError("gfy_chain_runs_link: no run starts a chain")
-        chains = Chains(fresh(total, 2), fresh(total, 2), fresh(total, 2), fresh(total, 2),
-                        fresh(total), fresh(total), fresh(total, dtype=torch.float32),
-                        fresh(count))
-        native.check(lib.gfy_chain_runs_emit(
-            *front, marks.data_ptr(), slots.data_ptr(), total,
-            *(out.data_ptr() for out in chains), status[1:].data_ptr(), *back),
-            "gfy_chain_runs_emit")
-        if bool(status.any().item()):
-            raise native.NativeLibraryError(
-                "gfy_chain_runs: the sorted order contradicted the sizes of the call")
-        return chains
 
 
 def _checked_parameter(value, name: str) -> float:
@@ -892,8 +340,7 @@ def _launch(call: _Call, name: str, sizer: str, leading: tuple, span: bool, work
             scratch = (workspace or AlignWorkspace()).buffer(device, need)
             native.check(getattr(lib, name)(
                 *call.arguments(), *leading, *(out.data_ptr() for out in outputs),
-                scratch.data_ptr(), scratch.numel(),
-                torch.cuda.current_stream(device).cuda_stream), name)
+                *_scratch_tail(scratch, device)), name)
     return outputs
 
 
@@ -1027,8 +474,7 @@ def _traced(call: _Call, name: str, trace, sizer: str, refusal: str, scores, sta
     slot_ops = torch.empty(int(slot_ptr[-1]), dtype=torch.uint8, device=device)
     lengths = torch.zeros(count, dtype=torch.int32, device=device)
     native.check(trace(lib, slot_ptr_dev.data_ptr(), slot_ops.data_ptr(), lengths.data_ptr(),
-                       box_rows, box_cols, scratch.data_ptr(), need,
-                       torch.cuda.current_stream(device).cuda_stream), name)
+                       box_rows, box_cols, *_scratch_tail(scratch[:need], device)), name)
     if bool((lengths < 0).any()):
         raise native.NativeLibraryError(refusal)
     return AlignedPaths(scores, starts, ends, *_compacted(slot_ops, slot_ptr_dev, slots, lengths))
@@ -1053,10 +499,7 @@ def _checked_within(within) -> bool:
 
 
 def _checked_cap(max_workspace_bytes) -> int:
-    if isinstance(max_workspace_bytes, bool) or \
-            not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 1:
-        raise ValueError("max_workspace_bytes must be a positive integer")
-    return int(max_workspace_bytes)
+    return _checked_integer(max_workspace_bytes, "max_workspace_bytes", 1)
 
 
 def _launch_global(call: _Call, within: bool, workspace) -> tuple:
@@ -1131,16 +574,12 @@ def path_cells(ops, start) -> np.ndarray:
     for the ops of one pair (``ops[offsets[p]:offsets[p + 1]]`` of ``local_paths``) from its
     ``start``, with ``-1`` on the gap side (op ``1``: ``(-1, j)``, op ``2``: ``(i, -1)``).  A pure
     function of its arguments: no device is needed."""
-    if isinstance(ops, torch.Tensor):
-        ops = ops.detach().cpu().numpy()
-    ops = np.asarray(ops)
+    ops = _host_array(ops)
     if ops.size == 0 and ops.ndim == 1:
         return np.zeros((0, 2), dtype=np.int32)
     if ops.ndim != 1 or ops.dtype.kind not in "iu" or ops.min() < 0 or ops.max() > 2:
         raise ValueError("ops must be a one-dimensional integer array of 0, 1 and 2")
-    if isinstance(start, torch.Tensor):
-        start = start.detach().cpu().numpy()
-    start = np.asarray(start)
+    start = _host_array(start)
     if start.shape != (2,) or start.dtype.kind not in "iu" or start.min() < 0:
         raise ValueError("start must be a cell (i, j) with both coordinates >= 0")
     in_a, in_b = ops != 1, ops != 2
@@ -1155,13 +594,10 @@ def top_pairs(scores, k: int, *, largest: bool) -> np.ndarray:
     order and inside a row the best column first.  ``largest`` says which end is good (True for
     cosine scores, False for L2).  Ties go to the lowest r; NaN (a record of zero rows) ranks
     behind every number.  A pure function of its arguments: no device is needed."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 1:
-        raise ValueError("k must be a positive integer")
+    k = _checked_integer(k, "k", 1)
     if not isinstance(largest, (bool, np.bool_)):
         raise ValueError("largest must be True (large scores are good) or False")
-    if isinstance(scores, torch.Tensor):
-        scores = scores.detach().cpu().numpy()
-    scores = np.asarray(scores)
+    scores = _host_array(scores)
     if scores.ndim != 2 or scores.dtype.kind != "f":
         raise ValueError("scores must be a floating-point matrix [Q, R]")
     missing = np.isnan(scores)

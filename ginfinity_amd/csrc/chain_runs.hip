@@ -24,7 +24,7 @@
 // memory (order, bounds, pred, succ, the heads, slots) is clipped or checked against the sizes of
 // the call in front of its use, a walk only ever moves forward, and what does not fit sets
 // *status.  Every store is an ordinary vector store or a vector atomic.
-#include "gfy_common.h"
+#include "seed_launch.h"
 
 namespace gfy {
 namespace {
@@ -318,11 +318,7 @@ int gfy_chain_runs_link(const int32_t* pairs, const int32_t* cells, const int32_
   p.max_gap = max_gap;
   p.max_shift = max_shift;
   p.plain = plain != 0;
-  hipStream_t s = (hipStream_t)stream;
-  GFY_CHECK_HIP(hipMemsetAsync(status, 0, 4, s));
-  k_chain_link<<<(unsigned)groups, kChainWave, 0, s>>>(p);
-  GFY_CHECK_HIP(hipGetLastError());
-  return GFY_OK;
+  return seed_launch<k_chain_link>(p, (unsigned)groups, kChainWave, stream);
 }
 
 int gfy_chain_runs_emit(const int32_t* pairs, const int32_t* cells, const int32_t* lengths,
@@ -353,10 +349,6 @@ int gfy_chain_runs_emit(const int32_t* pairs, const int32_t* cells, const int32_
   p.out_lengths = out_lengths;
   p.out_weights = out_weights;
   p.out_members = out_members;
-  hipStream_t s = (hipStream_t)stream;
-  GFY_CHECK_HIP(hipMemsetAsync(status, 0, 4, s));
   const unsigned grid = (unsigned)((runs + kChainEmitThreads - 1) / kChainEmitThreads);
-  k_chain_emit<<<grid, kChainEmitThreads, 0, s>>>(p);
-  GFY_CHECK_HIP(hipGetLastError());
-  return GFY_OK;
+  return seed_launch<k_chain_emit>(p, grid, kChainEmitThreads, stream);
 }

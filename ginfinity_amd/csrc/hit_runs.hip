@@ -19,7 +19,7 @@
 // Whatever the arrays hold, no access leaves them: every index read from memory is clipped or
 // checked against the sizes of the call in front of its use, and what does not fit sets *status.
 // Every store is an ordinary vector store or a vector atomic.
-#include "gfy_common.h"
+#include "seed_launch.h"
 
 namespace gfy {
 namespace {
@@ -214,12 +214,8 @@ int gfy_hit_runs_mark(const int64_t* offsets, int64_t n, const int32_t* indices,
                                       ptr_a, records_a, ptr_b, records_b, m, marks, status, ws,
                                       ws_bytes, p))
     return rc;
-  hipStream_t s = (hipStream_t)stream;
-  GFY_CHECK_HIP(hipMemsetAsync(status, 0, 4, s));
   const unsigned grid = (unsigned)((hits + kRunThreads - 1) / kRunThreads);
-  k_hit_runs_mark<<<grid, kRunThreads, 0, s>>>(p);
-  GFY_CHECK_HIP(hipGetLastError());
-  return GFY_OK;
+  return seed_launch<k_hit_runs_mark>(p, grid, kRunThreads, stream);
 }
 
 int gfy_hit_runs_emit(const int64_t* offsets, int64_t n, const int32_t* indices,
@@ -247,10 +243,6 @@ int gfy_hit_runs_emit(const int64_t* offsets, int64_t n, const int32_t* indices,
   p.out_cells = out_cells;
   p.out_lengths = out_lengths;
   p.out_weights = out_weights;
-  hipStream_t s = (hipStream_t)stream;
-  GFY_CHECK_HIP(hipMemsetAsync(status, 0, 4, s));
   const unsigned grid = (unsigned)((hits + kRunThreads - 1) / kRunThreads);
-  k_hit_runs_emit<<<grid, kRunThreads, 0, s>>>(p);
-  GFY_CHECK_HIP(hipGetLastError());
-  return GFY_OK;
+  return seed_launch<k_hit_runs_emit>(p, grid, kRunThreads, stream);
 }

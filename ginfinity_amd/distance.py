@@ -74,6 +74,28 @@ def _checked(rows) -> torch.Tensor:
     return rows
 
 
+def _checked_integer(value, name: str, least: int) -> int:
+    """``value`` as an int; ``ValueError`` unless it is an ``int`` or ``np.integer`` of at least
+    ``least`` (1 or 0).  A bool is no integer here, and ``np.bool_`` is neither of the two."""
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or value < least:
+        raise ValueError(f"{name} must be a {'positive' if least else 'non-negative'} integer")
+    return int(value)
+
+
+def _host_array(values) -> np.ndarray:
+    """``values`` as a host numpy array: a torch tensor from wherever it lives, anything else as
+    ``np.asarray`` takes it."""
+    if isinstance(values, torch.Tensor):
+        values = values.detach().cpu().numpy()
+    return np.asarray(values)
+
+
+def _scratch_tail(scratch, device) -> tuple:
+    """What every call of the C ABI ends with: the scratch memory, its size and the current
+    stream of ``device``."""
+    return scratch.data_ptr(), scratch.numel(), torch.cuda.current_stream(device).cuda_stream
+
+
 def _prepare(rows, device: torch.device | None) -> torch.Tensor:
     rows = _checked(rows)
     if rows.device.type != "cuda":
@@ -101,9 +123,7 @@ def pairwise(a, b=None, *, metric: str = "l2") -> torch.Tensor:
                               dtype=torch.uint8, device=a.device)
         native.check(lib.gfy_pairwise_dense(
             a.data_ptr(), n, b.data_ptr(), m, _metric(metric), out.data_ptr(),
-            scratch.data_ptr(), scratch.numel(),
-            torch.cuda.current_stream(a.device).cuda_stream),
-            "gfy_pairwise_dense")
+            *_scratch_tail(scratch, a.device)), "gfy_pairwise_dense")
     return out
 
 
@@ -134,9 +154,7 @@ class NearestWorkspace:
 
 def _checked_counts(counts) -> np.ndarray:
     """Record sizes as a non-negative int64 array; ``ValueError`` ("record counts ...") else."""
-    if isinstance(counts, torch.Tensor):
-        counts = counts.detach().cpu().numpy()
-    counts = np.asarray(counts)
+    counts = _host_array(counts)
     if counts.size == 0:
         counts = np.zeros(0, dtype=np.int64)
     if counts.ndim != 1 or counts.dtype.kind not in "iu":
@@ -239,8 +257,7 @@ def _pair_ranges(n: int, exclude_self: bool, exclude_offset: int | None,
 def _results(values, indices, scratch) -> tuple:
     """What a ``nearest`` / ``topk`` call of the C ABI ends with: the two results, the scratch
     memory and its size, the current stream of their device."""
-    return (values.data_ptr(), indices.data_ptr(), scratch.data_ptr(), scratch.numel(),
-            torch.cuda.current_stream(values.device).cuda_stream)
+    return values.data_ptr(), indices.data_ptr(), *_scratch_tail(scratch, values.device)
 
 
 def nearest(a, b=None, *, metric: str = "l2", exclude_self: bool = False,
@@ -316,10 +333,12 @@ def checked_k(k) -> int:
     """``k`` of a top-k search as an int; ``ValueError`` unless it is an integer (a numpy
     integer included, no bool) in 1..GFY_PAIRWISE_TOPK_MAX.  The one check of ``topk`` and of
     ``parallel.cross_shard_topk``."""
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or \
-            not 1 <= k <= native.GFY_PAIRWISE_TOPK_MAX:
-        raise ValueError(f"k must be an integer in 1..{native.GFY_PAIRWISE_TOPK_MAX}")
-    return int(k)
+    try:
+        if _checked_integer(k, "k", 1) <= native.GFY_PAIRWISE_TOPK_MAX:
+            return int(k)
+    except ValueError:
+        pass
+    raise ValueError(f"k must be an integer in 1..{native.GFY_PAIRWISE_TOPK_MAX}")
 
 
 def topk(a, b=None, *, k: int, metric: str = "l2", exclude_self: bool = False,
@@ -504,8 +523,7 @@ def record_best(a, b=None, *, counts_b, metric: str = "l2",
         ptr = torch.from_numpy(ptr_b.astype(np.int32)).to(a.device)
         native.check(lib.gfy_pairwise_record_best(
             a.data_ptr(), n, b.data_ptr(), m, code, ptr.data_ptr(), records, best.data_ptr(),
-            scratch.data_ptr(), scratch.numel(),
-            torch.cuda.current_stream(a.device).cuda_stream), "gfy_pairwise_record_best")
+            *_scratch_tail(scratch, a.device)), "gfy_pairwise_record_best")
     return best
 
 
@@ -543,9 +561,7 @@ def record_scores(a, b=None, *, counts_a, counts_b=None, metric: str = "l2",
     ptr_a = _record_ptr(counts_a, n, "counts_a", "a")
     ptr_b = _record_ptr(counts_b, m, "counts_b", "b")
     queries, records = ptr_a.size - 1, ptr_b.size - 1
-    if isinstance(max_workspace_bytes, bool) or \
-            not isinstance(max_workspace_bytes, (int, np.integer)) or max_workspace_bytes < 0:
-        raise ValueError("max_workspace_bytes must be a non-negative integer")
+    max_workspace_bytes = _checked_integer(max_workspace_bytes, "max_workspace_bytes", 0)
     blocks = plan_record_blocks(np.diff(ptr_a), records, max_workspace_bytes)
     a = _prepare(a, None)
     b = a if b is None else _prepare(b, a.device)
@@ -559,7 +575,6 @@ def record_scores(a, b=None, *, counts_a, counts_b=None, metric: str = "l2",
             scores[empty] = float("nan")
             return scores
         lib = native.library()
-        stream = torch.cuda.current_stream(a.device).cuda_stream
         ptr_b_dev = torch.from_numpy(ptr_b.astype(np.int32)).to(a.device)
         # every block's running sums, counted from the block's first row: one upload
         relative = [ptr_a[first:last + 1] - ptr_a[first] for first, last in blocks]
@@ -577,7 +592,7 @@ def record_scores(a, b=None, *, counts_a, counts_b=None, metric: str = "l2",
             native.check(lib.gfy_pairwise_record_scores(
                 a[row_lo:row_hi].data_ptr(), rows, b.data_ptr(), m, code,
                 ptr_a_dev[at:].data_ptr(), last - first, ptr_b_dev.data_ptr(), records,
-                scores[first:last].data_ptr(), scratch.data_ptr(), scratch.numel(), stream),
+                scores[first:last].data_ptr(), *_scratch_tail(scratch, a.device)),
                 "gfy_pairwise_record_scores")
     return scores
 
@@ -664,8 +679,7 @@ class _WithinCall:
                 *skip)
 
     def _back(self, scratch) -> tuple:
-        return (scratch.data_ptr(), scratch.numel(),
-                torch.cuda.current_stream(self.device).cuda_stream)
+        return _scratch_tail(scratch, self.device)
 
     def buffers(self):
         need = native.library().gfy_pairwise_within_workspace_bytes(self.n, self.m)
@@ -728,9 +742,8 @@ def within(a, b=None, *, threshold=None, metric: str = "l2", exclude_self: bool 
     row's segment.  ``max_hits``: a positive integer; a total above it raises ``TooManyHits``
     (which carries ``total``) before anything is allocated for the hits.  No rows, or no hit,
     returns empty ``indices`` / ``values`` without the second sweep."""
-    if max_hits is not None and (isinstance(max_hits, bool)
-                                 or not isinstance(max_hits, (int, np.integer)) or max_hits < 1):
-        raise ValueError("max_hits must be a positive integer")
+    if max_hits is not None:
+        max_hits = _checked_integer(max_hits, "max_hits", 1)
     call = _WithinCall(a, b, threshold, metric, exclude_self, exclude_ranges, exclude_records,
                        workspace)
     with torch.cuda.device(call.device):
@@ -740,7 +753,7 @@ def within(a, b=None, *, threshold=None, metric: str = "l2", exclude_self: bool 
             torch.cumsum(call.count(), 0, dtype=torch.int64, out=offsets[1:])
             total = int(offsets[-1].item())   # waits for the device
         if max_hits is not None and total > max_hits:
-            raise TooManyHits(total, int(max_hits))
+            raise TooManyHits(total, max_hits)
         if total == 0:
             return Hits(offsets, torch.empty(0, dtype=torch.int32, device=call.device),
                         torch.empty(0, dtype=torch.float32, device=call.device))

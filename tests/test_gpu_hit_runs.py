@@ -182,6 +182,26 @@ def test_min_length_filters_the_runs_of_min_length_one(boundary_hits):
     assert not keep.any()
 
 
+def test_one_workspace_on_a_large_a_small_and_a_large_input(boundary_hits):
+    """The second call uses nine entries of buffers that hold some 3,000 marks and slots of the
+    first: anything read beyond the call's own length would show there, anything left behind by
+    it in the third."""
+    from ginfinity_amd import align
+    from test_hit_runs_host import PATTERN, VALUES
+    large = (boundary_hits, COUNTS_A, COUNTS_B, oracle.runs(*boundary_hits, COUNTS_A, COUNTS_B))
+    small_hits = oracle.hits_of(PATTERN, VALUES)
+    small = (small_hits, (7,), None, oracle.runs(*small_hits, (7,)))
+    assert small_hits[1].size == 9 and boundary_hits[1].size > 2_000
+    workspace = align.RunsWorkspace()
+    for hits, counts_a, counts_b, want in (large, small, large):
+        kept = _runs(hits, counts_a=counts_a, counts_b=counts_b, workspace=workspace)
+        fresh = _runs(hits, counts_a=counts_a, counts_b=counts_b)
+        for first, second in zip(kept, fresh):
+            assert first.cpu().numpy().tobytes() == second.cpu().numpy().tobytes()
+        oracle.assert_same(kept, want)
+        assert workspace.marks.numel() >= boundary_hits[1].size     # grown once, never shrunk
+
+
 # --------------------------------------------------------------------------------------------
 # 6. behind the real searcher
 

@@ -6,6 +6,8 @@ and the three symbols declared where the others are."""
 from __future__ import annotations
 
 import ctypes
+import subprocess
+import sys
 from pathlib import Path
 
 import numpy as np
@@ -15,7 +17,7 @@ import torch
 import hit_runs_oracle as oracle
 import search_cases
 from ginfinity_amd import _native as native
-from ginfinity_amd import align, distance
+from ginfinity_amd import align, distance, seeds
 
 ROOT = Path(__file__).resolve().parents[1]
 SYMBOLS = ("gfy_hit_runs_workspace_bytes", "gfy_hit_runs_mark", "gfy_hit_runs_emit")
@@ -83,6 +85,45 @@ def test_symbols_are_declared_loaded_and_exported():
         assert name in align.__all__ and hasattr(align, name)
     assert native.ABI_VERSION == 4 == lib.gfy_abi_version()
     assert "#define GFY_ABI_VERSION 4" in header
+
+
+def test_seed_names_are_those_of_align_and_seeds_imports_no_align():
+    moved = ("band_around", "hit_cells", "hit_runs", "Runs", "RunsWorkspace", "chain_runs",
+             "Chains", "ChainsWorkspace")
+    for name in moved:
+        assert getattr(align, name) is getattr(seeds, name), name
+    assert sorted(seeds.__all__) == sorted(moved)
+    assert align.__all__ == [
+        "local_align", "local_spans", "local_paths", "global_align", "global_paths",
+        "path_cells", "AlignedPaths", "AlignWorkspace", "top_pairs", "band_around",
+        "hit_cells", "hit_runs", "Runs", "RunsWorkspace", "chain_runs", "Chains",
+        "ChainsWorkspace"]
+    assert seeds.native is align.native is native      # what the refusal tests replace
+    # a fresh interpreter; the package itself imports align, so seeds is loaded under a bare
+    # package object: what sys.modules then holds is what seeds and its own imports ask for
+    code = ("import sys, types; package = types.ModuleType('ginfinity_amd'); "
+            "package.__path__ = ['ginfinity_amd']; sys.modules['ginfinity_amd'] = package; "
+            "import ginfinity_amd.seeds; loaded = sorted(m for m in sys.modules "
+            "if m.startswith('ginfinity_amd.')); print(*loaded)")
+    done = subprocess.run([sys.executable, "-c", code], cwd=ROOT, capture_output=True, text=True)
+    assert done.returncode == 0, done.stderr
+    assert done.stdout.split() == ["ginfinity_amd._native", "ginfinity_amd.distance",
+                                   "ginfinity_amd.seeds"]
+
+
+def test_checked_integer_takes_integers_from_least_up_and_no_bool():
+    refused = (0, -1, True, np.True_, 1.5, "2", None, np.float32(2))
+    for value in refused:
+        with pytest.raises(ValueError, match="^size must be a positive integer$"):
+            distance._checked_integer(value, "size", 1)
+    for value in refused[1:]:
+        with pytest.raises(ValueError, match="^size must be a non-negative integer$"):
+            distance._checked_integer(value, "size", 0)
+    assert distance._checked_integer(0, "size", 0) == 0
+    for least in (0, 1):
+        for value, want in ((3, 3), (np.int64(3), 3), (2 ** 40, 2 ** 40)):
+            got = distance._checked_integer(value, "size", least)
+            assert type(got) is int and got == want
 
 
 def test_c_abi_refuses_bad_arguments_without_a_device():
