@@ -254,7 +254,7 @@ int gfy_pack_microbatch(const float* node_features, int feature_dim, const int32
   // points inside the micro-batch.
   offsets[1] = at;
   int32_t seen = 0, inside = 0;
-  for (int row = 0; row < 2; ++row) {
+  for (int row = 0; row < 2 && e > 0; ++row) {   // (no edges: edge_index may be NULL, no offset to it)
     const int32_t* from = edge_index + (int64_t)row * edges_total + e0;
     int32_t* to = reinterpret_cast<int32_t*>(out + at) + (int64_t)row * e;
     if (!records) {
