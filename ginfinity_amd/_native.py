@@ -167,6 +167,12 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_align_trace_band": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
                                      c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t,
                                      c_void_p]),
+    # the score and span calls inside a box: `boxes` (int32 [P][4], device) behind `bands`, which
+    # may be NULL
+    "gfy_align_local_box": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_void_p]),
+    "gfy_align_local_span_box": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
+                                         c_void_p, c_void_p, c_size_t, c_void_p]),
     "gfy_align_global": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
     "gfy_align_global_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),

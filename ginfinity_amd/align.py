@@ -8,13 +8,16 @@ picks from that ranking, without the embeddings leaving the device:
     score, end = align.local_align(rows, counts_a=counts, pairs=pairs, gap_open=1.0, gap_extend=0.25)
 
 The sparse chain needs no dense ``[Q, R]`` matrix: the radius search, its hits collapsed into
-diagonal runs, the best runs as seeds, alignment inside a band around each seed's diagonal:
+diagonal runs, the runs linked into chains, the best chains as seeds, alignment inside a band
+around each seed's diagonals and a box around its rows:
 
     hits = distance.within(rows, threshold=0.9, metric="cosine", exclude_records=counts)
     runs = align.hit_runs(hits, counts_a=counts, min_length=8)
-    best = runs.best(64)                                    # host indices: longest, then heaviest
-    paths = align.local_paths(rows, counts_a=counts, pairs=runs.pairs[best],
-                              band=runs.bands(16)[best], gap_open=1.0, gap_extend=0.25)
+    chains = align.chain_runs(runs, max_gap=8)
+    best = chains.best(64)                                  # host indices: most hits, then heaviest
+    paths = align.local_paths(rows, counts_a=counts, pairs=chains.pairs[best],
+                              band=chains.bands(4)[best], box=chains.boxes(16)[best],
+                              gap_open=1.0, gap_extend=0.25)
 
 **This is not ``ginfinity-sw``.**  The reference delegates alignment to that external package,
 which is not in its tree; it holds the names of eight scoring parameters and no formula.  The
@@ -149,17 +152,53 @@ Seeds and their bands come from ``seeds.py``, whose names this module exports: `
 makes bands from seed cells, ``hit_cells`` gives one seed per hit of ``distance.topk`` or
 ``within``, ``hit_runs`` one per maximal diagonal run of ``within`` hits, and ``chain_runs``
 links the runs that an inserted or deleted row cut apart into one band (``chains.pairs`` and
-``chains.bands(4)`` in place of the runs' in the recipe above).  Their definitions are at the
+``chains.bands(4)`` in the recipe above; ``runs.pairs`` and ``runs.bands(16)`` seed from the runs
+themselves).  Their definitions are at the
 head of that module.  The device does not do the work outside the band: a strip of 64 rows from row ``i0`` holds band cells in the
 columns ``c_lo = max(0, i0 + lo) .. c_hi = min(Lr - 1, i0 + rows - 1 + hi)`` only, a strip
 without any is skipped, and a strip takes ``c_hi - (c_lo & ~31) + rows`` steps against ``Lr + rows
 - 1`` (arithmetic, not a measurement; two records of 4,096 rows and a band of 129 diagonals:
 about 290 steps per strip against about 4,160).
 
+Alignment inside a box (one answer per chain).  A band says on which diagonals a seed lies, not
+where on them: two conserved regions of one record pair at the same offset, an unrelated linker
+between them, share their band, and a banded call returns the stronger region for both.
+``local_align``, ``local_spans`` and ``local_paths`` take ``box``: per pair four integers ``(i_lo,
+i_hi, j_lo, j_hi)``, rows of the a-record and of the b-record, 0-based inside the two records,
+both ends inclusive.  **The box is the matrix**, exactly as the band is: a cell outside the box
+is outside the matrix, ``H = 0``, ``E = F = -inf``, no origin.  Nothing else changes: the
+substitution scores, the recurrences, every rounded operation, the order that names ``end``, the
+origin rules, the tie rules of the walk and the op codes stay as they are.  ``band`` keeps its
+meaning, diagonals ``j - i`` in the records' coordinates, and combines with the box by
+intersection.  ``starts``, ``ends`` and ``path_cells`` stay in the records' coordinates.  The
+box is clipped into the record; a box that holds no cell after clipping gives what a band that
+meets no cell gives: score 0, start and end ``(-1, -1)`` and an empty path.  ``i_lo > i_hi`` or
+``j_lo > j_hi`` as given is a ``ValueError`` (the kernel refuses it like a band with ``lo >
+hi``).  It follows that
+
+* a box that covers both records gives the results of the call without a box bit for bit:
+  scores, starts, ends and ops;
+* a boxed call equals, bit for bit, the call without a box on rows ``i_lo..i_hi`` of A and
+  ``j_lo..j_hi`` of B taken as two records of their own, with the band shifted by ``-(j_lo -
+  i_lo)`` and the cells shifted back by ``(i_lo, j_lo)``;
+* enlarging a box never lowers a score, exactly, in float32 comparison (the band's argument);
+* re-scoring the ops gives ``score`` bit for bit;
+* a pair's result depends neither on the other pairs of the call nor on the run.
+
+``Runs.boxes(margin)`` and ``Chains.boxes(margin)`` make the boxes of seeds, ``margin`` rows
+around each on all four sides; with ``band=chains.bands(4)[best], box=chains.boxes(16)[best]``
+eight seeds in one target get eight answers also where they share their diagonals.  The device
+does not do the work outside the box: the strips start at the box's first row, ``ceil(box rows /
+64)`` of them, so a 150-row chain with a margin of 16 in two 4,096-row records takes 3 strips
+where a band of 9 diagonals alone meets all 64 of the a-record (arithmetic, not a measurement),
+and the carry workspace is sized by the widest box of the call.  The path needs no boxed trace:
+``start..end`` lies inside the box, so the trace on ``start..end`` walks the same path
+(include/gfy.h has the argument).
+
 Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIMUM_LENGTH_NT``),
-``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: a band on the global
-and ``within`` modes (borders that leave the band, pairs with no admissible path at all),
-band-only storage of the direction words, a span-only kernel for the global and ``within`` modes,
+``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: a band or a box on the
+global and ``within`` modes (borders that leave the band, pairs with no admissible path at all),
+band-only or box-only storage of the direction words, boxes that are not rectangles, a span-only kernel for the global and ``within`` modes,
 free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
 scores.  Measured cost: DESIGN.md §4.
 """
@@ -235,6 +274,34 @@ def _checked_band(band, count: int) -> np.ndarray | None:
     return np.ascontiguousarray(np.clip(band, -limit, limit).astype(np.int32))
 
 
+def _checked_box(box, count: int) -> np.ndarray | None:
+    """``box`` as an int32 ``[count, 4]`` host array of ``(i_lo, i_hi, j_lo, j_hi)`` with ``i_lo <=
+    i_hi`` and ``j_lo <= j_hi``, clipped into ``[-GFY_ALIGN_ROWS_MAX, GFY_ALIGN_ROWS_MAX]``; ``None``
+    stays ``None`` (no box)."""
+    if box is None:
+        return None
+    if isinstance(box, (tuple, list)) and any(isinstance(x, (bool, np.bool_)) for x in box):
+        raise ValueError("box must hold integers (i_lo, i_hi, j_lo, j_hi)")
+    box = _host_array(box)
+    if box.size == 0 and count == 0 and box.ndim in (1, 2):
+        box = np.zeros((0, 4), dtype=np.int64)
+    if box.dtype.kind not in "iu":
+        raise ValueError("box must be an integer array of shape (P, 4) or one (i_lo, i_hi, j_lo, "
+                         "j_hi)")
+    if box.shape == (4,):
+        box = np.broadcast_to(box, (count, 4))
+    if box.ndim != 2 or box.shape != (count, 4):
+        raise ValueError(f"box must be one (i_lo, i_hi, j_lo, j_hi) or an integer array of shape "
+                         f"(P, 4) = ({count}, 4), one box per pair")
+    wrong = (box[:, 0] > box[:, 1]) | (box[:, 2] > box[:, 3])
+    if np.any(wrong):
+        bad = int(np.argmax(wrong))
+        raise ValueError(f"box of pair {bad} = ({', '.join(str(int(x)) for x in box[bad])}): "
+                         "i_lo <= i_hi and j_lo <= j_hi are required")
+    limit = native.GFY_ALIGN_ROWS_MAX
+    return np.ascontiguousarray(np.clip(box, -limit, limit).astype(np.int32))
+
+
 def _checked_parameter(value, name: str) -> float:
     if value is None:
         raise ValueError(f"{name} is required: it has no default")
@@ -249,7 +316,8 @@ def _checked_parameter(value, name: str) -> float:
 
 class _Call(NamedTuple):
     """A checked call: the rows (``b`` is ``a`` where it was omitted), the records and pairs on
-    both sides and the band of every pair, or None; ``on_device`` adds the device arrays."""
+    both sides and the band and the box of every pair, or None; ``on_device`` adds the device
+    arrays."""
     a: torch.Tensor
     b: torch.Tensor
     ptr_a: np.ndarray
@@ -262,6 +330,17 @@ class _Call(NamedTuple):
     pairs_dev: torch.Tensor | None = None
     band: np.ndarray | None = None       # int32 [P, 2] of (lo, hi), clipped
     band_dev: torch.Tensor | None = None
+    box: np.ndarray | None = None        # int32 [P, 4] of (i_lo, i_hi, j_lo, j_hi), clipped
+    box_dev: torch.Tensor | None = None
+
+    @property
+    def box_columns(self) -> np.ndarray:
+        """The columns of every pair's matrix: those of its box clipped into the b-record, or
+        with no box the b-record's rows.  This is what a carry buffer has to hold."""
+        if self.box is None:
+            return self.rows_b
+        columns = np.minimum(self.box[:, 3], self.rows_b - 1) - np.maximum(self.box[:, 2], 0) + 1
+        return np.maximum(columns, 0)
 
     @property
     def empty(self) -> bool:
@@ -280,19 +359,24 @@ class _Call(NamedTuple):
                              ptr_b_dev=torch.from_numpy(self.ptr_b.astype(np.int32)).to(a.device),
                              pairs_dev=torch.from_numpy(self.pairs).to(a.device),
                              band_dev=None if self.band is None
-                             else torch.from_numpy(self.band).to(a.device))
+                             else torch.from_numpy(self.band).to(a.device),
+                             box_dev=None if self.box is None
+                             else torch.from_numpy(self.box).to(a.device))
 
     def arguments(self) -> tuple:
         """What every alignment call of the C ABI starts with, and behind it the band where the
-        call has one (the ``*_band`` symbols)."""
+        call has one (the ``*_band`` symbols).  A call with a box (the ``*_box`` symbols) has
+        both behind it, the band or NULL and then the box."""
         band = () if self.band is None else (self.band_dev.data_ptr(),)
+        if self.box is not None:
+            band = (None if self.band is None else self.band_dev.data_ptr(), self.box_dev.data_ptr())
         return (self.a.data_ptr(), self.a.shape[0], self.ptr_a_dev.data_ptr(), self.ptr_a.size - 1,
                 self.b.data_ptr(), self.b.shape[0], self.ptr_b_dev.data_ptr(), self.ptr_b.size - 1,
                 self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters, *band)
 
 
 def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-                  match_shift, band=None) -> _Call:
+                  match_shift, band=None, box=None) -> _Call:
     """Every check the alignment functions share: the call, or the ``ValueError``.  No device is
     touched."""
     gap_open = _checked_parameter(gap_open, "gap_open")
@@ -320,7 +404,7 @@ def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_s
                              f"{int(rows[bad])} rows, more than {native.GFY_ALIGN_ROWS_MAX}")
     return _Call(a, b, ptr_a, ptr_b, pairs, rows_b,
                  (match_scale, match_shift, gap_open, gap_extend),
-                 band=_checked_band(band, pairs.shape[0]))
+                 band=_checked_band(band, pairs.shape[0]), box=_checked_box(box, pairs.shape[0]))
 
 
 def _launch(call: _Call, name: str, sizer: str, leading: tuple, span: bool, workspace) -> tuple:
@@ -336,7 +420,7 @@ def _launch(call: _Call, name: str, sizer: str, leading: tuple, span: bool, work
         outputs = (scores, starts, ends) if span else (scores, ends)
         if not call.empty:
             lib = native.library()
-            need = getattr(lib, sizer)(count, int(call.rows_b.max()))
+            need = getattr(lib, sizer)(count, int(call.box_columns.max()))
             scratch = (workspace or AlignWorkspace()).buffer(device, need)
             native.check(getattr(lib, name)(
                 *call.arguments(), *leading, *(out.data_ptr() for out in outputs),
@@ -347,13 +431,13 @@ def _launch(call: _Call, name: str, sizer: str, leading: tuple, span: bool, work
 def _launch_local(call: _Call, span: bool, workspace) -> tuple:
     """``_launch`` for ``local_align`` (``span`` False) and ``local_spans`` (True)."""
     name = "gfy_align_local_span" if span else "gfy_align_local"
-    name += "_band" if call.band is not None else ""
+    name += "_box" if call.box is not None else "_band" if call.band is not None else ""
     sizer = "gfy_align_span_workspace_bytes" if span else "gfy_align_workspace_bytes"
     return _launch(call, name, sizer, (), span, workspace)
 
 
 def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                match_scale=1.0, match_shift=0.0, band=None,
+                match_scale=1.0, match_shift=0.0, band=None, box=None,
                 workspace: AlignWorkspace | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Local alignment of the record pairs ``pairs``: ``(scores float32 [P], ends int32 [P, 2])``
     on the device, exact, the ``Lq x Lr`` matrix of a pair never written (the definition is at
@@ -375,16 +459,27 @@ def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     that means, ``band_around`` makes bands from seeds), and the columns of a strip outside the
     band cost nothing.  Values are clipped into ``+-GFY_ALIGN_ROWS_MAX``, which covers any matrix.
 
+    ``box=None`` aligns the two whole records.  Otherwise ``box`` is an integer array ``[P, 4]``
+    (numpy or torch, on any device) of ``(i_lo, i_hi, j_lo, j_hi)`` per pair, or one such tuple for
+    every pair: only the cells of rows ``i_lo .. i_hi`` of the a-record and ``j_lo .. j_hi`` of the
+    b-record exist, both ends inclusive (the head of this module says what that means,
+    ``Runs.boxes`` and ``Chains.boxes`` make boxes from seeds), and the strips outside the box
+    cost nothing.  Values are clipped into ``+-GFY_ALIGN_ROWS_MAX`` and the box into the two
+    records; a box that then holds no cell gives score 0 and ``(-1, -1)``.  ``band`` keeps its
+    meaning with a box, and ``ends`` stay in the records' coordinates.
+
     Every argument error is a ``ValueError`` before a device is touched: a pair out of range, a
     record named by a pair with more than ``GFY_ALIGN_ROWS_MAX`` rows, a parameter that is not
-    finite or out of order, a band that is not integer, of another shape, or with ``lo > hi``.
+    finite or out of order, a band that is not integer, of another shape, or with ``lo > hi``,
+    a box that is not integer, of another shape, or with ``i_lo > i_hi`` or ``j_lo > j_hi``.
     ``P == 0`` returns empty tensors without a launch."""
     return _launch_local(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                       match_scale, match_shift, band).on_device(), False, workspace)
+                                       match_scale, match_shift, band, box).on_device(), False,
+                         workspace)
 
 
 def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                match_scale=1.0, match_shift=0.0, band=None,
+                match_scale=1.0, match_shift=0.0, band=None, box=None,
                 workspace: AlignWorkspace | None = None
                 ) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
     """``local_align`` with the start cell of every alignment: ``(scores float32 [P], starts
@@ -393,11 +488,13 @@ def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     (the origin rules are at the head of this module).  Scores and ends are those of
     ``local_align`` bit for bit; a score of 0 gives a start of ``(-1, -1)``.
 
-    The arguments (``band`` among them), their checks and the ``ValueError``s are those of
+    The arguments (``band`` and ``box`` among them; ``starts`` too stay in the records'
+    coordinates), their checks and the ``ValueError``s are those of
     ``local_align``; an ``AlignWorkspace`` serves both functions (this one needs twice the
     bytes)."""
     return _launch_local(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                       match_scale, match_shift, band).on_device(), True, workspace)
+                                       match_scale, match_shift, band, box).on_device(), True,
+                         workspace)
 
 
 class AlignedPaths(NamedTuple):
@@ -411,7 +508,7 @@ class AlignedPaths(NamedTuple):
 
 
 def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                match_scale=1.0, match_shift=0.0, band=None,
+                match_scale=1.0, match_shift=0.0, band=None, box=None,
                 workspace: AlignWorkspace | None = None,
                 max_workspace_bytes: int = 2 << 30) -> AlignedPaths:
     """``local_spans`` with the aligned path of every pair: ``AlignedPaths(scores, starts, ends,
@@ -433,12 +530,15 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
 
     The other arguments, their checks and the ``ValueError``s are those of ``local_spans``;
     with a ``band`` both launches get the same array (the trace shifts it into each box itself).
+    A ``box`` goes to the span launch alone: ``start..end`` lies inside it, so the trace on
+    ``start..end`` walks the same path without it.
     An ``AlignWorkspace`` serves all three functions.  ``P == 0``, or a call with no rows, returns
     empty tensors without a launch."""
     max_workspace_bytes = _checked_cap(max_workspace_bytes)
     call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-                         match_shift, band).on_device()
+                         match_shift, band, box).on_device()
     scores, starts, ends = _launch_local(call, True, workspace)
+    call = call._replace(box=None, box_dev=None)                    # the trace takes none
     with torch.cuda.device(scores.device):
         box = (ends - starts + 1).cpu().numpy().astype(np.int64)    # waits for the span launch
         box[starts.cpu().numpy()[:, 0] < 0] = 0                     # nothing aligned: no box

@@ -1,7 +1,8 @@
 // The one alignment loop of the library (semantics: include/gfy.h), shared by k_align_local
 // (align_local.hip, mode 0: score and end), k_align_span (align_span.hip, kSpan: score, start and
 // end) and k_align_trace (align_trace.hip, kTrace: the aligned path of a given box), their three
-// twins inside a band of diagonals (align_band.hip, | kBand) and the two global kernels
+// twins inside a band of diagonals (align_band.hip, | kBand), the score and span kernels inside
+// a box of rows the caller names (align_box.hip, | kBand | kBox) and the two global kernels
 // (kGlobal), as pairwise_topk.inc is shared by the top-k family.
 //
 // One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
@@ -17,7 +18,7 @@
 //     the next strip 32 columns at a time, one load ahead, two buffers in turn.
 //   * Each lane keeps its best cell and one butterfly at the end orders them.
 // What a pair needs before and after its strips stands in front of the loop: resolve_pair (the
-// pair's rows, its band, its trace box), trace_walk (kTrace: the path) and finish_pair (score, end
+// pair's rows, its band, its box), trace_walk (kTrace: the path) and finish_pair (score, end
 // and start).  align_pairs itself is the pair loop and, inline, the strip loop: stage the strip,
 // the borders of kGlobal, the carry, the 32-column blocks and the cell step; what each mode adds
 // is said at the statement that does it.  (The strip loop stays in one body on purpose: taking
@@ -55,7 +56,10 @@ static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an or
 //   kGlobal  no 0 candidate and charged borders, with the wave-uniform flag `within` the
 //            query-in-target mode; not with kSpan
 //   kBand    only the cells of a band of diagonals exist; not with kGlobal
-enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8 };
+//   kBox     only the cells of a box of rows the caller names exist, and the results are in the
+//            records' coordinates; with kBand (a call without a band has the covering one), not
+//            with kTrace or kGlobal
+enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8, kBox = 16 };
 
 // a carry entry: (H, F) of a column, and with kSpan their origins behind them
 template <bool kSpan>
@@ -84,10 +88,11 @@ __device__ __forceinline__ void record_rows(const int32_t* ptr, int index, int64
 // a pair, resolved: with ok == false lq = lr = 0 and the pair gets the refusal values
 struct AlignPair {
   bool ok;
-  int lq, lr;            // rows of A and B that are aligned (kTrace: the box's sizes)
+  int lq, lr;            // rows of A and B that are aligned (kTrace, kBox: the box's sizes)
   const f16* rows_a;
   const f16* rows_b;
-  int lo, hi;            // kBand: the band, clipped (kTrace: in the box's coordinates)
+  int lo, hi;            // kBand: the band, clipped (kTrace, kBox: in the box's coordinates)
+  int box_i, box_j;      // kBox: the box's first cell in the records' coordinates
   int64_t op_lo;         // kTrace: where the pair's slot starts
   int dir_pitch;         // kTrace: words of a row of the box
 };
@@ -103,19 +108,43 @@ struct AlignPair {
 //     records' coordinates and shifts it by start_j - start_i itself.
 //   kTrace and kGlobal: the box is rows 0 .. Lq - 1 and columns 0 .. end_j, whose top-left corner
 //     is the matrix's own.
+//   kBox: the pair has a box (i_lo, i_hi, j_lo, j_hi) of rows of the two records, both ends
+//     inclusive, read like the band from `boxes` and clipped into +-GFY_ALIGN_ROWS_MAX; i_lo > i_hi
+//     or j_lo > j_hi as given is refused like a band with lo > hi.  The box is then clipped into
+//     the records and replaces them as kTrace's box does: a-rows from i_lo, b-rows from j_lo, lq
+//     and lr the box's sizes, the band shifted by j_lo - i_lo.  A box that holds no cell leaves lq
+//     = lr = 0, the pair of a record of zero rows.  The carry has to hold the box's columns, not
+//     the record's.  A null `bands` is the covering band.
 template <unsigned kMode>
 __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs* trace,
                                              bool within, int64_t pair, AlignPair& pr) {
   constexpr bool kTrace = kMode & AlignMode::kTrace, kGlobal = kMode & AlignMode::kGlobal;
-  constexpr bool kBand = kMode & AlignMode::kBand;
+  constexpr bool kBand = kMode & AlignMode::kBand, kBox = kMode & AlignMode::kBox;
   const int q = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair]);
   const int rec = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair + 1]);
   bool ok = (uint32_t)q < (uint32_t)p.records_a && (uint32_t)rec < (uint32_t)p.records_b;
   int64_t a_lo = 0, a_hi = 0, b_lo = 0, b_hi = 0;
   int lo = 0, hi = 0;   // kBand: the band, from here on clipped
+  int i_lo = 0, i_hi = 0, j_lo = 0, j_hi = 0;   // kBox: the box, from here on clipped
+  if constexpr (kBox) {
+    constexpr int most = GFY_ALIGN_ROWS_MAX;
+    i_lo = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair]);
+    i_hi = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 1]);
+    j_lo = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 2]);
+    j_hi = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 3]);
+    ok = ok && i_lo <= i_hi && j_lo <= j_hi;
+    i_lo = i_lo < -most ? -most : i_lo > most ? most : i_lo;
+    i_hi = i_hi < -most ? -most : i_hi > most ? most : i_hi;
+    j_lo = j_lo < -most ? -most : j_lo > most ? most : j_lo;
+    j_hi = j_hi < -most ? -most : j_hi > most ? most : j_hi;
+  }
   if constexpr (kBand) {
-    lo = __builtin_amdgcn_readfirstlane(p.bands[2 * pair]);
-    hi = __builtin_amdgcn_readfirstlane(p.bands[2 * pair + 1]);
+    if (!kBox || p.bands != nullptr) {
+      lo = __builtin_amdgcn_readfirstlane(p.bands[2 * pair]);
+      hi = __builtin_amdgcn_readfirstlane(p.bands[2 * pair + 1]);
+    } else {   // kBox, a call without a band: the covering one
+      lo = -GFY_ALIGN_ROWS_MAX, hi = GFY_ALIGN_ROWS_MAX;
+    }
     ok = ok && lo <= hi;
     lo = lo < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : lo > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : lo;
     hi = hi < -GFY_ALIGN_ROWS_MAX ? -GFY_ALIGN_ROWS_MAX : hi > GFY_ALIGN_ROWS_MAX ? GFY_ALIGN_ROWS_MAX : hi;
@@ -125,8 +154,27 @@ __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs
     record_rows(p.ptr_b, rec, p.m, b_lo, b_hi);
   }
   ok = ok && a_hi - a_lo <= GFY_ALIGN_ROWS_MAX && b_hi - b_lo <= GFY_ALIGN_ROWS_MAX &&
-       (kTrace || b_hi - b_lo <= p.cap);
+       (kTrace || kBox || b_hi - b_lo <= p.cap);
   pr.op_lo = 0;
+  pr.box_i = 0, pr.box_j = 0;
+  if constexpr (kBox) {
+    // the box inside the records; a record of more than GFY_ALIGN_ROWS_MAX rows is refused above
+    const int full_q = ok ? (int)(a_hi - a_lo) : 0, full_r = ok ? (int)(b_hi - b_lo) : 0;
+    i_lo = i_lo < 0 ? 0 : i_lo;
+    j_lo = j_lo < 0 ? 0 : j_lo;
+    i_hi = i_hi > full_q - 1 ? full_q - 1 : i_hi;
+    j_hi = j_hi > full_r - 1 ? full_r - 1 : j_hi;
+    const bool box = ok && i_lo <= i_hi && j_lo <= j_hi;   // it holds a cell
+    const int box_rows = box ? i_hi - i_lo + 1 : 0, box_cols = box ? j_hi - j_lo + 1 : 0;
+    ok = ok && box_cols <= p.cap;
+    pr.box_i = box ? i_lo : 0, pr.box_j = box ? j_lo : 0;
+    lo -= pr.box_j - pr.box_i;   // the band in the box's coordinates
+    hi -= pr.box_j - pr.box_i;
+    a_lo += pr.box_i;
+    b_lo += pr.box_j;
+    a_hi = a_lo + box_rows;
+    b_hi = b_lo + box_cols;
+  }
   if constexpr (kTrace) {
     // only a box that the span call (kGlobal: gfy_align_global) can have named, that fits the
     // wave's region and whose path fits the slot is followed; (-1, -1) is the empty alignment
@@ -265,13 +313,15 @@ __device__ __forceinline__ void trace_walk(int lane, char* ring, const uint32_t*
 
 // The pair's result.  kGlobal: the last cell, or (within) the first best cell of the last row:
 // one lane holds either.  Otherwise one butterfly orders the lanes' best cells by (score
-// descending, i ascending, j ascending), and with kSpan the origin goes along.
+// descending, i ascending, j ascending), and with kSpan the origin goes along.  kBox: the cells
+// of a positive score go back into the records' coordinates; (-1, -1) and (-2, -2) stay.
 template <unsigned kMode>
 __device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const AlignPair& pr,
                                             bool within, int64_t pair, int strips, float h_last,
                                             float best, int best_i, int best_j,
                                             uint32_t best_o, int32_t* out_start) {
   constexpr bool kSpan = kMode & AlignMode::kSpan, kGlobal = kMode & AlignMode::kGlobal;
+  constexpr bool kBox = kMode & AlignMode::kBox;
   const bool ok = pr.ok;
   if constexpr (kGlobal) {
     const int owner = (pr.lq - 1) & (kStrip - 1);
@@ -299,19 +349,29 @@ __device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const 
     }
     if (lane == 0) {
       const bool none = !(best > 0.f);
+      int start_i = 0, start_j = 0;   // kSpan: the origin
+      if constexpr (kSpan) {
+        start_i = (int)(best_o >> kOriginBits);
+        start_j = (int)(best_o & ((1u << kOriginBits) - 1));
+      }
+      if constexpr (kBox) {
+        best_i += pr.box_i, best_j += pr.box_j;
+        start_i += pr.box_i, start_j += pr.box_j;
+      }
       p.out_score[pair] = ok ? (none ? 0.f : best) : __builtin_nanf("");
       p.out_end[2 * pair] = ok ? (none ? -1 : best_i) : -2;
       p.out_end[2 * pair + 1] = ok ? (none ? -1 : best_j) : -2;
       if constexpr (kSpan) {
-        out_start[2 * pair] = ok ? (none ? -1 : (int)(best_o >> kOriginBits)) : -2;
-        out_start[2 * pair + 1] = ok ? (none ? -1 : (int)(best_o & ((1u << kOriginBits) - 1))) : -2;
+        out_start[2 * pair] = ok ? (none ? -1 : start_i) : -2;
+        out_start[2 * pair + 1] = ok ? (none ? -1 : start_j) : -2;
       }
     }
   }
 }
 
 // out_start ([P][2]) is written with kSpan, and with kTrace and kGlobal together; trace is read
-// with kTrace alone, within (wave-uniform) with kGlobal alone, p.bands with kBand alone
+// with kTrace alone, within (wave-uniform) with kGlobal alone, p.bands with kBand alone, p.boxes
+// with kBox alone
 template <unsigned kMode>
 __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start,
                                             const TraceArgs* trace = nullptr,
@@ -321,6 +381,8 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
   static_assert(!(kSpan && kTrace), "the trace runs on the plain (H, F) carry");
   static_assert(!(kSpan && kGlobal), "a global alignment starts at the matrix's corner");
   static_assert(!(kBand && kGlobal), "a band on the global modes: borders that leave the band");
+  static_assert(!(kMode & AlignMode::kBox) || (kBand && !kTrace && !kGlobal),
+                "a box comes with a band and serves the score and span kernels");
   using Carry = AlignCarry<kSpan>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;

@@ -1135,6 +1135,60 @@ int gfy_align_trace_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t
 }
 #undef GFY_REQUIRE_BANDS
 
+// The score and span calls inside a box of rows per pair: the banded call's checks in its order,
+// with `boxes` named first and `bands` free to be NULL (no band), and the boxed kernels
+// (align_box.hip).
+#define GFY_REQUIRE_BOXES(who, plain)                                                          \
+  GFY_REQUIRE(boxes, GFY_ERR_INVALID,                                                          \
+              who ": boxes is NULL (int32 [P][4] of (i_lo, i_hi, j_lo, j_hi) rows in device "  \
+                  "memory; " plain " is the call without a box)")
+
+int gfy_align_local_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                        const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                        const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                        float gap_open, float gap_extend, const int32_t* bands,
+                        const int32_t* boxes, float* out_score, int32_t* out_end, void* ws,
+                        size_t ws_bytes, void* stream) {
+  clear_error();
+  GFY_REQUIRE_BOXES("gfy_align_local_box", "gfy_align_local_band");
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_local_box",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
+    return rc;
+  call.bands = bands;
+  call.boxes = boxes;
+  call.out_score = out_score;
+  call.out_end = out_end;
+  return launch_align_local_box(call, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                             const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                             const int32_t* pairs, int64_t P, float match_scale,
+                             float match_shift, float gap_open, float gap_extend,
+                             const int32_t* bands, const int32_t* boxes, float* out_score,
+                             int32_t* out_start, int32_t* out_end, void* ws, size_t ws_bytes,
+                             void* stream) {
+  clear_error();
+  GFY_REQUIRE_BOXES("gfy_align_local_span_box", "gfy_align_local_span_band");
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_local_span_box",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{out_score, "out_score"}, {out_start, "out_start"}, {out_end, "out_end"}}, ws, &call))
+    return rc;
+  call.bands = bands;
+  call.boxes = boxes;
+  call.out_score = out_score;
+  call.out_end = out_end;
+  return launch_align_local_span_box(call, out_start, ws, ws_bytes, (hipStream_t)stream);
+}
+#undef GFY_REQUIRE_BOXES
+
 int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                      const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                      const int32_t* pairs, int64_t P, float match_scale, float match_shift,

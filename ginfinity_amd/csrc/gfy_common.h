@@ -384,6 +384,8 @@ struct AlignArgs {
   void* carry;            // [waves of the grid][2][cap] entries of a strip's last row
   int cap;                // columns a carry buffer holds
   const int32_t* bands;   // [P][2] (lo, hi) diagonals j - i per pair: the *_band kernels alone
+  const int32_t* boxes;   // [P][4] (i_lo, i_hi, j_lo, j_hi) rows per pair: the *_box kernels alone,
+                          // for which a null bands is the covering band
 };
 
 // what k_align_trace takes next to AlignArgs (whose out_score / out_end it leaves alone, and whose
@@ -428,6 +430,12 @@ int launch_align_local_span_band(const AlignArgs& call, int32_t* out_start, void
                                  size_t ws_bytes, hipStream_t s);
 int launch_align_trace_band(const AlignArgs& call, const TraceArgs& trace, int64_t max_box_rows,
                             int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
+// align_box.hip: the score and span calls inside a box of rows per pair (call.boxes) and, where
+// call.bands is not null, a band; the workspaces are those of the unbanded calls with the widest
+// box's columns for max_rows_b
+int launch_align_local_box(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
+int launch_align_local_span_box(const AlignArgs& call, int32_t* out_start, void* ws,
+                                size_t ws_bytes, hipStream_t s);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS

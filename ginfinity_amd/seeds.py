@@ -9,7 +9,8 @@ The sparse search chain is ``distance.within`` -> ``hit_runs`` -> ``chain_runs``
     chains = align.chain_runs(runs, max_gap=8)              # max_shift defaults to max_gap
     best = chains.best(64)                                  # most hits, then heaviest
     paths = align.local_paths(rows, counts_a=counts, pairs=chains.pairs[best],
-                              band=chains.bands(4)[best], gap_open=1.0, gap_extend=0.25)
+                              band=chains.bands(4)[best], box=chains.boxes(16)[best],
+                              gap_open=1.0, gap_extend=0.25)
 
 The definitions below stand here once in Python; include/gfy.h has them as the C contract.
 
@@ -80,7 +81,9 @@ added in float64 in chain order, each addition one rounded operation, rounded to
 ``members`` int32 ``[S]``, the chain of every run: a chain's runs are ``flatnonzero(members ==
 c)``, ascending.  ``Chains.bands(half_width)`` gives ``(diagonals[:, 0] - half_width,
 diagonals[:, 1] + half_width)`` as an int32 host array, which is what ``local_align`` /
-``local_spans`` / ``local_paths`` take with ``pairs=chains.pairs``; ``Chains.best(k)`` is the rule
+``local_spans`` / ``local_paths`` take with ``pairs=chains.pairs``, and ``Chains.boxes(margin)``
+gives ``(starts_i - margin, ends_i + margin, starts_j - margin, ends_j + margin)``, what they take
+as ``box`` (``Runs.boxes(margin)`` is the same from a run's head and tail); ``Chains.best(k)`` is the rule
 of ``Runs.best``: lengths descending, then weights descending with NaN last, then position.
 
 Consequences.  ``max_gap=0`` links nothing, because two such runs would have been one maximal
@@ -114,6 +117,17 @@ def _widened(lo, hi, half_width) -> np.ndarray:
     limit = np.iinfo(np.int32)
     return np.clip(np.stack([lo - width, hi + width], axis=1), limit.min,
                    limit.max).astype(np.int32)
+
+
+def _boxed(first, last, margin) -> np.ndarray:
+    """The boxes ``(first_i - margin, last_i + margin, first_j - margin, last_j + margin)`` of
+    int64 cells ``first <= last`` (``[P, 2]`` each) as an int32 ``[P, 4]`` array.  ``margin`` is a
+    non-negative integer, cut like a ``half_width`` at twice ``GFY_ALIGN_ROWS_MAX``; the bounds are
+    clipped into int32 and not into any record: the call that takes the boxes does that."""
+    margin = min(_checked_integer(margin, "margin", 0), 2 * native.GFY_ALIGN_ROWS_MAX)
+    limit = np.iinfo(np.int32)
+    return np.clip(np.stack([first[:, 0] - margin, last[:, 0] + margin, first[:, 1] - margin,
+                             last[:, 1] + margin], axis=1), limit.min, limit.max).astype(np.int32)
 
 
 def band_around(seeds, half_width: int) -> np.ndarray:
@@ -206,6 +220,17 @@ class Runs(NamedTuple):
         ``local_align`` / ``local_spans`` / ``local_paths`` with ``pairs=self.pairs``."""
         return band_around(self.cells, half_width)
 
+    def boxes(self, margin: int) -> np.ndarray:
+        """The box of every run with ``margin`` rows around it on all four sides, as an int32
+        ``[S, 4]`` host array of ``(i_lo, i_hi, j_lo, j_hi)``: from the head ``cells`` minus
+        ``margin`` to the tail ``cells + lengths - 1`` plus ``margin``, for the ``box`` of
+        ``local_align`` / ``local_spans`` / ``local_paths`` with ``pairs=self.pairs``.  ``margin``
+        is a non-negative integer, cut like ``half_width``.  A pure function of ``cells`` and
+        ``lengths``; the boxes are not clipped at the records' ends, the call does that."""
+        cells = _host_array(self.cells).astype(np.int64).reshape(-1, 2)
+        lengths = _host_array(self.lengths).astype(np.int64).reshape(-1, 1)
+        return _boxed(cells, cells + lengths - 1, margin)
+
     def best(self, k: int) -> np.ndarray:
         """The indices (int64 host array, at most ``k``) of the ``k`` runs that come first in the
         order ``lengths`` descending, then ``weights`` descending, then position ascending; a NaN
@@ -238,6 +263,17 @@ class Chains(NamedTuple):
         at twice ``GFY_ALIGN_ROWS_MAX``, wider than any matrix."""
         diagonals = _host_array(self.diagonals).astype(np.int64).reshape(-1, 2)
         return _widened(diagonals[:, 0], diagonals[:, 1], half_width)
+
+    def boxes(self, margin: int) -> np.ndarray:
+        """The box of every chain with ``margin`` rows around it on all four sides, as an int32
+        ``[K, 4]`` host array of ``(starts_i - margin, ends_i + margin, starts_j - margin, ends_j +
+        margin)``, for the ``box`` of ``local_align`` / ``local_spans`` / ``local_paths`` next to
+        ``band=self.bands(...)``: two chains on the same diagonals of one record pair then get two
+        answers.  ``margin`` is a non-negative integer, cut like ``half_width``.  A pure function
+        of ``starts`` and ``ends``; the boxes are not clipped at the records' ends, the call does
+        that."""
+        return _boxed(_host_array(self.starts).astype(np.int64).reshape(-1, 2),
+                      _host_array(self.ends).astype(np.int64).reshape(-1, 2), margin)
 
     def best(self, k: int) -> np.ndarray:
         """The indices (int64 host array, at most ``k``) of the ``k`` chains that come first by

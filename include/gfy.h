@@ -861,6 +861,76 @@ int gfy_align_trace_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t
                          int32_t* out_len /* [P] */, int64_t max_box_rows, int64_t max_box_cols,
                          void* workspace, size_t workspace_bytes, void* stream);
 
+/* Local alignment INSIDE A BOX of rows per pair: gfy_align_local_band and
+ * gfy_align_local_span_band with `boxes` (int32 [P][4], device memory) behind `bands`.  A band
+ * says on which diagonals a seed lies, not where on them: two conserved regions of one record
+ * pair at the same offset share their band, and a banded call returns the stronger one for
+ * both.  A box around each region gives each its own answer, and costs the box's strips only.
+ *   Box         boxes[p] = (i_lo, i_hi, j_lo, j_hi), i_lo <= i_hi and j_lo <= j_hi: rows of the
+ *               a-record and of the b-record, 0-based inside the two records, both ends
+ *               inclusive.  THE BOX IS THE MATRIX, exactly as the band is: a cell outside the box
+ *               is outside the matrix in the sense of gfy_align_local, H = 0, E = F = -inf, no
+ *               origin.  Nothing else changes: s[i][j], the recurrences, every rounded operation,
+ *               the order that names out_end, the origin rules, the tie rules of the walk and the
+ *               op codes are those of the calls without a box.
+ *   Band        bands keeps its meaning, diagonals d = j - i in the RECORDS' coordinates, and
+ *               combines with the box by intersection.  bands may be NULL: no band.
+ *   Results     out_start and out_end stay in the records' coordinates.
+ *   Clipping    the kernel reads the four values per pair like the band, clips them into
+ *               [-GFY_ALIGN_ROWS_MAX, GFY_ALIGN_ROWS_MAX] and then into the two records.  A box
+ *               that holds no cell after clipping gives what a band that meets no cell gives:
+ *               score 0, start and end (-1, -1).  A pair with i_lo > i_hi or j_lo > j_hi as given
+ *               is refused like a band with lo > hi: NaN and (-2, -2).
+ *   It follows  - a box that covers both records gives the results of the call without a box,
+ *                 bit for bit.
+ *               - a boxed call equals, bit for bit, the call without a box on rows i_lo..i_hi of
+ *                 A and j_lo..j_hi of B taken as two records of their own, under the band (lo -
+ *                 (j_lo - i_lo), hi - (j_lo - i_lo)), with (i_lo, j_lo) added to its cells (the
+ *                 clipped box's i_lo and j_lo).  That is how the kernel does it.
+ *               - every operation is monotone and an outside cell holds the least values a cell
+ *                 can have, so enlarging a box never lowers a pair's score, exactly, in fp32
+ *                 comparison.
+ *               - re-scoring the ops gives out_score bit for bit.
+ *               - a pair's result depends neither on the other pairs of the call nor on the run.
+ *   Trace       there is no boxed trace call and none is needed.  The span property holds inside
+ *               the box as it does inside the band: what the box lacks counts as 0 or -inf, so
+ *               the recurrences on start..end alone reach out_score at end.  start..end lies
+ *               inside the caller's box, so every cell of start..end is a cell of the boxed
+ *               matrix, and gfy_align_trace_band (gfy_align_trace where bands is NULL) on
+ *               start..end, with the band in the records' coordinates, walks the same path.
+ *   Work        the strips follow the box, not the record: ceil(box rows / 64) strips of at most
+ *               box columns + 63 steps, the first at the box's first row.  A 150-row chain
+ *               with a margin of 16 in two 4,096-row records under a band of 9 diagonals: a box
+ *               of 182 rows, 3 strips (4 from a margin of 22 on) against the 64 strips of the
+ *               a-record that the band meets (arithmetic from the loop bounds; no time is
+ *               claimed).
+ *   Workspace   the sizers of the calls without a box, gfy_align_workspace_bytes and
+ *               gfy_align_span_workspace_bytes, with the widest box's columns (after clipping)
+ *               for max_rows_b; a pair whose box has more columns than the workspace holds is
+ *               refused: NaN and (-2, -2).
+ *   Arguments, checks and error codes are those of the banded counterpart but for bands; a NULL
+ *   boxes is GFY_ERR_INVALID, named, with a pointer to the call without a box.  Out of scope: a
+ *   box on gfy_align_global and gfy_align_global_trace, band-only or box-only storage of the
+ *   direction words, boxes that are not rectangles.
+ *   Cost: DESIGN.md §4.                                                                        */
+int gfy_align_local_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                        const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                        const int32_t* pairs /* [P][2] device */, int64_t P,
+                        float match_scale, float match_shift, float gap_open, float gap_extend,
+                        const int32_t* bands /* [P][2] device, or NULL */,
+                        const int32_t* boxes /* [P][4] device */,
+                        float* out_score /* [P] */, int32_t* out_end /* [P][2] */,
+                        void* workspace, size_t workspace_bytes, void* stream);
+int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                             const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                             const int32_t* pairs /* [P][2] device */, int64_t P,
+                             float match_scale, float match_shift, float gap_open,
+                             float gap_extend, const int32_t* bands /* [P][2] device, or NULL */,
+                             const int32_t* boxes /* [P][4] device */,
+                             float* out_score /* [P] */, int32_t* out_start /* [P][2] */,
+                             int32_t* out_end /* [P][2] */,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* GLOBAL and QUERY-IN-TARGET alignment of record pairs: the recurrences of gfy_align_local with
  * charged borders and without the 0 candidate.  within = 0 aligns both records end to end
  * (Needleman-Wunsch with affine gaps): unrelated flanks are charged for, not ignored.  within = 1

@@ -38,7 +38,19 @@ kernel's loop bounds (arithmetic, counted on the host); with ``--spans`` the sam
 itself, whose diagonal 0 is the path).  Random records share nothing: the band changes which
 alignment is found, and the times say what the band saves, not what it finds.
 
+``--box MARGIN`` is a measurement of its own (nothing above runs): ``--records`` records of 4,096
+rows on either side, b-record r random but for a copy of 150 rows of a-record r at another
+place, and ``--pairs`` pairs ``(r, r)``.  Every pair is aligned inside the band of 9 diagonals
+around its region's diagonal, once without a box and once inside the box of the region and
+``MARGIN`` rows around it (what ``Chains.bands(4)`` and ``Chains.boxes(MARGIN)`` give for such a
+region), by ``local_align``, ``local_spans`` and ``local_paths``.  The document (default
+profiles/align_box_bench.json) holds the medians, ``boxed_over_banded`` (their ratio), the strips
+of both by the kernel's loop bounds (arithmetic, counted on the host) and how many of the boxed
+alignments are the banded ones bit for bit (the region is the best alignment of its band, so
+all of them should be).
+
     python tools/bench_align.py --pairs 20000
+    python tools/bench_align.py --pairs 2000 --records 64 --box 16
     python tools/bench_align.py --pairs 20000 --spans
     python tools/bench_align.py --pairs 20000 --band 129 --spans --paths
     python tools/bench_align.py --pairs 20000 --global --within
@@ -69,6 +81,9 @@ SPAN_SOURCES = ("align_local.inc", "align_span.hip")     # --spans: the shared b
 PATH_SOURCES = ("align_local.inc", "align_span.hip", "align_trace.hip")   # --paths
 GLOBAL_SOURCES = ("align_local.inc", "align_global.hip")                  # --global, --within
 BAND_SOURCES = ("align_local.inc", "align_band.hip")                      # --band
+BOX_SOURCES = ("align_local.inc", "align_band.hip", "align_box.hip")      # --box
+BOX_RECORD_ROWS = 4096            # --box: rows of every record
+BOX_REGION_ROWS = 150             # --box: rows of the region a pair shares
 
 
 def _commit() -> str | None:
@@ -145,6 +160,88 @@ def _band_against_plain(call, plain_mid: float, pairs: int, repeats: int, warmup
     return {"seconds": _span(seconds), "pairs_per_s": pairs / mid, "over_unbanded": mid / plain_mid}
 
 
+def _measured_arguments() -> list[str]:
+    """The command line without ``--out``: where the document goes is no part of what was measured."""
+    kept, skip = [], False
+    for word in sys.argv[1:]:
+        if skip or word.startswith("--out="):
+            skip = False
+        elif word == "--out":
+            skip = True
+        else:
+            kept.append(word)
+    return kept
+
+
+def _box_bench(args) -> dict:
+    """``--box``: the same pairs banded, without and with the box of the planted region."""
+    rng = np.random.default_rng(0)
+    rows, region, margin = BOX_RECORD_ROWS, BOX_REGION_ROWS, args.box
+    counts = np.full(args.records, rows)
+    a = synthetic.unit_rows(0, args.records * rows)
+    b = synthetic.unit_rows(1, args.records * rows)
+    at = rng.integers(0, rows - region + 1, size=(args.records, 2))     # (i, j) of every region
+    for r, (i, j) in enumerate(at.tolist()):
+        b[r * rows + j:r * rows + j + region] = a[r * rows + i:r * rows + i + region]
+    a, b = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
+    record = rng.integers(0, args.records, size=args.pairs)
+    pairs = torch.from_numpy(np.stack([record, record], axis=1).astype(np.int32))
+    first, last = at[record], at[record] + region - 1
+    diagonal = first[:, 1] - first[:, 0]
+    bands = np.stack([diagonal - 4, diagonal + 4], axis=1).astype(np.int32)
+    boxes = np.stack([first[:, 0] - margin, last[:, 0] + margin, first[:, 1] - margin,
+                      last[:, 1] + margin], axis=1).astype(np.int32)
+    parameters = dict(gap_open=1.0, gap_extend=0.25, match_scale=1.0, match_shift=-0.3)
+    keeper = align.AlignWorkspace()
+    common = dict(counts_a=counts, counts_b=counts, pairs=pairs, band=torch.from_numpy(bands),
+                  workspace=keeper, **parameters)
+    box_dev = torch.from_numpy(boxes)
+    # strips by the loop bounds: a band of 9 diagonals meets every strip of the a-record whose
+    # rows have a column, a box has ceil(its rows inside the record / 64)
+    i0 = np.arange(0, rows, 64)[None, :]
+    banded_strips = int(((np.maximum(i0 + bands[:, :1], 0) <=
+                          np.minimum(i0 + 63 + bands[:, 1:], rows - 1))).sum())
+    box_rows = np.minimum(boxes[:, 1], rows - 1) - np.maximum(boxes[:, 0], 0) + 1
+    boxed_strips = int(((box_rows + 63) // 64).sum())
+    source = ROOT / "ginfinity_amd" / "csrc"
+    result = {"metric": "local alignment of pairs of 4,096-row records that share a 150-row region, "
+                        "inside a band of 9 diagonals, without and with the region's box",
+              "pairs": args.pairs, "records": args.records, "record_rows": rows,
+              "region_rows": region, "margin": margin, "band_diagonals": 9,
+              "parameters": parameters, "host": platform.node(),
+              "utc": datetime.datetime.now(datetime.timezone.utc).isoformat(timespec="seconds"),
+              "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
+              "torch": torch.__version__, "commit": args.commit or _commit(),
+              "source_sha256": {name: hashlib.sha256((source / name).read_bytes()).hexdigest()
+                                for name in BOX_SOURCES},
+              "command": "python tools/bench_align.py " + " ".join(_measured_arguments()),
+              "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
+              "timed": "the whole call: host checks, the upload of pairs, bands and boxes, the "
+                       "launches",
+              "strips": {"banded": banded_strips, "boxed": boxed_strips,
+                         "counted": "on the host from the loop bounds, not measured"}}
+    for name in ("local_align", "local_spans", "local_paths"):
+        function = getattr(align, name)
+        banded = _timed(lambda: function(a, b, **common), args.repeats, args.warmup)
+        boxed = _timed(lambda: function(a, b, box=box_dev, **common), args.repeats, args.warmup)
+        banded_mid, boxed_mid = statistics.median(banded), statistics.median(boxed)
+        result[name] = {"banded_seconds": _span(banded), "boxed_seconds": _span(boxed),
+                        "banded_pairs_per_s": args.pairs / banded_mid,
+                        "boxed_pairs_per_s": args.pairs / boxed_mid,
+                        "boxed_over_banded": boxed_mid / banded_mid}
+        print(f"{name}: banded {banded_mid:.4f} s, boxed {boxed_mid:.4f} s = "
+              f"{boxed_mid / banded_mid:.3f} x; strips {boxed_strips} of {banded_strips} (counted)",
+              file=sys.stderr, flush=True)
+    one = align.local_spans(a, b, **common)
+    two = align.local_spans(a, b, box=box_dev, **common)
+    same = torch.stack([(x.reshape(args.pairs, -1) == y.reshape(args.pairs, -1)).all(dim=1)
+                        for x, y in zip(one, two)]).all(dim=0)
+    result["boxed_equal_to_banded"] = int(same.sum())
+    result["region_inside_the_alignment"] = int(
+        ((two[1].cpu().numpy() <= first) & (two[2].cpu().numpy() >= last)).all(axis=1).sum())
+    return result
+
+
 def _host_gotoh(S: np.ndarray, go: np.float32, ge: np.float32) -> np.float32:
     """max H of the recurrences in numpy float32, one anti-diagonal at a time."""
     lq, lr = S.shape
@@ -184,13 +281,30 @@ def main() -> None:
                         help="time the same pairs inside a band of W diagonals around diagonal 0 "
                              "next to the calls without a band (with --spans and --paths: those "
                              "calls too)")
+    parser.add_argument("--box", type=int, default=None, metavar="MARGIN",
+                        help="a measurement of its own: pairs of 4,096-row records that share a "
+                             "150-row region, banded, without and with the region's box of MARGIN "
+                             "rows around it (default output profiles/align_box_bench.json)")
     parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
-    parser.add_argument("--out", default=str(ROOT / "profiles" / "align_bench.json"))
+    parser.add_argument("--out", default=None,
+                        help="default profiles/align_bench.json, with --box "
+                             "profiles/align_box_bench.json")
     args = parser.parse_args()
     if args.pairs < 1 or args.records < 1:
         parser.error("--pairs, --records: positive")
     if args.band < 0:
         parser.error("--band: a positive number of diagonals")
+    if args.box is not None and args.box < 0:
+        parser.error("--box: a margin of 0 rows or more")
+    if args.out is None:
+        args.out = str(ROOT / "profiles" / ("align_bench.json" if args.box is None
+                                            else "align_box_bench.json"))
+    if args.box is not None:
+        result = _box_bench(args)
+        Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+        print(json.dumps(result))
+        return
     rng = np.random.default_rng(0)
     counts = rng.integers(200, 601, size=args.records)
     ptr = np.concatenate(([0], np.cumsum(counts)))
