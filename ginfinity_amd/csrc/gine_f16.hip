@@ -405,12 +405,6 @@ __global__ __launch_bounds__(256) void k_copy_rows_f16(const f16* __restrict__ s
 }  // namespace
 }  // namespace gfy
 #else
-int persistent_grid(int num_tiles) {
-  int g = num_tiles < 256 ? num_tiles : 256;
-  g = (g + 7) & ~7;  // whole XCD rounds (TileWalk divides by 8)
-  return g < 8 ? 8 : g;
-}
-
 }  // namespace
 
 #ifdef GFY_STAMPS
@@ -439,9 +433,19 @@ static size_t h_buffer_bytes(int64_t rows) {
 static size_t plan_bytes(int64_t rows) {
   return align_up((size_t)((rows + kLTile - 1) / kLTile) * kPlanBytes, 256);
 }
+// ... plus, for the parity tap of one layer (gfy_debug_layer), the tapped rows
+static size_t tap_bytes(int64_t rows) { return align_up((size_t)rows * kMlp * sizeof(f16), 256); }
+// the one cut of that workspace, [ha][hb][plans][taps]; base == nullptr: the sizes alone
+struct EncodeWorkspace { f16 *ha, *hb; char* plans; f16* taps; size_t bytes; };
+static EncodeWorkspace cut_workspace(void* base, int64_t rows, bool with_taps) {
+  const size_t h = h_buffer_bytes(rows), plans = 2 * h, taps = plans + plan_bytes(rows);
+  const auto at = [&](size_t off) { return base ? (char*)base + off : nullptr; };
+  return {(f16*)at(0), (f16*)at(h), at(plans), with_taps ? (f16*)at(taps) : nullptr,
+          taps + (with_taps ? tap_bytes(rows) : 0)};
+}
 static int64_t padded_rows(int64_t n) { return (n + kLTile - 1) / kLTile * kLTile; }
 size_t encode_f16_workspace_bytes(int64_t n, int64_t /*e*/) {
-  return 2 * h_buffer_bytes(padded_rows(n)) + plan_bytes(padded_rows(n));
+  return cut_workspace(nullptr, padded_rows(n), false).bytes;
 }
 
 // > 64 KB of dynamic LDS needs an opt-in per kernel and per DEVICE (a process may drive
@@ -487,66 +491,193 @@ struct CooInput {
   uint8_t* typ;
 };
 
-// One shard or a batch (ShardTable), CSR given (row_ptr / col / typ: one shard only) or finished
-// here from the counting kernel's table (coo).
-static int encode_f16_on(const gfy_encoder* enc, const ShardTable& shards, const int32_t* row_ptr,
-                         const int32_t* col, const uint8_t* typ, const CooInput* coo,
-                         int out_dtype, int normalise, int tap_stage, void* ws, size_t ws_bytes,
+// the CSR the layer kernels read, and the rows they may look up in row_ptr (the direct path of
+// hub tiles): the caller's CSR has n + 1 entries, the one finished here covers the padded rows
+// as well
+struct Csr { const int32_t *row_ptr, *col; const uint8_t* typ; int limit; };
+
+// The set-up launch: the input Linear into ha and, except before a stage-0 tap, the tile plans
+// (with a COO input the rest of the CSR as well).
+static void launch_setup(const gfy_encoder* enc, const ShardTable& shards, const Csr& csr,
+                         const CooInput* coo, int tap_stage, f16* ha, char* plans,
                          hipStream_t s) {
+  const int layer_tiles = shards.total_tiles();
+  const int64_t blocks = (shards.total_rows() * 16 + 255) / 256;
+  const int linear_blocks = (int)(blocks > 2048 ? 2048 : blocks);
+  if (tap_stage == 0)
+    k_input_linear_f16<<<linear_blocks, 256, 0, s>>>(shards, enc->f16.w_in, enc->f16.b_in, ha);
+  else if (coo && coo->records) {   // COO -> plans by record ranges (csr_records.inc): no counting launch
+#ifdef GFY_DIAG_SETUP_SPLIT   // diagnostic: GFY_DIAG_SETUP=1 range workgroups only, 2 Linear only (wrong results)
+    static const int diag = getenv("GFY_DIAG_SETUP") ? atoi(getenv("GFY_DIAG_SETUP")) : 0;
+    const int ranges = diag == 2 ? 0 : coo->records->range_base[shards.shards];
+    static const int diag_linear = getenv("GFY_DIAG_LINEAR") ? atoi(getenv("GFY_DIAG_LINEAR")) : 0;
+    const int linear = diag == 1 ? 0 : diag_linear > 0 ? diag_linear : linear_blocks;
+#else
+    const int ranges = coo->records->range_base[shards.shards], linear = linear_blocks;
+#endif
+    // the Linear's workgroups have the range workgroups' size: the same number of threads
+#define GFY_LAUNCH_SETUP_REC(ROWS, THREADS)                                                 \
+  k_encode_setup_rec<ROWS, THREADS>                                                         \
+      <<<ranges + (linear * 256 + THREADS - 1) / THREADS, THREADS, 0, s>>>(                 \
+          shards, *coo->records, enc->f16.w_in, enc->f16.b_in, ha, coo->row_ptr, coo->col,  \
+          coo->typ, coo->scratch.perm, plans, ranges, enc->edge_dim)
+    if (coo->records->range_rows == kRecRowsLarge) GFY_LAUNCH_SETUP_REC(kRecRowsLarge, kRecThreadsLarge);
+    else if (coo->records->range_rows == kRecRowsSmall) GFY_LAUNCH_SETUP_REC(kRecRowsSmall, kRecThreadsSmall);
+    else GFY_LAUNCH_SETUP_REC(kRecRowsLone, kRecThreadsLone);
+#undef GFY_LAUNCH_SETUP_REC
+  }
+  else if (coo)   // + last CSR stage (scan_free: row offsets included) + tile plans
+    (coo->scan_free ? k_encode_setup_coo<false> : k_encode_setup_coo<true>)
+        <<<layer_tiles + linear_blocks, 256, 0, s>>>(
+            shards, enc->f16.w_in, enc->f16.b_in, ha, coo->scratch, coo->row_ptr, coo->col,
+            coo->typ, plans, layer_tiles, enc->edge_dim);
+  else            // + tile plans
+    k_encode_setup<<<layer_tiles + linear_blocks, 256, 0, s>>>(
+        shards, enc->f16.w_in, enc->f16.b_in, ha, csr.row_ptr, csr.col, csr.typ, plans,
+        layer_tiles, enc->edge_dim);
+}
+
+// the grid of a persistent layer kernel and the rounds its workgroups run: one tile per wave,
+// XCD x = workgroups x, x + 8, ..., at most per_cu workgroups resident on each CU
+struct RoundsGrid { int grid, rounds; };
+static RoundsGrid rounds_grid(int layer_tiles, int cus, int waves, int per_cu) {
+  const int tiles_per_xcd = (layer_tiles + 7) / 8;
+  const int wanted = (tiles_per_xcd + waves - 1) / waves, per_xcd = per_cu * (cus / 8);
+  return {8 * (wanted < per_xcd ? wanted : per_xcd), (wanted + per_xcd - 1) / per_xcd};
+}
+
+// Which layer kernel: a launch that gives every CU more than one round of eight tiles (a
+// large micro-batch, or a batch of shards) runs the persistent-rounds kernel
+// (gine_layer_q.inc: the fills of round r + 1 under the arithmetic of round r, CUs de-phased
+// by a start stagger) and the stand-alone head behind it; a single-round launch (the 60,000-
+// node shard by itself) runs the round-2 kernel, whose last launch carries the head.
+// GFY_OPT_LAYER_KERNEL (`option`) forces either (A/B runs, parity tests).
+static int choose_layer_kernel(int option, int edge_dim, int layer_tiles, int cus) {
+  const bool several_rounds = rounds_grid(layer_tiles, cus, kLWaves, 1).rounds > 1;
+  // ... and, where the edge table leaves its last rows free for the plan-head slots, as two
+  // 4-wave workgroups per CU with the weights streamed through a window (gine_layer_w.inc)
+  const bool window_ok = edge_dim <= kWMaxEdgeTypes;
+  // ... or as three 4-wave workgroups per CU of <= 168 registers (gine_layer_x.inc)
+  if (window_ok && option == 5) return 5;
+  if (window_ok && (option == 4 || (option < 0 && several_rounds))) return 4;
+  return option >= 3 || (option < 0 && several_rounds) ? 3 : 1;
+}
+
+// grid, start stagger and s_setprio levels of layer kernel 1 / 3 / 4 / 5; `stagger` and
+// `priority` >= 0 (GFY_OPT_STAGGER, GFY_OPT_PRIORITY) replace the kernel's own
+struct LayerLaunch { int kernel, grid, stagger, priority; };
+static LayerLaunch layer_launch(int kernel, int layer_tiles, int cus, int stagger, int priority) {
+  const auto or_own = [](int option, int own) { return option >= 0 ? option : own; };
+  RoundsGrid g;
+  switch (kernel) {
+    case 5:   // residents 0, 1, 2 at levels 0, 1, 2
+      g = rounds_grid(layer_tiles, cus, kXWaves, 3);
+      return {5, g.grid, or_own(stagger, g.rounds >= 2 ? 250 : 0), or_own(priority, 0x24)};
+    case 4:   // the second workgroup of a CU multiplies at s_setprio 1 (gine_layer_w.inc)
+      g = rounds_grid(layer_tiles, cus, kWWaves, 2);
+      return {4, g.grid, or_own(stagger, g.rounds >= 3 ? 250 : 0), or_own(priority, 4)};
+    case 3:
+      // start offsets only pay once a workgroup runs several rounds (the offset costs up to one
+      // round at the start of the launch)
+      g = rounds_grid(layer_tiles, cus, kLWaves, 1);
+      return {3, g.grid, or_own(stagger, g.rounds >= 3 ? 500 : 0), 0};
+    default:
+      // one tile per wave, eight per workgroup, XCD x = workgroups x, x + 8, ... (gine_layer.inc)
+      return {1, 8 * ((layer_tiles + 8 * kLWaves - 1) / (8 * kLWaves)), 0, 0};
+  }
+}
+
+// f(std::bool_constant<a>, std::bool_constant<b>): two runtime flags as template arguments
+template <class F>
+static void with_flags(bool a, bool b, F&& f) {
+  if (a && b) f(std::true_type{}, std::true_type{});
+  else if (a) f(std::true_type{}, std::false_type{});
+  else if (b) f(std::false_type{}, std::true_type{});
+  else f(std::false_type{}, std::false_type{});
+}
+
+// One layer, h_in -> h_out: the launch site of each kernel family.  `head_out` is read by the
+// kHead instantiations, `tap` / `taps` by the kTap ones (which the round-2 kernel has not).
+template <bool kResidual, bool kTap, bool kHead>
+static void launch_layer(const LayerLaunch& how, const LayerF16& p, const f16* h_in, f16* h_out,
+                         const Csr& csr, const char* plans, int layer_tiles, int32_t* spent,
+                         unsigned long long* span, int tap, f16* taps, const HeadOut& head_out,
+                         hipStream_t s) {
+  const HeadOut out = kHead ? head_out : HeadOut{};
+  if (how.kernel == 5)
+    k_gine_layer_x<kResidual, kTap, kHead><<<how.grid, kXThreads, kXLdsBytes, s>>>(
+        p, h_in, h_out, csr.row_ptr, csr.col, csr.typ, plans, csr.limit, layer_tiles,
+        how.stagger, how.priority, spent, span, tap, taps, out);
+  else if (how.kernel == 4)
+    k_gine_layer_w<kResidual, kTap, kHead><<<how.grid, kWThreads, kWLdsBytes, s>>>(
+        p, h_in, h_out, csr.row_ptr, csr.col, csr.typ, plans, csr.limit, layer_tiles,
+        how.stagger, how.priority, spent, span, tap, taps, out);
+  else if (how.kernel == 3)
+    k_gine_layer_q<kResidual, kTap, kHead><<<how.grid, kLThreads, kQLdsBytes, s>>>(
+        p, h_in, h_out, csr.row_ptr, csr.col, csr.typ, plans, csr.limit, layer_tiles,
+        how.stagger, spent, span, tap, taps, out);
+  else if constexpr (!kTap)
+    k_gine_layer_f16<kResidual, kHead><<<how.grid, kLThreads, kLdsBytes, s>>>(
+        p, h_in, h_out, csr.row_ptr, csr.col, csr.typ, plans, csr.limit, layer_tiles,
+        head_out.head, head_out.shards, head_out.normalise, spent, span);
+}
+
+// `groups` of 16 channels between stored and natural channel order
+static void copy_rows(const f16* from, f16* to, int64_t groups, hipStream_t s) {
+  const int g = (int)((groups + 255) / 256);
+  k_copy_rows_f16<<<g > 2048 ? 2048 : g, 256, 0, s>>>(from, to, groups);
+}
+
+static int persistent_grid(int num_tiles) {
+  int g = num_tiles < 256 ? num_tiles : 256;
+  g = (g + 7) & ~7;  // whole XCD rounds (TileWalk divides by 8)
+  return g < 8 ? 8 : g;
+}
+
+// What follows the layers (of kernel `layer_kernel`) on the final hidden rows `h`, unless the
+// last layer launch ran the head: the tap's copy, or a stand-alone head.
+static void launch_tail(const gfy_encoder* enc, const ShardTable& shards, const f16* h,
+                        int out_dtype, int normalise, int tap_stage, int layer_kernel,
+                        hipStream_t s) {
+  const int layer_tiles = shards.total_tiles();
+  if (tap_stage >= 0) {   // one shard: its rows, natural channel order
+    copy_rows(h, (f16*)shards.out[0], (int64_t)shards.nodes[0] * 8, s);
+  } else if (out_dtype == GFY_F16 && layer_kernel != 1) {
+    k_head_d<<<rounds_grid(layer_tiles, enc->cus, kLWaves, 1).grid, kLThreads, kLdsBytes, s>>>(
+        enc->f16.head, h, shards, layer_tiles, normalise);
+  } else {   // the tiled stand-alone head, shard by shard (f32 / f64 output, A/B runs)
+    for (int k = 0; k < shards.shards; ++k) {
+      const int n = shards.nodes[k];
+      const int num_tiles = (n + kTile - 1) / kTile;
+      const f16* rows_k = h + (size_t)shards.tile_base[k] * kLTile * kHidden;
+      const auto head = [&](auto* out) {
+        k_head_f16<<<persistent_grid(num_tiles), kThreads, 2 * kTile * 256, s>>>(
+            enc->f16.head, rows_k, shards.out_rows[k], out, n, num_tiles, normalise);
+      };
+      switch (out_dtype) {
+        case GFY_F16: head((f16*)shards.out[k]); break;
+        case GFY_F32: head((float*)shards.out[k]); break;
+        default: head((double*)shards.out[k]);
+      }
+    }
+  }
+}
+
+// One shard or a batch (ShardTable), CSR given (one shard only) or finished here, into `csr`,
+// from the counting kernel's table (coo).
+static int encode_f16_on(const gfy_encoder* enc, const ShardTable& shards, const Csr& csr,
+                         const CooInput* coo, int out_dtype, int normalise, int tap_stage,
+                         void* ws, size_t ws_bytes, hipStream_t s) {
   const int64_t rows = shards.total_rows();
-  const size_t need = 2 * h_buffer_bytes(rows) + plan_bytes(rows);
-  GFY_REQUIRE(ws_bytes >= need, GFY_ERR_WORKSPACE,
-              "gfy_encode: workspace %zu < required %zu", ws_bytes, need);
+  const EncodeWorkspace w = cut_workspace(ws, rows, false);
+  GFY_REQUIRE(ws_bytes >= w.bytes, GFY_ERR_WORKSPACE,
+              "gfy_encode: workspace %zu < required %zu", ws_bytes, w.bytes);
   GFY_REQUIRE(rows <= (int64_t)1 << 24, GFY_ERR_UNSUPPORTED,
               "gfy_encode: fp16 path addresses rows with 32-bit byte offsets; "
               "split micro-batches / batches above 16,777,216 nodes (got %lld)", (long long)rows);
-  f16* ha = (f16*)ws;
-  f16* hb = (f16*)((char*)ws + h_buffer_bytes(rows));
-  char* plans = (char*)ws + 2 * h_buffer_bytes(rows);
   const int layer_tiles = shards.total_tiles();
-  // one tile per wave, eight per workgroup, XCD x = workgroups x, x + 8, ... (gine_layer.inc)
-  const int layer_grid = 8 * ((layer_tiles + 8 * kLWaves - 1) / (8 * kLWaves));
-
-  const int64_t items = rows * 16;
   enc->mark(s, 0);
-  {
-    const int64_t blocks = (items + 255) / 256;
-    const int linear_blocks = (int)(blocks > 2048 ? 2048 : blocks);
-    if (tap_stage == 0)
-      k_input_linear_f16<<<linear_blocks, 256, 0, s>>>(shards, enc->f16.w_in, enc->f16.b_in, ha);
-    else if (coo && coo->records) {   // COO -> plans by record ranges (csr_records.inc): no counting launch
-#ifdef GFY_DIAG_SETUP_SPLIT   // diagnostic: GFY_DIAG_SETUP=1 range workgroups only, 2 Linear only (wrong results)
-      static const int diag = getenv("GFY_DIAG_SETUP") ? atoi(getenv("GFY_DIAG_SETUP")) : 0;
-      const int ranges = diag == 2 ? 0 : coo->records->range_base[shards.shards];
-      static const int diag_linear = getenv("GFY_DIAG_LINEAR") ? atoi(getenv("GFY_DIAG_LINEAR")) : 0;
-      const int linear = diag == 1 ? 0 : diag_linear > 0 ? diag_linear : linear_blocks;
-#else
-      const int ranges = coo->records->range_base[shards.shards], linear = linear_blocks;
-#endif
-      // the Linear's workgroups have the range workgroups' size: the same number of threads
-#define GFY_LAUNCH_SETUP_REC(ROWS, THREADS)                                                   \
-  k_encode_setup_rec<ROWS, THREADS>                                                           \
-      <<<ranges + (linear * 256 + THREADS - 1) / THREADS, THREADS, 0, s>>>(                   \
-          shards, *coo->records, enc->f16.w_in, enc->f16.b_in, ha, coo->row_ptr, coo->col,    \
-          coo->typ, coo->scratch.perm, plans, ranges, enc->edge_dim)
-      if (coo->records->range_rows == kRecRowsLarge) GFY_LAUNCH_SETUP_REC(kRecRowsLarge, kRecThreadsLarge);
-      else if (coo->records->range_rows == kRecRowsSmall) GFY_LAUNCH_SETUP_REC(kRecRowsSmall, kRecThreadsSmall);
-      else GFY_LAUNCH_SETUP_REC(kRecRowsLone, kRecThreadsLone);
-#undef GFY_LAUNCH_SETUP_REC
-    }
-    else if (coo && coo->scan_free)   // + last CSR stage (row offsets included) + tile plans
-      k_encode_setup_coo<false><<<layer_tiles + linear_blocks, 256, 0, s>>>(
-          shards, enc->f16.w_in, enc->f16.b_in, ha, coo->scratch, coo->row_ptr, coo->col,
-          coo->typ, plans, layer_tiles, enc->edge_dim);
-    else if (coo)
-      k_encode_setup_coo<true><<<layer_tiles + linear_blocks, 256, 0, s>>>(
-          shards, enc->f16.w_in, enc->f16.b_in, ha, coo->scratch, coo->row_ptr, coo->col,
-          coo->typ, plans, layer_tiles, enc->edge_dim);
-    else            // + tile plans
-      k_encode_setup<<<layer_tiles + linear_blocks, 256, 0, s>>>(
-          shards, enc->f16.w_in, enc->f16.b_in, ha, row_ptr, col, typ, plans, layer_tiles,
-          enc->edge_dim);
-  }
+  launch_setup(enc, shards, csr, coo, tap_stage, w.ha, w.plans, s);
   enc->mark(s, 1);
   const int stop = tap_stage >= 0 ? tap_stage : enc->layers;
   if (enc->timing == 3) {   // start = +inf, end = 0 for every layer launch
@@ -554,140 +685,31 @@ static int encode_f16_on(const gfy_encoder* enc, const ShardTable& shards, const
         ~0ull, 0, ~0ull, 0, ~0ull, 0, ~0ull, 0, ~0ull, 0, ~0ull, 0, ~0ull, 0, ~0ull, 0};
     GFY_CHECK_HIP(hipMemcpyAsync(enc->device_spans, init, sizeof init, hipMemcpyHostToDevice, s));
   }
-  // Which layer kernel: a launch that gives every CU more than one round of eight tiles (a
-  // large micro-batch, or a batch of shards) runs the persistent-rounds kernel
-  // (gine_layer_q.inc: the fills of round r + 1 under the arithmetic of round r, CUs de-phased
-  // by a start stagger) and the stand-alone head behind it; a single-round launch (the 60,000-
-  // node shard by itself) runs the round-2 kernel, whose last launch carries the head.
-  // GFY_OPT_LAYER_KERNEL forces either (A/B runs, parity tests).
-  const int tiles_per_xcd = (layer_tiles + 7) / 8;
-  const int wanted = (tiles_per_xcd + kLWaves - 1) / kLWaves, per_xcd = enc->cus / 8;
-  const int p_grid = 8 * (wanted < per_xcd ? wanted : per_xcd);
-  const int rounds = (wanted + per_xcd - 1) / per_xcd;
-  // ... and, where the edge table leaves its last rows free for the plan-head slots, as two
-  // 4-wave workgroups per CU with the weights streamed through a window (gine_layer_w.inc)
-  const bool window_ok = enc->edge_dim <= kWMaxEdgeTypes;
-  // ... or as three 4-wave workgroups per CU of <= 168 registers (gine_layer_x.inc)
-  const bool triple = window_ok && enc->layer_kernel == 5;
-  const bool windowed =
-      !triple && window_ok && (enc->layer_kernel == 4 || (enc->layer_kernel < 0 && rounds > 1));
-  const bool persistent =
-      !triple && !windowed && (enc->layer_kernel >= 3 || (enc->layer_kernel < 0 && rounds > 1));
-  const int w_wanted = (tiles_per_xcd + kWWaves - 1) / kWWaves, w_per_xcd = 2 * per_xcd;
-  const int w_grid = 8 * (w_wanted < w_per_xcd ? w_wanted : w_per_xcd);
-  const int w_rounds = (w_wanted + w_per_xcd - 1) / w_per_xcd;
-  const int x_wanted = (tiles_per_xcd + kXWaves - 1) / kXWaves, x_per_xcd = 3 * per_xcd;
-  const int x_grid = 8 * (x_wanted < x_per_xcd ? x_wanted : x_per_xcd);
-  const int x_rounds = (x_wanted + x_per_xcd - 1) / x_per_xcd;
-  const int x_stagger = enc->stagger >= 0 ? enc->stagger : x_rounds >= 2 ? 250 : 0;
-  const int x_priority = enc->priority >= 0 ? enc->priority : 0x24;   // residents 0, 1, 2 at levels 0, 1, 2
-  enc->last_layer_kernel = triple ? 5 : windowed ? 4 : persistent ? 3 : 1;
-  const int w_stagger = enc->stagger >= 0 ? enc->stagger : w_rounds >= 3 ? 250 : 0;
-  // the second workgroup of a CU multiplies at s_setprio 1 (gine_layer_w.inc)
-  const int w_priority = enc->priority >= 0 ? enc->priority : 4;
-  // start offsets only pay once a workgroup runs several rounds (the offset costs up to one
-  // round at the start of the launch)
-  const int stagger = enc->stagger >= 0 ? enc->stagger : rounds >= 3 ? 500 : 0;
+  enc->last_layer_kernel =
+      choose_layer_kernel(enc->layer_kernel, enc->edge_dim, layer_tiles, enc->cus);
+  const LayerLaunch how =
+      layer_launch(enc->last_layer_kernel, layer_tiles, enc->cus, enc->stagger, enc->priority);
   // fp16 output of a full encode: the round-2 kernel's last launch runs the head as well
   // (GFY_OPT_SEPARATE_HEAD keeps the stand-alone head kernel: A/B runs and parity tests)
   const bool fuse_head =
       tap_stage < 0 && out_dtype == GFY_F16 && stop > 0 && !enc->separate_head;
-  const int32_t* const csr_rows = coo ? coo->row_ptr : row_ptr;
-  const int32_t* const csr_col = coo ? coo->col : col;
-  const uint8_t* const csr_typ = coo ? coo->typ : typ;
-  // rows the layer kernels may look up in row_ptr (the direct path of hub tiles): the caller's
-  // CSR has n + 1 entries, the one finished here covers the padded rows as well
-  const int csr_limit = coo ? (int)rows : shards.nodes[0];
-  HeadOut no_out{};
   const HeadOut head_out{enc->f16.head, shards, normalise};
+  f16 *ha = w.ha, *hb = w.hb;
   for (int l = 0; l < stop; ++l) {
     int32_t* const spent =
         coo && l == 0 && coo->scan_free && !coo->records ? coo->scratch.tile_sum : nullptr;
     unsigned long long* const span = enc->timing == 3 ? enc->device_spans + 2 * l : nullptr;
     const bool with_head = fuse_head && l == stop - 1;
-#define GFY_LAUNCH_LAYER(RES, HEAD)                                                          \
-  k_gine_layer_f16<RES, HEAD><<<layer_grid, kLThreads, kLdsBytes, s>>>(                      \
-      enc->f16.layer[l], ha, hb, csr_rows, csr_col, csr_typ, plans, csr_limit, layer_tiles,  \
-      enc->f16.head, shards, normalise, spent, span)
-#define GFY_LAUNCH_ROUNDS(RES, HEAD)                                                         \
-  k_gine_layer_q<RES, false, HEAD><<<p_grid, kLThreads, kQLdsBytes, s>>>(                    \
-      enc->f16.layer[l], ha, hb, csr_rows, csr_col, csr_typ, plans, csr_limit, layer_tiles,  \
-      stagger, spent, span, kTapNone, nullptr, HEAD ? head_out : no_out)
-#define GFY_LAUNCH_WINDOW(RES, HEAD)                                                         \
-  k_gine_layer_w<RES, false, HEAD><<<w_grid, kWThreads, kWLdsBytes, s>>>(                    \
-      enc->f16.layer[l], ha, hb, csr_rows, csr_col, csr_typ, plans, csr_limit, layer_tiles,  \
-      w_stagger, w_priority, spent, span, kTapNone, nullptr,         \
-      HEAD ? head_out : no_out)
-#define GFY_LAUNCH_TRIPLE(RES, HEAD)                                                         \
-  k_gine_layer_x<RES, false, HEAD><<<x_grid, kXThreads, kXLdsBytes, s>>>(                    \
-      enc->f16.layer[l], ha, hb, csr_rows, csr_col, csr_typ, plans, csr_limit, layer_tiles,  \
-      x_stagger, x_priority, spent, span, kTapNone, nullptr, HEAD ? head_out : no_out)
-    if (triple && enc->residual && with_head) GFY_LAUNCH_TRIPLE(true, true);
-    else if (triple && enc->residual) GFY_LAUNCH_TRIPLE(true, false);
-    else if (triple && with_head) GFY_LAUNCH_TRIPLE(false, true);
-    else if (triple) GFY_LAUNCH_TRIPLE(false, false);
-    else if (windowed && enc->residual && with_head) GFY_LAUNCH_WINDOW(true, true);
-    else if (windowed && enc->residual) GFY_LAUNCH_WINDOW(true, false);
-    else if (windowed && with_head) GFY_LAUNCH_WINDOW(false, true);
-    else if (windowed) GFY_LAUNCH_WINDOW(false, false);
-    else if (persistent && enc->residual && with_head) GFY_LAUNCH_ROUNDS(true, true);
-    else if (persistent && enc->residual) GFY_LAUNCH_ROUNDS(true, false);
-    else if (persistent && with_head) GFY_LAUNCH_ROUNDS(false, true);
-    else if (persistent) GFY_LAUNCH_ROUNDS(false, false);
-    else if (enc->residual && with_head) GFY_LAUNCH_LAYER(true, true);
-    else if (enc->residual) GFY_LAUNCH_LAYER(true, false);
-    else if (with_head) GFY_LAUNCH_LAYER(false, true);
-    else GFY_LAUNCH_LAYER(false, false);
-#undef GFY_LAUNCH_LAYER
-#undef GFY_LAUNCH_ROUNDS
-#undef GFY_LAUNCH_WINDOW
-#undef GFY_LAUNCH_TRIPLE
-    f16* sw = ha;
-    ha = hb;
-    hb = sw;
+    with_flags(enc->residual, with_head, [&](auto residual, auto head) {
+      launch_layer<decltype(residual)::value, false, decltype(head)::value>(
+          how, enc->f16.layer[l], ha, hb, csr, w.plans, layer_tiles, spent, span, kTapNone,
+          nullptr, head_out, s);
+    });
+    std::swap(ha, hb);
     enc->mark(s, 2 + l);
   }
-  if (tap_stage >= 0) {   // one shard: its rows, natural channel order
-    const int64_t groups = (int64_t)shards.nodes[0] * 8;
-    int g = (int)((groups + 255) / 256);
-    k_copy_rows_f16<<<g > 2048 ? 2048 : g, 256, 0, s>>>(ha, (f16*)shards.out[0], groups);
-    GFY_CHECK_HIP(hipGetLastError());
-    return GFY_OK;
-  }
-  if (fuse_head) {
-    enc->mark(s, 2 + enc->layers);
-    GFY_CHECK_HIP(hipGetLastError());
-    return GFY_OK;
-  }
-  if (out_dtype == GFY_F16 && (persistent || windowed || triple)) {
-    k_head_d<<<p_grid, kLThreads, kLdsBytes, s>>>(enc->f16.head, ha, shards, layer_tiles,
-                                                  normalise);
-  } else {   // the tiled stand-alone head, shard by shard (f32 / f64 output, A/B runs)
-    const int head_lds = 2 * kTile * 256;
-    for (int k = 0; k < shards.shards; ++k) {
-      const int n = shards.nodes[k];
-      const int num_tiles = (n + kTile - 1) / kTile;
-      const int grid = persistent_grid(num_tiles);
-      const f16* rows_k = ha + (size_t)shards.tile_base[k] * kLTile * kHidden;
-      switch (out_dtype) {
-        case GFY_F16:
-          k_head_f16<f16><<<grid, kThreads, head_lds, s>>>(
-              enc->f16.head, rows_k, shards.out_rows[k], (f16*)shards.out[k], n, num_tiles,
-              normalise);
-          break;
-        case GFY_F32:
-          k_head_f16<float><<<grid, kThreads, head_lds, s>>>(
-              enc->f16.head, rows_k, shards.out_rows[k], (float*)shards.out[k], n, num_tiles,
-              normalise);
-          break;
-        default:
-          k_head_f16<double><<<grid, kThreads, head_lds, s>>>(
-              enc->f16.head, rows_k, shards.out_rows[k], (double*)shards.out[k], n, num_tiles,
-              normalise);
-      }
-    }
-  }
-  enc->mark(s, 2 + enc->layers);
+  if (!fuse_head) launch_tail(enc, shards, ha, out_dtype, normalise, tap_stage, how.kernel, s);
+  if (tap_stage < 0) enc->mark(s, 2 + enc->layers);
   GFY_CHECK_HIP(hipGetLastError());
   return GFY_OK;
 }
@@ -699,8 +721,8 @@ int launch_encode_f16(const gfy_encoder* enc, const float* x,
                       int normalise, int tap_stage, void* ws, size_t ws_bytes,
                       hipStream_t s) {
   const ShardTable shards = single_shard(x, nullptr, nullptr, n, e, out_rows, out);
-  return encode_f16_on(enc, shards, row_ptr, col, typ, nullptr, out_dtype, normalise, tap_stage,
-                       ws, ws_bytes, s);
+  return encode_f16_on(enc, shards, Csr{row_ptr, col, typ, (int)n}, nullptr, out_dtype, normalise,
+                       tap_stage, ws, ws_bytes, s);
 }
 
 // workspace of gfy_encode_coo / gfy_encode_coo_batch over `rows` padded rows and `e` edges:
@@ -726,7 +748,7 @@ static CooWorkspace carve_coo(void* base, int64_t rows, int64_t e) {
   w.row_ptr = (int32_t*)take((size_t)(rows + 1) * 4);
   w.col = (int32_t*)take((size_t)(e > 0 ? e : 1) * 4);
   w.typ = (uint8_t*)take((size_t)(e > 0 ? e : 1));
-  w.encode_bytes = 2 * h_buffer_bytes(rows) + plan_bytes(rows);
+  w.encode_bytes = cut_workspace(nullptr, rows, false).bytes;
   w.encode = take(w.encode_bytes);
   w.bytes = off;
   return w;
@@ -756,15 +778,13 @@ int launch_encode_coo_f16(const gfy_encoder* enc, const ShardTable& shards,
                                              shards.total_rows(), s))
       return rc;
   const CooInput coo{w.scratch, records, scan_free, w.row_ptr, w.col, w.typ};
-  return encode_f16_on(enc, shards, nullptr, nullptr, nullptr, &coo, out_dtype, normalise, -1,
-                       w.encode, w.encode_bytes, s);
+  return encode_f16_on(enc, shards, Csr{w.row_ptr, w.col, w.typ, (int)shards.total_rows()}, &coo,
+                       out_dtype, normalise, -1, w.encode, w.encode_bytes, s);
 }
 
 // ---- parity tap of one layer (gfy_debug_layer) ----------------------------------------------
-static size_t tap_bytes(int64_t rows) { return align_up((size_t)rows * kMlp * sizeof(f16), 256); }
 size_t debug_layer_f16_workspace_bytes(int64_t n) {
-  const int64_t rows = padded_rows(n);
-  return 2 * h_buffer_bytes(rows) + plan_bytes(rows) + tap_bytes(rows);
+  return cut_workspace(nullptr, padded_rows(n), true).bytes;
 }
 
 int launch_debug_layer_f16(const gfy_encoder* enc, int layer, const void* hidden_in,
@@ -775,50 +795,27 @@ int launch_debug_layer_f16(const gfy_encoder* enc, int layer, const void* hidden
               "gfy_debug_layer: only the residual architecture has a tap instantiation");
   const ShardTable shards = single_shard(nullptr, nullptr, nullptr, n, e, nullptr, out);
   const int64_t rows = shards.total_rows();
-  GFY_REQUIRE(ws_bytes >= debug_layer_f16_workspace_bytes(n), GFY_ERR_WORKSPACE,
-              "gfy_debug_layer: workspace %zu < required %zu", ws_bytes,
-              debug_layer_f16_workspace_bytes(n));
-  f16* ha = (f16*)ws;
-  f16* hb = (f16*)((char*)ws + h_buffer_bytes(rows));
-  char* plans = (char*)ws + 2 * h_buffer_bytes(rows);
-  f16* taps = (f16*)(plans + plan_bytes(rows));
+  const EncodeWorkspace w = cut_workspace(ws, rows, true);
+  GFY_REQUIRE(ws_bytes >= w.bytes, GFY_ERR_WORKSPACE,
+              "gfy_debug_layer: workspace %zu < required %zu", ws_bytes, w.bytes);
   const int layer_tiles = shards.total_tiles();
-  auto copy_rows = [&](const f16* from, f16* to, int64_t groups) {
-    const int g = (int)((groups + 255) / 256);
-    k_copy_rows_f16<<<g > 2048 ? 2048 : g, 256, 0, s>>>(from, to, groups);
-  };
-  GFY_CHECK_HIP(hipMemsetAsync(ha, 0, h_buffer_bytes(rows), s));   // padding rows: zeros
-  copy_rows((const f16*)hidden_in, ha, n * 8);                      // natural -> stored order
-  k_encode_setup<<<layer_tiles, 256, 0, s>>>(shards, enc->f16.w_in, enc->f16.b_in, ha, row_ptr,
-                                             col, typ, plans, layer_tiles,
+  GFY_CHECK_HIP(hipMemsetAsync(w.ha, 0, h_buffer_bytes(rows), s));   // padding rows: zeros
+  copy_rows((const f16*)hidden_in, w.ha, n * 8, s);                 // natural -> stored order
+  k_encode_setup<<<layer_tiles, 256, 0, s>>>(shards, enc->f16.w_in, enc->f16.b_in, w.ha, row_ptr,
+                                             col, typ, w.plans, layer_tiles,
                                              enc->edge_dim);   // plans only
   // the tap instantiation of the layer kernel the encoder is set to (GFY_OPT_LAYER_KERNEL 4 / 5:
   // windowed / three workgroups per CU, where the edge table leaves room for their plan-head
-  // slots; anything else: persistent rounds, whose pipelines the one-round kernel shares)
-  const int tiles_per_xcd = (layer_tiles + 7) / 8;
-  const int per_xcd = enc->cus / 8;
+  // slots; anything else: persistent rounds, whose pipelines the one-round kernel shares),
+  // without start stagger or priorities
   const bool slots_ok = enc->edge_dim <= kWMaxEdgeTypes;
-  if (slots_ok && enc->layer_kernel == 5) {
-    const int wanted = (tiles_per_xcd + kXWaves - 1) / kXWaves;
-    const int grid = 8 * (wanted < 3 * per_xcd ? wanted : 3 * per_xcd);
-    k_gine_layer_x<true, true, false><<<grid, kXThreads, kXLdsBytes, s>>>(
-        enc->f16.layer[layer], ha, hb, row_ptr, col, typ, plans, (int)n, layer_tiles, 0, 0,
-        nullptr, nullptr, tap, taps, HeadOut{});
-  } else if (slots_ok && enc->layer_kernel == 4) {
-    const int wanted = (tiles_per_xcd + kWWaves - 1) / kWWaves;
-    const int grid = 8 * (wanted < 2 * per_xcd ? wanted : 2 * per_xcd);
-    k_gine_layer_w<true, true, false><<<grid, kWThreads, kWLdsBytes, s>>>(
-        enc->f16.layer[layer], ha, hb, row_ptr, col, typ, plans, (int)n, layer_tiles, 0, 0,
-        nullptr, nullptr, tap, taps, HeadOut{});
-  } else {
-    const int wanted = (tiles_per_xcd + kLWaves - 1) / kLWaves;
-    const int grid = 8 * (wanted < per_xcd ? wanted : per_xcd);
-    k_gine_layer_q<true, true, false><<<grid, kLThreads, kQLdsBytes, s>>>(
-        enc->f16.layer[layer], ha, hb, row_ptr, col, typ, plans, (int)n, layer_tiles, 0, nullptr,
-        nullptr, tap, taps, HeadOut{});
-  }
-  if (tap == kTapNone) copy_rows(hb, (f16*)out, n * 8);
-  else copy_rows(taps, (f16*)out, n * (tap == kTapV ? 16 : 8));   // stored -> natural order
+  const int kernel = slots_ok && (enc->layer_kernel == 5 || enc->layer_kernel == 4)
+                         ? enc->layer_kernel : 3;
+  launch_layer<true, true, false>(layer_launch(kernel, layer_tiles, enc->cus, 0, 0),
+                                  enc->f16.layer[layer], w.ha, w.hb, Csr{row_ptr, col, typ, (int)n},
+                                  w.plans, layer_tiles, nullptr, nullptr, tap, w.taps, HeadOut{}, s);
+  if (tap == kTapNone) copy_rows(w.hb, (f16*)out, n * 8, s);
+  else copy_rows(w.taps, (f16*)out, n * (tap == kTapV ? 16 : 8), s);   // stored -> natural order
   GFY_CHECK_HIP(hipGetLastError());
   return GFY_OK;
 }
