@@ -179,6 +179,12 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_align_global_trace": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p,
                                        c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_size_t,
                                        c_void_p]),
+    # the two global calls inside a box: `boxes` (int32 [P][4], device) behind `within`
+    "gfy_align_global_box": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                     c_size_t, c_void_p]),
+    "gfy_align_global_trace_box": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                           c_void_p, c_size_t, c_void_p]),
     "gfy_hit_runs_workspace_bytes": (c_size_t, [c_int64]),
     "gfy_hit_runs_mark": (c_int, [*_HIT_RUNS_CALL, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),

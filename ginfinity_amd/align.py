@@ -19,6 +19,17 @@ around each seed's diagonals and a box around its rows:
                               band=chains.bands(4)[best], box=chains.boxes(16)[best],
                               gap_open=1.0, gap_extend=0.25)
 
+A chain is a list of anchors, and the step after it is to fill between them: the stretch from a
+chain's first cell to its last aligned end to end, unrelated linkers included (a local
+alignment keeps the best piece and drops the rest), or a window of the query placed inside a
+region of the target:
+
+    paths = align.global_paths(rows, counts_a=counts, pairs=chains.pairs[best],
+                               box=chains.boxes(0)[best], gap_open=1.0, gap_extend=0.25)
+    where = align.global_paths(rows, counts_a=counts, pairs=chains.pairs[best], within=True,
+                               box=chains.boxes(0)[best] + [0, 0, -32, 32],   # 32 b-rows of slack
+                               gap_open=1.0, gap_extend=0.25)
+
 **This is not ``ginfinity-sw``.**  The reference delegates alignment to that external package,
 which is not in its tree; it holds the names of eight scoring parameters and no formula.  The
 semantics below are defined here and in include/gfy.h, as the whole distance path's are.
@@ -195,9 +206,46 @@ and the carry workspace is sized by the widest box of the call.  The path needs 
 ``start..end`` lies inside the box, so the trace on ``start..end`` walks the same path
 (include/gfy.h has the argument).
 
+Global and query-in-target alignment inside a box (fill between anchors).  ``global_align`` and
+``global_paths`` take ``box`` exactly as the local functions do: the same form, the same
+clipping, the same checks and ``ValueError`` texts.  **The box is the matrix**: a boxed global
+alignment is by definition the global alignment of rows ``i_lo..i_hi`` of A and ``j_lo..j_hi`` of
+B taken as two records of their own.  Row -1 and column -1 of the definition are the rows just
+outside the box; the left border is the charged gap iterated in float32, the top border is
+charged (global) or free (``within``), exactly as without a box; substitution scores,
+recurrences, rounded operations, tie rules and op codes do not change.  With ``within=True`` the
+a-side of the box is the window, the b-side the region, and the b-rows of the region in front
+of and behind the alignment are free.  Results stay in the records' coordinates: global has
+``end = (i_hi, j_hi)`` of the clipped box and ``start = (i_lo, j_lo)``; ``within`` has ``end =
+(i_hi, j)`` for the first best ``j`` in ``j_lo..j_hi`` and ``start = (i_lo, start_j)``, ``start_j =
+end_j + 1`` where no b-row is consumed.  A box that holds no cell after clipping is "nothing to
+align", like a record of zero rows: score 0, start and end ``(-1, -1)``, an empty path.  It
+follows that
+
+* a covering box gives the results of the call without a box bit for bit: scores, starts, ends
+  and ops;
+* a boxed call equals, bit for bit, the call without a box on the sliced rows as two records of
+  their own, with the cells shifted back by ``(i_lo, j_lo)``;
+* re-scoring the ops gives ``score`` bit for bit;
+* in one and the same box ``global <= within <= local`` holds exactly;
+* a pair's result depends neither on the other pairs of the call, nor on the run, nor on the
+  workspace;
+* for ``within``, widening the box on the b-side (a lower ``j_lo``, a higher ``j_hi``, the same
+  a-rows) never lowers the score, exactly, in float32 comparison: a real cell of a column is
+  never below the charged left border it replaces, and every operation is monotone
+  (include/gfy.h has the induction).  Global has no such property: a wider box must pay for the
+  rows it adds.
+
+The device does not do the work outside the box: ``ceil(box rows / 64)`` strips from the box's
+first row, 3 for a 150-row chain where ``global_paths`` on two whole 4,096-row records takes 64
+and charges the flanks as well, so that its path is not even the same one (arithmetic, not a
+measurement).  ``global_paths`` stays two launches with no copy to the host between them: slots
+and the largest box come from the boxes clipped on the host.
+
 Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIMUM_LENGTH_NT``),
-``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: a band or a box on the
-global and ``within`` modes (borders that leave the band, pairs with no admissible path at all),
+``0 <= gap_extend <= gap_open``, the four parameters finite.  Out of scope: a band on the
+global and ``within`` modes (borders that leave the band, pairs with no admissible path at all;
+a box has neither, and is built),
 band-only or box-only storage of the direction words, boxes that are not rectangles, a span-only kernel for the global and ``within`` modes,
 free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
 scores.  Measured cost: DESIGN.md §4.
@@ -343,6 +391,15 @@ class _Call(NamedTuple):
         return np.maximum(columns, 0)
 
     @property
+    def box_rows(self) -> np.ndarray:
+        """The rows of every pair's matrix: those of its box clipped into the a-record, or with
+        no box the a-record's rows."""
+        rows_a = np.diff(self.ptr_a)[self.pairs[:, 0]]
+        if self.box is None:
+            return rows_a
+        return np.maximum(np.minimum(self.box[:, 1], rows_a - 1) - np.maximum(self.box[:, 0], 0) + 1, 0)
+
+    @property
     def empty(self) -> bool:
         """No pair, or no pair with a row on both sides: nothing is launched."""
         return self.pairs.shape[0] == 0 or self.a.shape[0] == 0 or self.b.shape[0] == 0
@@ -363,13 +420,17 @@ class _Call(NamedTuple):
                              box_dev=None if self.box is None
                              else torch.from_numpy(self.box).to(a.device))
 
-    def arguments(self) -> tuple:
+    def arguments(self, within: bool | None = None) -> tuple:
         """What every alignment call of the C ABI starts with, and behind it the band where the
         call has one (the ``*_band`` symbols).  A call with a box (the ``*_box`` symbols) has
-        both behind it, the band or NULL and then the box."""
+        both behind it, the band or NULL and then the box.  The global calls (``within`` given)
+        have no band: ``within`` is behind the parameters, and behind it the box where the call
+        has one."""
         band = () if self.band is None else (self.band_dev.data_ptr(),)
         if self.box is not None:
             band = (None if self.band is None else self.band_dev.data_ptr(), self.box_dev.data_ptr())
+        if within is not None:
+            band = (int(within),) + (() if self.box is None else (self.box_dev.data_ptr(),))
         return (self.a.data_ptr(), self.a.shape[0], self.ptr_a_dev.data_ptr(), self.ptr_a.size - 1,
                 self.b.data_ptr(), self.b.shape[0], self.ptr_b_dev.data_ptr(), self.ptr_b.size - 1,
                 self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters, *band)
@@ -407,9 +468,10 @@ def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_s
                  band=_checked_band(band, pairs.shape[0]), box=_checked_box(box, pairs.shape[0]))
 
 
-def _launch(call: _Call, name: str, sizer: str, leading: tuple, span: bool, workspace) -> tuple:
-    """The one score launch of a call that is ``on_device``: the symbol ``name`` with ``leading``
-    between the call's arguments and the outputs, its workspace sized by the symbol ``sizer``.
+def _launch(call: _Call, name: str, sizer: str, within, span: bool, workspace) -> tuple:
+    """The one score launch of a call that is ``on_device``: the symbol ``name`` with the call's
+    arguments (``within`` among them for the global calls, None for the local ones) in front of
+    the outputs, its workspace sized by the symbol ``sizer`` for the widest matrix of the call.
     ``span`` False gives ``(scores, ends)``, True ``(scores, starts, ends)``; an empty call gives
     its results without a launch."""
     device, count = call.a.device, call.pairs.shape[0]
@@ -423,7 +485,7 @@ def _launch(call: _Call, name: str, sizer: str, leading: tuple, span: bool, work
             need = getattr(lib, sizer)(count, int(call.box_columns.max()))
             scratch = (workspace or AlignWorkspace()).buffer(device, need)
             native.check(getattr(lib, name)(
-                *call.arguments(), *leading, *(out.data_ptr() for out in outputs),
+                *call.arguments(within), *(out.data_ptr() for out in outputs),
                 *_scratch_tail(scratch, device)), name)
     return outputs
 
@@ -433,7 +495,7 @@ def _launch_local(call: _Call, span: bool, workspace) -> tuple:
     name = "gfy_align_local_span" if span else "gfy_align_local"
     name += "_box" if call.box is not None else "_band" if call.band is not None else ""
     sizer = "gfy_align_span_workspace_bytes" if span else "gfy_align_workspace_bytes"
-    return _launch(call, name, sizer, (), span, workspace)
+    return _launch(call, name, sizer, None, span, workspace)
 
 
 def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -604,12 +666,12 @@ def _checked_cap(max_workspace_bytes) -> int:
 
 def _launch_global(call: _Call, within: bool, workspace) -> tuple:
     """``_launch`` for ``global_align``: ``(scores, ends)``."""
-    return _launch(call, "gfy_align_global", "gfy_align_workspace_bytes", (int(within),), False,
-                   workspace)
+    name = "gfy_align_global_box" if call.box is not None else "gfy_align_global"
+    return _launch(call, name, "gfy_align_workspace_bytes", within, False, workspace)
 
 
 def global_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                 match_scale=1.0, match_shift=0.0, within: bool = False,
+                 match_scale=1.0, match_shift=0.0, within: bool = False, box=None,
                  workspace: AlignWorkspace | None = None) -> tuple[torch.Tensor, torch.Tensor]:
     """Global (``within=False``) or query-in-target (``within=True``) alignment of the record
     pairs ``pairs``: ``(scores float32 [P], ends int32 [P, 2])`` on the device, exact, the ``Lq x
@@ -620,15 +682,27 @@ def global_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_ext
     record of zero rows on either side has nothing to align and gives 0 and ``(-1, -1)``.
     ``global <= within <= local_align`` holds for the scores of any pair, exactly.
 
-    The other arguments, their checks and the ``ValueError``s are those of ``local_align``;
-    ``within`` must be a bool.  An ``AlignWorkspace`` serves this function too."""
+    ``box=None`` aligns the two whole records.  Otherwise ``box`` is what ``local_align`` takes,
+    an integer array ``[P, 4]`` of ``(i_lo, i_hi, j_lo, j_hi)`` per pair or one such tuple for every
+    pair, and **the box is the matrix**: rows ``i_lo .. i_hi`` of the a-record and ``j_lo .. j_hi``
+    of the b-record are aligned as two records of their own (the head of this module says what
+    follows from that; ``Chains.boxes(0)`` is the stretch from a chain's first cell to its
+    last), and the strips outside the box cost nothing.  ``ends`` stay in the records'
+    coordinates: ``(i_hi, j_hi)`` of the box clipped into the records, or with ``within`` ``(i_hi,
+    j)`` for the first best j in ``j_lo .. j_hi``.  A box that holds no cell after clipping has
+    nothing to align: 0 and ``(-1, -1)``.  There is no ``band`` on these modes.
+
+    The other arguments, their checks and the ``ValueError``s are those of ``local_align``
+    (``box`` and its texts included); ``within`` must be a bool.  An ``AlignWorkspace`` serves
+    this function too."""
     within = _checked_within(within)
     return _launch_global(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                        match_scale, match_shift).on_device(), within, workspace)
+                                        match_scale, match_shift, None, box).on_device(), within,
+                          workspace)
 
 
 def global_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
-                 match_scale=1.0, match_shift=0.0, within: bool = False,
+                 match_scale=1.0, match_shift=0.0, within: bool = False, box=None,
                  workspace: AlignWorkspace | None = None,
                  max_workspace_bytes: int = 2 << 30) -> AlignedPaths:
     """``global_align`` with the aligned path of every pair: ``AlignedPaths(scores, starts, ends,
@@ -646,27 +720,34 @@ def global_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_ext
     on the device.  The workspace of the trace and ``max_workspace_bytes`` are those of
     ``local_paths``, the boxes being the records' own sizes.
 
+    With a ``box`` (``global_align`` says what it is) the path is that of the box's rows taken as
+    two records of their own, in the records' coordinates: ``starts[p]`` is ``(i_lo, j_lo)`` of the
+    clipped box for global and ``(i_lo, start_j)`` for ``within``, a path has up to ``box rows +
+    box columns`` ops, and both launches get the same boxes.  Slots and the largest box come from
+    the boxes clipped on the host, so there is still no copy between the launches.
+
     The other arguments, their checks and the ``ValueError``s are those of ``global_align``."""
     within = _checked_within(within)
     cap = _checked_cap(max_workspace_bytes)
     call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
-                         match_shift).on_device()
+                         match_shift, None, box).on_device()
     scores, ends = _launch_global(call, within, workspace)
     device, count = scores.device, scores.shape[0]
     with torch.cuda.device(device):
         starts = torch.full((count, 2), -1, dtype=torch.int32, device=device)
-        rows_a = np.diff(call.ptr_a)[call.pairs[:, 0]].astype(np.int64)
-        rows_b = call.rows_b.astype(np.int64)
-        slots = np.where((rows_a > 0) & (rows_b > 0), rows_a + rows_b, 0)   # Lq + Lr ops at most
+        rows_a, rows_b = call.box_rows.astype(np.int64), call.box_columns.astype(np.int64)
+        both = (rows_a > 0) & (rows_b > 0)
+        slots = np.where(both, rows_a + rows_b, 0)           # rows + columns ops at most
+        name = "gfy_align_global_trace" + ("_box" if call.box is not None else "")
 
         def trace(lib, slot_ptr, slot_ops, lengths, *rest):   # rest: box, workspace, stream
-            return lib.gfy_align_global_trace(
-                *call.arguments(), int(within), ends.data_ptr(), slot_ptr, slot_ops, lengths,
-                starts.data_ptr(), *rest)
-        return _traced(call, "gfy_align_global_trace", trace,
-                       "gfy_align_global_trace_workspace_bytes",
-                       "gfy_align_global_trace refused an end of gfy_align_global", scores, starts,
-                       ends, slots, np.stack([rows_a, rows_b], axis=1), cap, workspace)
+            tail = (ends.data_ptr(), slot_ptr, slot_ops, lengths, starts.data_ptr(), *rest)
+            if call.box is not None:
+                return lib.gfy_align_global_trace_box(*call.arguments(within), *tail)
+            return lib.gfy_align_global_trace(*call.arguments(within), *tail)
+        return _traced(call, name, trace, "gfy_align_global_trace_workspace_bytes",
+                       f"{name} refused an end of its score call", scores, starts, ends, slots,
+                       np.stack([rows_a, rows_b], axis=1), cap, workspace)
 
 
 def path_cells(ops, start) -> np.ndarray:

@@ -2,8 +2,9 @@
 // (align_local.hip, mode 0: score and end), k_align_span (align_span.hip, kSpan: score, start and
 // end) and k_align_trace (align_trace.hip, kTrace: the aligned path of a given box), their three
 // twins inside a band of diagonals (align_band.hip, | kBand), the score and span kernels inside
-// a box of rows the caller names (align_box.hip, | kBand | kBox) and the two global kernels
-// (kGlobal), as pairwise_topk.inc is shared by the top-k family.
+// a box of rows the caller names (align_box.hip, | kBand | kBox), the two global kernels
+// (kGlobal) and their twins inside such a box (align_global_box.hip, | kBox), as
+// pairwise_topk.inc is shared by the top-k family.
 //
 // One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
 // wave takes pairs wave, wave + waves of the grid, ... until the list ends.
@@ -57,8 +58,9 @@ static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an or
 //            query-in-target mode; not with kSpan
 //   kBand    only the cells of a band of diagonals exist; not with kGlobal
 //   kBox     only the cells of a box of rows the caller names exist, and the results are in the
-//            records' coordinates; with kBand (a call without a band has the covering one), not
-//            with kTrace or kGlobal
+//            records' coordinates; with kBand (a call without a band has the covering one) or
+//            with kGlobal (no band: the box's edges are the charged or free borders), and with
+//            kTrace only next to kGlobal
 enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8, kBox = 16 };
 
 // a carry entry: (H, F) of a column, and with kSpan their origins behind them
@@ -115,6 +117,10 @@ struct AlignPair {
 //     and lr the box's sizes, the band shifted by j_lo - i_lo.  A box that holds no cell leaves lq
 //     = lr = 0, the pair of a record of zero rows.  The carry has to hold the box's columns, not
 //     the record's.  A null `bands` is the covering band.
+//   kBox and kGlobal: there is no band; the box is the matrix, so row -1 and column -1 of the
+//     definition are the rows just outside it and the loop needs nothing more.
+//   kTrace, kGlobal and kBox: the caller's box is applied FIRST, and the checks of kTrace and
+//     kGlobal then run on the box's sizes, with the given end shifted by -(i_lo, j_lo).
 template <unsigned kMode>
 __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs* trace,
                                              bool within, int64_t pair, AlignPair& pr) {
@@ -168,8 +174,10 @@ __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs
     const int box_rows = box ? i_hi - i_lo + 1 : 0, box_cols = box ? j_hi - j_lo + 1 : 0;
     ok = ok && box_cols <= p.cap;
     pr.box_i = box ? i_lo : 0, pr.box_j = box ? j_lo : 0;
-    lo -= pr.box_j - pr.box_i;   // the band in the box's coordinates
-    hi -= pr.box_j - pr.box_i;
+    if constexpr (kBand) {   // the band in the box's coordinates
+      lo -= pr.box_j - pr.box_i;
+      hi -= pr.box_j - pr.box_i;
+    }
     a_lo += pr.box_i;
     b_lo += pr.box_j;
     a_hi = a_lo + box_rows;
@@ -183,16 +191,18 @@ __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs
       si = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair]);
       sj = __builtin_amdgcn_readfirstlane(trace->starts[2 * pair + 1]);
     }
-    const int ei = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair]);
-    const int ej = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair + 1]);
+    int ei = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair]);
+    int ej = __builtin_amdgcn_readfirstlane(trace->ends[2 * pair + 1]);
     pr.op_lo = trace->op_ptr[pair];
     const int64_t op_hi = trace->op_ptr[pair + 1];
     bool none, box;
     int64_t box_rows, box_cols;
     if constexpr (kGlobal) {
-      // rows 0 .. Lq - 1 and columns 0 .. end_j of the records
+      // rows 0 .. Lq - 1 and columns 0 .. end_j of the records (kBox: of the caller's box, which
+      // stands in the records' place by now, the end in its coordinates)
       const int64_t full_q = a_hi - a_lo, full_r = b_hi - b_lo;
       none = ei == -1 && ej == -1;
+      if constexpr (kBox) ei -= pr.box_i, ej -= pr.box_j;
       box = ok && !none && ei == full_q - 1 && ej >= 0 && ej < full_r &&
             (within || ej == full_r - 1);
       box_rows = box ? full_q : 0, box_cols = box ? (int64_t)ej + 1 : 0;
@@ -234,7 +244,8 @@ __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs
 // cell is the last H of the lane that owns its row.
 //   kGlobal: the walk has no "starts here", leaves the box over a border and the lanes add the
 //     border's ops behind it; any H is walked back from, and a path that is all gaps has Lq + Lr
-//     ops.  start_j is the first row of B the path consumes.
+//     ops.  start_j is the first row of B the path consumes.  kBox: lq and lr are the box's, so
+//     are the borders, and the start goes back into the records' coordinates.
 //   kBand: a box whose last cell lies outside the band has no path.
 template <unsigned kMode>
 __device__ __forceinline__ void trace_walk(int lane, char* ring, const uint32_t* dir,
@@ -242,6 +253,7 @@ __device__ __forceinline__ void trace_walk(int lane, char* ring, const uint32_t*
                                            bool within, int64_t pair, int strips, float h_last,
                                            int32_t* out_start) {
   constexpr bool kGlobal = kMode & AlignMode::kGlobal, kBand = kMode & AlignMode::kBand;
+  constexpr bool kBox = kMode & AlignMode::kBox;
   const int lq = pr.lq, lr = pr.lr;
   int length = 0;
   int start_j = 0;
@@ -304,8 +316,10 @@ __device__ __forceinline__ void trace_walk(int lane, char* ring, const uint32_t*
   }
   if (lane == 0) trace->out_len[pair] = pr.ok ? length : -2;
   if constexpr (kGlobal) {
+    int start_i = 0;
+    if constexpr (kBox) start_i = pr.box_i, start_j += pr.box_j;
     if (lane == 0) {
-      out_start[2 * pair] = pr.ok ? (strips > 0 ? 0 : -1) : -2;
+      out_start[2 * pair] = pr.ok ? (strips > 0 ? start_i : -1) : -2;
       out_start[2 * pair + 1] = pr.ok ? (strips > 0 ? start_j : -1) : -2;
     }
   }
@@ -314,7 +328,8 @@ __device__ __forceinline__ void trace_walk(int lane, char* ring, const uint32_t*
 // The pair's result.  kGlobal: the last cell, or (within) the first best cell of the last row:
 // one lane holds either.  Otherwise one butterfly orders the lanes' best cells by (score
 // descending, i ascending, j ascending), and with kSpan the origin goes along.  kBox: the cells
-// of a positive score go back into the records' coordinates; (-1, -1) and (-2, -2) stay.
+// of a positive score (kGlobal: a real end) go back into the records' coordinates; (-1, -1) and
+// (-2, -2) stay.
 template <unsigned kMode>
 __device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const AlignPair& pr,
                                             bool within, int64_t pair, int strips, float h_last,
@@ -326,11 +341,13 @@ __device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const 
   if constexpr (kGlobal) {
     const int owner = (pr.lq - 1) & (kStrip - 1);
     const float score = within ? lane_value(best, owner) : lane_value(h_last, owner);
-    const int end_j = within ? __builtin_amdgcn_readlane(best_j, owner) : pr.lr - 1;
+    int end_i = pr.lq - 1;
+    int end_j = within ? __builtin_amdgcn_readlane(best_j, owner) : pr.lr - 1;
+    if constexpr (kBox) end_i += pr.box_i, end_j += pr.box_j;
     if (lane == 0) {
-      const bool none = strips == 0;   // a record of zero rows: nothing to align
+      const bool none = strips == 0;   // a record (kBox: a box) of zero rows: nothing to align
       p.out_score[pair] = ok ? (none ? 0.f : score) : __builtin_nanf("");
-      p.out_end[2 * pair] = ok ? (none ? -1 : pr.lq - 1) : -2;
+      p.out_end[2 * pair] = ok ? (none ? -1 : end_i) : -2;
       p.out_end[2 * pair + 1] = ok ? (none ? -1 : end_j) : -2;
     }
   } else {
@@ -381,8 +398,10 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
   static_assert(!(kSpan && kTrace), "the trace runs on the plain (H, F) carry");
   static_assert(!(kSpan && kGlobal), "a global alignment starts at the matrix's corner");
   static_assert(!(kBand && kGlobal), "a band on the global modes: borders that leave the band");
-  static_assert(!(kMode & AlignMode::kBox) || (kBand && !kTrace && !kGlobal),
-                "a box comes with a band and serves the score and span kernels");
+  static_assert(!(kMode & AlignMode::kBox) || kBand || kGlobal,
+                "a box comes with a band (local) or with the global modes");
+  static_assert(!((kMode & AlignMode::kBox) && kTrace) || kGlobal,
+                "a local path needs no boxed trace: start..end lies inside the box");
   using Carry = AlignCarry<kSpan>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int lane = threadIdx.x & 63;

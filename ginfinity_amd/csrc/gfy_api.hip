@@ -916,7 +916,7 @@ struct NamedOutput {
   const char* name;
 };
 
-// The argument rules every alignment call (gfy_align_local to gfy_align_global_trace) shares, in one
+// The argument rules every alignment call (gfy_align_local to gfy_align_global_trace_box) shares, in one
 // order (the outputs in the order given), and the call record the launchers take: `call` gets
 // every field that comes from the 14 values; the outputs are the entry point's, carry and cap the
 // launcher's.
@@ -1249,5 +1249,75 @@ int gfy_align_global_trace(const void* a, int64_t n, const int32_t* ptr_a, int64
                                    clipped_align_rows(max_rows_b), ws, ws_bytes,
                                    (hipStream_t)stream);
 }
+
+// The two global calls inside a box of rows per pair: their counterpart's checks in its order,
+// with `boxes` named first, and the boxed kernels (align_global_box.hip).  There is no band.
+#define GFY_REQUIRE_BOXES(who, plain)                                                          \
+  GFY_REQUIRE(boxes, GFY_ERR_INVALID,                                                          \
+              who ": boxes is NULL (int32 [P][4] of (i_lo, i_hi, j_lo, j_hi) rows in device "  \
+                  "memory; " plain " is the call without a box)")
+
+int gfy_align_global_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                         float gap_open, float gap_extend, int within, const int32_t* boxes,
+                         float* out_score, int32_t* out_end, void* ws, size_t ws_bytes,
+                         void* stream) {
+  clear_error();
+  GFY_REQUIRE_BOXES("gfy_align_global_box", "gfy_align_global");
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_global_box",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
+    return rc;
+  GFY_REQUIRE(within == 0 || within == 1, GFY_ERR_INVALID,
+              "gfy_align_global_box: within = %d is neither 0 nor 1", within);
+  call.boxes = boxes;
+  call.out_score = out_score;
+  call.out_end = out_end;
+  return launch_align_global_box(call, within, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int gfy_align_global_trace_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                               const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                               const int32_t* pairs, int64_t P, float match_scale,
+                               float match_shift, float gap_open, float gap_extend, int within,
+                               const int32_t* boxes, const int32_t* ends, const int64_t* op_ptr,
+                               uint8_t* out_ops, int32_t* out_len, int32_t* out_start,
+                               int64_t max_rows_a, int64_t max_rows_b, void* ws, size_t ws_bytes,
+                               void* stream) {
+  clear_error();
+  GFY_REQUIRE_BOXES("gfy_align_global_trace_box", "gfy_align_global_trace");
+  GFY_REQUIRE(ends, GFY_ERR_INVALID, "gfy_align_global_trace_box: ends is NULL");
+  GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_global_trace_box: op_ptr is NULL");
+  GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_global_trace_box: out_ops is NULL");
+  GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_global_trace_box: out_len is NULL");
+  GFY_REQUIRE(out_start, GFY_ERR_INVALID, "gfy_align_global_trace_box: out_start is NULL");
+  AlignArgs call;   // the pointers are named above: no output is left to the shared check
+  if (const int rc = checked_align_call(
+          "gfy_align_global_trace_box",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {}, ws, &call))
+    return rc;
+  GFY_REQUIRE(within == 0 || within == 1, GFY_ERR_INVALID,
+              "gfy_align_global_trace_box: within = %d is neither 0 nor 1", within);
+  GFY_REQUIRE(max_rows_a >= 0 && max_rows_b >= 0, GFY_ERR_INVALID,
+              "gfy_align_global_trace_box: max_rows_a = %lld, max_rows_b = %lld are negative",
+              (long long)max_rows_a, (long long)max_rows_b);
+  call.boxes = boxes;
+  TraceArgs trace{};
+  trace.ends = ends;
+  trace.op_ptr = op_ptr;
+  trace.out_ops = out_ops;
+  trace.out_len = out_len;
+  return launch_align_global_trace_box(call, trace, out_start, within,
+                                       clipped_align_rows(max_rows_a),
+                                       clipped_align_rows(max_rows_b), ws, ws_bytes,
+                                       (hipStream_t)stream);
+}
+#undef GFY_REQUIRE_BOXES
 
 }  // extern "C"

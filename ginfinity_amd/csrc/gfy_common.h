@@ -385,7 +385,8 @@ struct AlignArgs {
   int cap;                // columns a carry buffer holds
   const int32_t* bands;   // [P][2] (lo, hi) diagonals j - i per pair: the *_band kernels alone
   const int32_t* boxes;   // [P][4] (i_lo, i_hi, j_lo, j_hi) rows per pair: the *_box kernels alone,
-                          // for which a null bands is the covering band
+                          // for which a null bands is the covering band (the global ones read
+                          // no band at all)
 };
 
 // what k_align_trace takes next to AlignArgs (whose out_score / out_end it leaves alone, and whose
@@ -436,6 +437,14 @@ int launch_align_trace_band(const AlignArgs& call, const TraceArgs& trace, int64
 int launch_align_local_box(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_align_local_span_box(const AlignArgs& call, int32_t* out_start, void* ws,
                                 size_t ws_bytes, hipStream_t s);
+// align_global_box.hip: the two global calls inside a box of rows per pair (call.boxes, no band);
+// the workspaces are align_workspace_bytes with the widest box's columns and
+// align_global_trace_workspace_bytes with the largest box's rows and columns
+int launch_align_global_box(const AlignArgs& call, int within, void* ws, size_t ws_bytes,
+                            hipStream_t s);
+int launch_align_global_trace_box(const AlignArgs& call, const TraceArgs& trace,
+                                  int32_t* out_start, int within, int64_t max_box_rows,
+                                  int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
 
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS

@@ -909,8 +909,8 @@ int gfy_align_trace_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t
  *               for max_rows_b; a pair whose box has more columns than the workspace holds is
  *               refused: NaN and (-2, -2).
  *   Arguments, checks and error codes are those of the banded counterpart but for bands; a NULL
- *   boxes is GFY_ERR_INVALID, named, with a pointer to the call without a box.  Out of scope: a
- *   box on gfy_align_global and gfy_align_global_trace, band-only or box-only storage of the
+ *   boxes is GFY_ERR_INVALID, named, with a pointer to the call without a box.  A box on the
+ *   global modes is gfy_align_global_box's.  Out of scope: band-only or box-only storage of the
  *   direction words, boxes that are not rectangles.
  *   Cost: DESIGN.md §4.                                                                        */
 int gfy_align_local_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -962,8 +962,9 @@ int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int
  *               score(within = 0) <= score(within = 1) <= gfy_align_local's score.
  *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), used as gfy_align_local uses it.
  *   Arguments and error codes are those of gfy_align_local; a within other than 0 or 1 is
- *   GFY_ERR_INVALID.  Out of scope: a band on these modes (the gfy_align_*_band calls are local
- *   only), free ends on the a-side, a span-only call for these modes, normalisation of scores.
+ *   GFY_ERR_INVALID.  A box of rows on these modes is gfy_align_global_box's.  Out of scope: a
+ *   band on these modes (the gfy_align_*_band calls are local only), free ends on the a-side, a
+ *   span-only call for these modes, normalisation of scores.
  *   Cost: DESIGN.md §4.                                                                       */
 int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                      const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
@@ -1015,6 +1016,97 @@ int gfy_align_global_trace(const void* a, int64_t n, const int32_t* ptr_a, int64
                            int32_t* out_len /* [P] */, int32_t* out_start /* [P][2] */,
                            int64_t max_rows_a, int64_t max_rows_b,
                            void* workspace, size_t workspace_bytes, void* stream);
+
+/* Global and query-in-target alignment INSIDE A BOX of rows per pair (fill between anchors):
+ * gfy_align_global and gfy_align_global_trace with `boxes` (int32 [P][4], device memory) behind
+ * `within`.  A chain of seeds has a first and a last cell; the stretch between them aligned END
+ * TO END, unrelated linkers included, is the global alignment of that stretch, which a local
+ * alignment (it keeps the best piece) does not give.  within = 1 with a box asks where a WINDOW
+ * of the a-record (the box's a-rows) lies inside a REGION of the b-record (the box's b-rows).
+ *   Box         boxes[p] = (i_lo, i_hi, j_lo, j_hi) as gfy_align_local_box takes it: rows of the
+ *               a-record and of the b-record, 0-based inside the two records, both ends
+ *               inclusive.  THE BOX IS THE MATRIX: row -1 and column -1 of gfy_align_global's
+ *               definition are the rows just outside the box.  The left border is the charged
+ *               gap iterated in fp32, the top border is charged (within = 0) or free (within =
+ *               1), exactly as without a box.  Nothing else changes: s[i][j], the recurrences,
+ *               every rounded operation, the tie rules of the walk and the op codes.
+ *   Results     stay in the RECORDS' coordinates.  within = 0: out_end = (i_hi, j_hi) of the
+ *               clipped box and out_start = (i_lo, j_lo).  within = 1: out_end = (i_hi, j) for the
+ *               first best j in j_lo .. j_hi and out_start = (i_lo, start_j), start_j = end_j + 1
+ *               where no row of B is consumed.
+ *   Clipping    the kernel reads the four values per pair like the pair itself, clips them into
+ *               [-GFY_ALIGN_ROWS_MAX, GFY_ALIGN_ROWS_MAX] and then into the two records.  A box
+ *               that holds no cell after clipping is "nothing to align", like a record of zero
+ *               rows: score 0, start and end (-1, -1), out_len 0.  A pair with i_lo > i_hi or j_lo
+ *               > j_hi as given is refused as gfy_align_local_box refuses it: NaN, (-2, -2),
+ *               out_len -2.
+ *   It follows  - a box that covers both records gives the results of gfy_align_global and
+ *                 gfy_align_global_trace bit for bit: scores, starts, ends and ops.
+ *               - a boxed call equals, bit for bit, the call without a box on rows i_lo..i_hi of
+ *                 A and j_lo..j_hi of B taken as two records of their own, with (i_lo, j_lo) (the
+ *                 clipped box's) added to its cells.  That is how the kernel does it.
+ *               - re-scoring the ops by the rule of gfy_align_trace gives out_score bit for bit.
+ *               - in one and the same box, score(within = 0) <= score(within = 1) <=
+ *                 gfy_align_local_box's score (bands NULL), exactly: the ordering of
+ *                 gfy_align_global on the sliced rows.
+ *               - a pair's result depends neither on the other pairs of the call, nor on the
+ *                 run, nor on the workspace.
+ *   Widening    within = 1: widening the box on the b-side (a lower j_lo, a higher j_hi, the same
+ *               a-rows) never lowers out_score, exactly, in fp32 comparison.  A higher j_hi only
+ *               adds candidates to the max over the last row (columns do not depend on the
+ *               columns to their right).  A lower j_lo: compare the narrow matrix N (columns from
+ *               j_lo) with the wide one W (columns from j_lo' < j_lo) column by column.  In W,
+ *               column j_lo - 1 is a real column whose cells satisfy H_W[i][j_lo - 1] >=
+ *               F_W[i][j_lo - 1], and F_W there is >= the charged left border of N by induction
+ *               over rows: F_W[0] = H_W[-1] - gap_open = 0 - gap_open = N's border at row 0 (the
+ *               top border of within is 0 in every column), and F_W[i] >= F_W[i-1] - gap_extend
+ *               >= border[i-1] - gap_extend = border[i], subtraction being monotone.  E of that
+ *               column is >= -inf = E of N's border.  So every input of N's first column is <=
+ *               its counterpart in W, every operation (rounded +, rounded -, max) is monotone,
+ *               and by induction over columns and rows every H, E and F of N is <= W's at the
+ *               same cell; so is the max over the last row.  within = 0 has NO such property: a
+ *               wider box must also pay for the rows it adds.
+ *   Trace       gfy_align_global_trace_box takes the SAME boxes as the score call and the ends
+ *               that call returned, in the records' coordinates.  The box is applied first; the
+ *               trace's own box is then rows 0 .. box rows - 1 and columns 0 .. end_j - j_lo of
+ *               it, whose top-left corner is the boxed matrix's own.  Refused (out_len -2, start
+ *               (-2, -2)): what the score call refuses, an end other than (-1, -1) that it cannot
+ *               have named for that box (end_i != i_hi, end_j outside j_lo .. j_hi, with within =
+ *               0 end_j != j_hi, all after clipping), a box of more columns than max_rows_b or of
+ *               more direction words than a wave's region, a slot shorter than box rows + end_j -
+ *               j_lo + 1.
+ *   Slots       pair p owns at least box rows + box columns bytes of out_ops (after clipping).
+ *   Work        the strips follow the box: ceil(box rows / 64) strips of at most box columns + 63
+ *               steps.  A 150-row chain in two 4,096-row records: 3 strips against the 64 of
+ *               gfy_align_global on the whole records (arithmetic from the loop bounds; no time
+ *               is claimed here).
+ *   Workspace   no sizers of their own: gfy_align_workspace_bytes(pairs, widest box columns) and
+ *               gfy_align_global_trace_workspace_bytes(pairs, max box rows, max box columns),
+ *               sizes after clipping; max_rows_a and max_rows_b of the trace are the largest BOX
+ *               sizes.  A pair whose box has more columns than the workspace holds is refused.
+ *   Arguments, checks and error codes are those of the counterpart; a NULL boxes is
+ *   GFY_ERR_INVALID, named, with a pointer to the call without a box.  Out of scope: a BAND on
+ *   these modes (borders that leave the band, pairs with no admissible path at all), boxes that
+ *   are not rectangles, free ends on the a-side.
+ *   Cost: DESIGN.md §4.                                                                        */
+int gfy_align_global_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs /* [P][2] device */, int64_t P,
+                         float match_scale, float match_shift, float gap_open, float gap_extend,
+                         int within, const int32_t* boxes /* [P][4] device */,
+                         float* out_score /* [P] */, int32_t* out_end /* [P][2] */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int gfy_align_global_trace_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                               const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                               const int32_t* pairs /* [P][2] device */, int64_t P,
+                               float match_scale, float match_shift, float gap_open,
+                               float gap_extend, int within,
+                               const int32_t* boxes /* [P][4] device */,
+                               const int32_t* ends /* [P][2] */,
+                               const int64_t* op_ptr /* [P + 1] */, uint8_t* out_ops,
+                               int32_t* out_len /* [P] */, int32_t* out_start /* [P][2] */,
+                               int64_t max_rows_a, int64_t max_rows_b,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 /* Seeds from radius-search hits: the MAXIMAL DIAGONAL RUNS of the hits of
  * gfy_pairwise_within_fill, the step between that search and the gfy_align_*_band calls.  A

@@ -49,8 +49,17 @@ of both by the kernel's loop bounds (arithmetic, counted on the host) and how ma
 alignments are the banded ones bit for bit (the region is the best alignment of its band, so
 all of them should be).
 
+``--global --box MARGIN`` and ``--within --box MARGIN`` are the fill-between-anchors measurement, on
+the pairs of ``--box``: ``global_paths`` (``within=False`` / ``True``) inside the box of every
+region and ``MARGIN`` rows around it, next to (a) ``global_paths`` on the two whole records, the
+only way without a box (on the first ``--whole-pairs`` pairs, 4,096 x 4,096 cells each, and per
+pair), and (b) ``local_paths`` banded and boxed.  The document (default
+profiles/align_global_box_bench.json) holds the medians, the seconds per pair, the ratios and
+the strips of each by the kernel's loop bounds (arithmetic, counted on the host).
+
     python tools/bench_align.py --pairs 20000
     python tools/bench_align.py --pairs 2000 --records 64 --box 16
+    python tools/bench_align.py --pairs 2000 --records 64 --global --within --box 16
     python tools/bench_align.py --pairs 20000 --spans
     python tools/bench_align.py --pairs 20000 --band 129 --spans --paths
     python tools/bench_align.py --pairs 20000 --global --within
@@ -82,6 +91,8 @@ PATH_SOURCES = ("align_local.inc", "align_span.hip", "align_trace.hip")   # --pa
 GLOBAL_SOURCES = ("align_local.inc", "align_global.hip")                  # --global, --within
 BAND_SOURCES = ("align_local.inc", "align_band.hip")                      # --band
 BOX_SOURCES = ("align_local.inc", "align_band.hip", "align_box.hip")      # --box
+GLOBAL_BOX_SOURCES = ("align_local.inc", "align_global.hip", "align_global_trace.hip",
+                      "align_global_box.hip", "align_box.hip")           # --global / --within --box
 BOX_RECORD_ROWS = 4096            # --box: rows of every record
 BOX_REGION_ROWS = 150             # --box: rows of the region a pair shares
 
@@ -173,8 +184,9 @@ def _measured_arguments() -> list[str]:
     return kept
 
 
-def _box_bench(args) -> dict:
-    """``--box``: the same pairs banded, without and with the box of the planted region."""
+def _box_case(args):
+    """The records, pairs, bands and boxes of ``--box``: ``(a, b, counts, pairs, bands, boxes,
+    first, last)``, the rows on the device and the rest on the host."""
     rng = np.random.default_rng(0)
     rows, region, margin = BOX_RECORD_ROWS, BOX_REGION_ROWS, args.box
     counts = np.full(args.records, rows)
@@ -183,14 +195,83 @@ def _box_bench(args) -> dict:
     at = rng.integers(0, rows - region + 1, size=(args.records, 2))     # (i, j) of every region
     for r, (i, j) in enumerate(at.tolist()):
         b[r * rows + j:r * rows + j + region] = a[r * rows + i:r * rows + i + region]
-    a, b = torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda()
     record = rng.integers(0, args.records, size=args.pairs)
-    pairs = torch.from_numpy(np.stack([record, record], axis=1).astype(np.int32))
+    pairs = np.stack([record, record], axis=1).astype(np.int32)
     first, last = at[record], at[record] + region - 1
     diagonal = first[:, 1] - first[:, 0]
     bands = np.stack([diagonal - 4, diagonal + 4], axis=1).astype(np.int32)
     boxes = np.stack([first[:, 0] - margin, last[:, 0] + margin, first[:, 1] - margin,
                       last[:, 1] + margin], axis=1).astype(np.int32)
+    return torch.from_numpy(a).cuda(), torch.from_numpy(b).cuda(), counts, pairs, bands, boxes, \
+        first, last
+
+
+def _global_box_bench(args) -> dict:
+    """``--global`` / ``--within`` with ``--box``: ``global_paths`` in chain-sized boxes next to
+    ``global_paths`` on the whole records and ``local_paths`` banded and boxed."""
+    a, b, counts, pairs, bands, boxes, first, last = _box_case(args)
+    rows = BOX_RECORD_ROWS
+    parameters = dict(gap_open=1.0, gap_extend=0.25, match_scale=1.0, match_shift=-0.3)
+    keeper = align.AlignWorkspace()
+    pairs_dev, box_dev = torch.from_numpy(pairs), torch.from_numpy(boxes)
+    few = min(args.whole_pairs, args.pairs)
+    common = dict(counts_a=counts, counts_b=counts, workspace=keeper, **parameters)
+    box_rows = np.minimum(boxes[:, 1], rows - 1) - np.maximum(boxes[:, 0], 0) + 1
+    boxed_strips = int(((box_rows + 63) // 64).sum())
+    source = ROOT / "ginfinity_amd" / "csrc"
+    result = {"metric": "global_paths of pairs of 4,096-row records that share a 150-row region: "
+                        "inside the region's box, on the whole records, and local_paths banded and "
+                        "boxed",
+              "pairs": args.pairs, "records": args.records, "record_rows": rows,
+              "region_rows": BOX_REGION_ROWS, "margin": args.box, "whole_pairs": few,
+              "parameters": parameters, "host": platform.node(),
+              "utc": datetime.datetime.now(datetime.timezone.utc).isoformat(timespec="seconds"),
+              "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
+              "torch": torch.__version__, "commit": args.commit or _commit(),
+              "source_sha256": {name: hashlib.sha256((source / name).read_bytes()).hexdigest()
+                                for name in GLOBAL_BOX_SOURCES},
+              "command": "python tools/bench_align.py " + " ".join(_measured_arguments()),
+              "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
+              "timed": "the whole call: host checks, the uploads, both launches, the compaction",
+              "strips_per_pair": {"boxed": boxed_strips / args.pairs, "whole_records": rows // 64,
+                                  "counted": "on the host from the loop bounds, not measured"}}
+    local = _timed(lambda: align.local_paths(a, b, pairs=pairs_dev, band=torch.from_numpy(bands),
+                                             box=box_dev, **common), args.repeats, args.warmup)
+    local_mid = statistics.median(local)
+    result["local_paths_banded_and_boxed"] = {"seconds": _span(local),
+                                              "seconds_per_pair": local_mid / args.pairs}
+    for name, wanted, within in (("global", args.whole, False), ("within", args.within, True)):
+        if not wanted:
+            continue
+        boxed = _timed(lambda: align.global_paths(a, b, pairs=pairs_dev, within=within,
+                                                  box=box_dev, **common), args.repeats, args.warmup)
+        whole = _timed(lambda: align.global_paths(a, b, pairs=pairs_dev[:few], within=within,
+                                                  **common), args.repeats, args.warmup)
+        boxed_mid, whole_mid = statistics.median(boxed), statistics.median(whole)
+        got = align.global_paths(a, b, pairs=pairs_dev, within=within, box=box_dev, **common)
+        cells_first = got.starts.cpu().numpy()
+        result[name] = {"call": f"align.global_paths(within={within})",
+                        "boxed_seconds": _span(boxed), "whole_records_seconds": _span(whole),
+                        "boxed_seconds_per_pair": boxed_mid / args.pairs,
+                        "whole_records_seconds_per_pair": whole_mid / few,
+                        "boxed_over_whole_records_per_pair":
+                            (boxed_mid / args.pairs) / (whole_mid / few),
+                        "boxed_over_local_paths_banded_and_boxed": boxed_mid / local_mid,
+                        "ops": int(got.ops.shape[0]),
+                        "paths_that_start_at_their_box":
+                            int((cells_first[:, 0] == np.maximum(boxes[:, 0], 0)).sum())}
+        print(f"global_paths(within={within}): boxed {boxed_mid:.4f} s for {args.pairs} pairs, whole "
+              f"records {whole_mid:.4f} s for {few} pairs = "
+              f"{result[name]['boxed_over_whole_records_per_pair']:.5f} x per pair; local_paths "
+              f"banded and boxed {local_mid:.4f} s", file=sys.stderr, flush=True)
+    return result
+
+
+def _box_bench(args) -> dict:
+    """``--box``: the same pairs banded, without and with the box of the planted region."""
+    a, b, counts, pairs, bands, boxes, first, last = _box_case(args)
+    rows, region, margin = BOX_RECORD_ROWS, BOX_REGION_ROWS, args.box
+    pairs = torch.from_numpy(pairs)
     parameters = dict(gap_open=1.0, gap_extend=0.25, match_scale=1.0, match_shift=-0.3)
     keeper = align.AlignWorkspace()
     common = dict(counts_a=counts, counts_b=counts, pairs=pairs, band=torch.from_numpy(bands),
@@ -285,6 +366,9 @@ def main() -> None:
                         help="a measurement of its own: pairs of 4,096-row records that share a "
                              "150-row region, banded, without and with the region's box of MARGIN "
                              "rows around it (default output profiles/align_box_bench.json)")
+    parser.add_argument("--whole-pairs", type=int, default=64,
+                        help="with --global / --within and --box: the pairs on which global_paths "
+                             "on the two whole records is timed")
     parser.add_argument("--commit", default=None, help="the commit measured, where git cannot say")
     parser.add_argument("--out", default=None,
                         help="default profiles/align_bench.json, with --box "
@@ -296,11 +380,15 @@ def main() -> None:
         parser.error("--band: a positive number of diagonals")
     if args.box is not None and args.box < 0:
         parser.error("--box: a margin of 0 rows or more")
+    if args.whole_pairs < 1:
+        parser.error("--whole-pairs: positive")
+    fill = args.box is not None and (args.whole or args.within)
     if args.out is None:
         args.out = str(ROOT / "profiles" / ("align_bench.json" if args.box is None
+                                            else "align_global_box_bench.json" if fill
                                             else "align_box_bench.json"))
     if args.box is not None:
-        result = _box_bench(args)
+        result = _global_box_bench(args) if fill else _box_bench(args)
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
         print(json.dumps(result))
