@@ -185,6 +185,10 @@ SIGNATURES: dict[str, tuple] = {
     "gfy_align_global_trace_box": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, c_void_p, c_void_p, c_int64, c_int64,
                                            c_void_p, c_size_t, c_void_p]),
+    # the values of given paths: starts, op_ptr, ops, n_ops, the five outputs, max_waves, stream
+    "gfy_align_path_values": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_void_p]),
     "gfy_hit_runs_workspace_bytes": (c_size_t, [c_int64]),
     "gfy_hit_runs_mark": (c_int, [*_HIT_RUNS_CALL, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),

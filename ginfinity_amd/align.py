@@ -249,6 +249,13 @@ a box has neither, and is built),
 band-only or box-only storage of the direction words, boxes that are not rectangles, a span-only kernel for the global and ``within`` modes,
 free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
 scores.  Measured cost: DESIGN.md §4.
+
+Values along a path.  ``path_values`` takes the paths of any of the functions above (or a
+caller's own) and returns, per op, the cosine of its cell — the dense kernel's, bit for bit,
+from the same eight MFMA steps on the path's 32 row pairs at a time, not from a dense ``Lq x Lr``
+matrix — and the running score behind it, and per path the score (the aligner's, bit for bit),
+the matches, the gap runs and the float64 sum of the matched cosines.  No normalisation is
+built, but a normalisation of scores now has its inputs on the device.
 """
 from __future__ import annotations
 
@@ -748,6 +755,139 @@ def global_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_ext
         return _traced(call, name, trace, "gfy_align_global_trace_workspace_bytes",
                        f"{name} refused an end of its score call", scores, starts, ends, slots,
                        np.stack([rows_a, rows_b], axis=1), cap, workspace)
+
+
+class PathValues(NamedTuple):
+    """What ``path_values`` returns, all on the device: the per-op values of pair p are
+    ``cosines[offsets[p]:offsets[p + 1]]`` and ``running[offsets[p]:offsets[p + 1]]``."""
+    cosines: torch.Tensor       # float32 [offsets[P]]: the cosine of a matched cell, NaN at a gap op
+    running: torch.Tensor       # float32 [offsets[P]]: the score behind every op
+    scores: torch.Tensor        # float32 [P]: the last running value, 0 for an empty path
+    matches: torch.Tensor       # int32 [P]: ops 0
+    gap_runs: torch.Tensor      # int32 [P, 2]: runs of op 1, runs of op 2
+    cosine_sums: torch.Tensor   # float64 [P]: the matched cosines added in path order
+    status: torch.Tensor        # int32 [P]: 0, or -2 for a path that was refused
+    offsets: torch.Tensor       # int64 [P + 1]: the offsets of the paths
+
+    def mean_cosine(self) -> torch.Tensor:
+        """``cosine_sums / matches`` in float64 ``[P]``, NaN where nothing matched (and for a
+        path that was refused)."""
+        matched = self.matches > 0
+        return torch.where(matched, self.cosine_sums / self.matches.clamp(min=1).to(torch.float64),
+                           torch.full_like(self.cosine_sums, float("nan")))
+
+    def of(self, p: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(cosines, running)`` of pair p: the two per-op slices (reads two offsets, which
+        waits for the device)."""
+        lo, hi = (int(x) for x in self.offsets[p:p + 2].tolist())
+        return self.cosines[lo:hi], self.running[lo:hi]
+
+
+def _checked_paths(paths, count: int) -> tuple:
+    """``(starts, ops, offsets)`` of ``paths`` as tensors wherever they live, or the
+    ``ValueError``.  No device is touched: of arrays on a device only type and shape are looked
+    at, and what they hold is the kernel's to check."""
+    tensors = []
+    for name in ("starts", "ops", "offsets"):
+        try:
+            values = getattr(paths, name)
+        except AttributeError:
+            raise ValueError("paths must have starts, ops and offsets (an AlignedPaths, or any "
+                             "object with these three)") from None
+        if isinstance(values, np.ndarray):
+            values = torch.from_numpy(np.ascontiguousarray(values))
+        if not isinstance(values, torch.Tensor):
+            raise ValueError(f"paths.{name} must be a numpy array or a torch tensor")
+        tensors.append(values)
+    starts, ops, offsets = tensors
+    if ops.dtype != torch.uint8 or ops.dim() != 1:
+        raise ValueError("paths.ops must be a one-dimensional uint8 array of 0, 1 and 2")
+    if offsets.dtype != torch.int64 or offsets.shape != (count + 1,):
+        raise ValueError(f"paths.offsets must be an int64 array of shape (P + 1,) = ({count + 1},)")
+    if offsets.device.type == "cpu" and (int(offsets[0]) != 0 or int(offsets[-1]) != ops.shape[0]):
+        raise ValueError(f"paths.offsets must start at 0 and end at ops.shape[0] = {ops.shape[0]}, "
+                         f"not run from {int(offsets[0])} to {int(offsets[-1])}")
+    if starts.dtype != torch.int32 or starts.shape != (count, 2):
+        raise ValueError(f"paths.starts must be an int32 array of shape (P, 2) = ({count}, 2)")
+    return starts, ops, offsets
+
+
+def path_values(paths, a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                match_scale=1.0, match_shift=0.0, max_waves: int | None = None) -> PathValues:
+    """The values along aligned paths, without leaving the device: ``PathValues(cosines, running,
+    scores, matches, gap_runs, cosine_sums, status, offsets)``.
+
+    ``paths`` is what ``local_paths`` or ``global_paths`` returned for the same rows, counts,
+    pairs and parameters, or any object with ``starts`` (int32 ``[P, 2]``, the cell where each path
+    starts, in the records' coordinates), ``ops`` (uint8, all paths one after the other) and
+    ``offsets`` (int64 ``[P + 1]``), numpy or torch, on any device: a caller may hand in paths of
+    their own.  Op ``0`` consumes cell ``(i, j)`` and moves to ``(i + 1, j + 1)``, op ``1`` moves to
+    ``(i, j + 1)``, op ``2`` to ``(i + 1, j)``, as ``path_cells`` reads them.  There is no ``band`` and
+    no ``box``: the starts already are in the records' coordinates.
+
+    * ``cosines``: at an op ``0`` at ``(i, j)`` the cosine ``distance.pairwise(A, B,
+      metric="cosine")[i, j]`` of the pair's two records, bit for bit, and NaN at a gap op.  The
+      dense ``Lq x Lr`` matrix is not written.
+    * ``running``: the score behind every op under the re-scoring rule at the head of this module
+      (``h = 0``; op 0 adds ``s[i][j]``; the first op of a run of equal gap ops takes ``gap_open``,
+      each further one ``gap_extend``), every operation one rounded float32 operation.
+    * ``scores``: the last running value, 0 for an empty path.  For a path that one of the
+      aligners returned this is that aligner's score bit for bit (only a zero keeps no promise
+      of its sign).
+    * ``matches``, ``gap_runs``: the ops ``0``, and the runs of op ``1`` and of op ``2`` (op ``1``
+      behind op ``2`` starts a new run).
+    * ``cosine_sums``: the matched cosines added one at a time in float64 in path order;
+      ``values.mean_cosine()`` divides it by ``matches``.  Matched counts, gap runs and cosine sums
+      are what a normalisation of scores starts from.
+
+    A path is REFUSED where the kernel cannot follow it: a start with a negative coordinate other
+    than ``(-1, -1)`` (where only an empty path may start), an op byte above 2, a path that names
+    a cell outside its two records, offsets on the device that decrease or leave ``ops``.  A
+    refused path has ``status`` -2, NaN in all its per-op values, in its score and in its sum.
+    This is reported through ``status`` and NOT raised: reading it back would make the call wait
+    for the device.  The other paths of the call are not affected, and a path's values depend
+    neither on its company, nor on the order of the paths, nor on ``max_waves``.
+
+    ``max_waves=None`` leaves the number of waves to the library (one per path, up to 4,096); a
+    positive integer bounds it, and the waves take the paths in turn.
+
+    Every argument error is a ``ValueError`` before a device is touched: those of
+    ``local_align`` (without ``band`` and ``box``), ``ops`` that is not one-dimensional uint8,
+    ``offsets`` that is not int64 ``[P + 1]`` — or, where it lives on the host, does not start at 0
+    or end at ``ops.shape[0]`` —, ``starts`` that is not int32 ``[P, 2]``.  ``P == 0``, or every
+    path empty, returns empty or zero tensors without a launch."""
+    if max_waves is not None:
+        max_waves = _checked_integer(max_waves, "max_waves", 1)
+    call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
+                         match_shift)
+    count = call.pairs.shape[0]
+    starts, ops, offsets = _checked_paths(paths, count)
+    call = call.on_device()
+    device, total = call.a.device, ops.shape[0]
+    with torch.cuda.device(device):
+        starts, ops, offsets = (x.to(device).contiguous() for x in (starts, ops, offsets))
+        # NaN where the kernel writes nothing: the ops of a slot that it refuses
+        cosines = torch.full((total,), float("nan"), dtype=torch.float32, device=device)
+        running = torch.full((total,), float("nan"), dtype=torch.float32, device=device)
+        scores = torch.zeros(count, dtype=torch.float32, device=device)
+        counts = torch.zeros((count, 4), dtype=torch.int32, device=device)
+        sums = torch.zeros(count, dtype=torch.float64, device=device)
+        if call.empty and total and count:
+            # no row to align with: a path with ops names cells that do not exist.  torch.where,
+            # not an assignment under a mask, which would wait for the device
+            refused = offsets[1:] > offsets[:-1]
+            scores = torch.where(refused, torch.full_like(scores, float("nan")), scores)
+            sums = torch.where(refused, torch.full_like(sums, float("nan")), sums)
+            counts[:, 3] = torch.where(refused, -2, 0).to(torch.int32)
+        elif total and count:
+            name = "gfy_align_path_values"
+            native.check(getattr(native.library(), name)(
+                *call.arguments(), starts.data_ptr(), offsets.data_ptr(), ops.data_ptr(), total,
+                cosines.data_ptr(), running.data_ptr(), scores.data_ptr(), counts.data_ptr(),
+                sums.data_ptr(), max_waves or 0, torch.cuda.current_stream(device).cuda_stream),
+                name)
+    return PathValues(cosines, running, scores, counts[:, 0], counts[:, 1:3], sums, counts[:, 3],
+                      offsets)
 
 
 def path_cells(ops, start) -> np.ndarray:

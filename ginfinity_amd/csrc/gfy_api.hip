@@ -922,7 +922,7 @@ struct NamedOutput {
 // launcher's.
 static int checked_align_call(const char* who, const AlignAbi& v,
                               std::initializer_list<NamedOutput> outputs, const void* ws,
-                              AlignArgs* call) {
+                              AlignArgs* call, bool has_workspace = true) {
   GFY_REQUIRE(v.a, GFY_ERR_INVALID, "%s: a is NULL", who);
   GFY_REQUIRE(v.b, GFY_ERR_INVALID, "%s: b is NULL", who);
   GFY_REQUIRE(v.ptr_a, GFY_ERR_INVALID, "%s: ptr_a is NULL", who);
@@ -930,7 +930,7 @@ static int checked_align_call(const char* who, const AlignAbi& v,
   GFY_REQUIRE(v.pairs, GFY_ERR_INVALID, "%s: pairs is NULL", who);
   for (const NamedOutput& out : outputs)
     GFY_REQUIRE(out.pointer, GFY_ERR_INVALID, "%s: %s is NULL", who, out.name);
-  GFY_REQUIRE(ws, GFY_ERR_INVALID, "%s: workspace is NULL", who);
+  GFY_REQUIRE(ws || !has_workspace, GFY_ERR_INVALID, "%s: workspace is NULL", who);
   GFY_REQUIRE(v.n > 0 && v.m > 0 && v.n < INT32_MAX && v.m < INT32_MAX, GFY_ERR_INVALID,
               "%s: bad arguments: n = %lld, m = %lld", who, (long long)v.n, (long long)v.m);
   GFY_REQUIRE(v.records_a > 0 && v.records_a < INT32_MAX && v.records_b > 0 &&
@@ -1319,5 +1319,43 @@ int gfy_align_global_trace_box(const void* a, int64_t n, const int32_t* ptr_a, i
                                        (hipStream_t)stream);
 }
 #undef GFY_REQUIRE_BOXES
+
+// The values of given paths (align_values.hip): the shared checks of the alignment calls, the
+// pointers of its own named in its own order, and no workspace.
+int gfy_align_path_values(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                          const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                          float gap_open, float gap_extend, const int32_t* starts,
+                          const int64_t* op_ptr, const uint8_t* ops, int64_t n_ops,
+                          float* out_cosine, float* out_running, float* out_score,
+                          int32_t* out_counts, double* out_cosine_sum, int64_t max_waves,
+                          void* stream) {
+  clear_error();
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_path_values",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{starts, "starts"}, {op_ptr, "op_ptr"}, {ops, "ops"}, {out_cosine, "out_cosine"},
+           {out_running, "out_running"}, {out_score, "out_score"}, {out_counts, "out_counts"},
+           {out_cosine_sum, "out_cosine_sum"}},
+          nullptr, &call, false))
+    return rc;
+  GFY_REQUIRE(n_ops >= 0, GFY_ERR_INVALID, "gfy_align_path_values: n_ops = %lld is negative",
+              (long long)n_ops);
+  GFY_REQUIRE(max_waves >= 0, GFY_ERR_INVALID,
+              "gfy_align_path_values: max_waves = %lld is negative", (long long)max_waves);
+  PathValueArgs values{};
+  values.starts = starts;
+  values.op_ptr = op_ptr;
+  values.ops = ops;
+  values.n_ops = n_ops;
+  values.out_cosine = out_cosine;
+  values.out_running = out_running;
+  values.out_score = out_score;
+  values.out_counts = out_counts;
+  values.out_cosine_sum = out_cosine_sum;
+  return launch_align_path_values(call, values, max_waves, (hipStream_t)stream);
+}
 
 }  // extern "C"

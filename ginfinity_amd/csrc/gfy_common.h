@@ -446,6 +446,24 @@ int launch_align_global_trace_box(const AlignArgs& call, const TraceArgs& trace,
                                   int32_t* out_start, int within, int64_t max_box_rows,
                                   int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
 
+// what k_align_path_values takes next to AlignArgs (of which it reads the rows, the records, the
+// pairs and the four parameters, and no output, carry, band or box)
+struct PathValueArgs {
+  const int32_t* starts;    // [P][2]
+  const int64_t* op_ptr;    // [P + 1]: pair p's path is ops[op_ptr[p] .. op_ptr[p + 1])
+  const uint8_t* ops;       // [n_ops]
+  int64_t n_ops;
+  float* out_cosine;        // [n_ops]
+  float* out_running;       // [n_ops]
+  float* out_score;         // [P]
+  int32_t* out_counts;      // [P][4]
+  double* out_cosine_sum;   // [P]
+};
+// align_values.hip: the values of given paths; no workspace.  max_waves > 0 bounds the waves that
+// take the paths in turn
+int launch_align_path_values(const AlignArgs& call, const PathValueArgs& values, int64_t max_waves,
+                             hipStream_t s);
+
 // ---- LDS-DMA (global_load_lds_dwordx4) ---------------------------------------------
 // One wave instruction: lane L copies 16 bytes from its own global address to LDS
 // address lds + 16 L (lds is wave-uniform, in M0); inactive lanes move nothing.  No

@@ -1108,6 +1108,59 @@ int gfy_align_global_trace_box(const void* a, int64_t n, const int32_t* ptr_a, i
                                int64_t max_rows_a, int64_t max_rows_b,
                                void* workspace, size_t workspace_bytes, void* stream);
 
+/* The VALUES ALONG given paths: per op the cosine of its cell and the running score behind it, per
+ * path the score, the counts and the sum that a normalisation of scores starts from.  The dense
+ * L_q x L_r cosine matrix of a pair is not written to read a few hundred of its cells.
+ *   Paths       a, b, the records, pairs and the four parameters are those of gfy_align_local.
+ *               starts int32 [P][2], op_ptr int64 [P + 1], ops uint8 [n_ops], device memory: pair
+ *               p's path is ops[op_ptr[p] .. op_ptr[p + 1]), one byte per op, and starts at cell
+ *               starts[p] in the records' coordinates.  Op 0 consumes cell (i, j) and moves to
+ *               (i + 1, j + 1), op 1 moves to (i, j + 1), op 2 to (i + 1, j).  This is what
+ *               gfy_align_trace and gfy_align_global_trace (and their band and box forms) return
+ *               once the slots are compacted; any other path in that form is served as well.
+ *   Per op      out_cosine float32 [n_ops]: at an op 0 at cell (i, j) C[i][j], which is
+ *               gfy_pairwise_dense(A, B, GFY_COSINE)[i][j] bit for bit (the same eight MFMA steps
+ *               from 0, the same norms, key and value); NaN ("no value") at a gap op.
+ *               out_running float32 [n_ops]: h behind that op under the re-scoring rule of
+ *               gfy_align_trace: h = 0; op 0: h = fl32(h + s[i][j]) with s = fl32(fl32(C *
+ *               match_scale) + match_shift); the first op of a run of equal gap ops: fl32(h -
+ *               gap_open), each further one of the run fl32(. - gap_extend) (inside a run the entry
+ *               is the running g).  Every operation is rounded once and never contracted.
+ *   Per path    out_score float32 [P]: the last running value, 0 for an empty path.
+ *               out_counts int32 [P][4]: the ops 0, the runs of op 1, the runs of op 2 (op 1 behind
+ *               op 2 starts a run, and the other way round), and a status: 0, or -2 refused.
+ *               out_cosine_sum float64 [P]: the matched cosines, each widened to float64 and added
+ *               one at a time in path order from 0: a fixed function of the path.
+ *   It follows  for a path that an alignment call of this library returned for the same rows,
+ *               pairs and parameters, out_score[p] is that call's out_score[p] bit for bit (local,
+ *               band, box, global and within; only the sign of a zero is not promised): the
+ *               re-scoring promise of gfy_align_trace, kept on the device.  A path's values depend
+ *               neither on the other paths of the call, nor on their order, nor on max_waves.
+ *   Refused     status -2, every per-op value of the path NaN, score and sum NaN, the counts 0: a
+ *               record index out of range, a record longer than GFY_ALIGN_ROWS_MAX, a start with
+ *               a negative coordinate other than (-1, -1) (where only an empty path may start),
+ *               an op byte above 2, a path that names a cell outside its two records (start_i +
+ *               #(ops 0 and 2) > L_q or start_j + #(ops 0 and 1) > L_r), op_ptr[p] > op_ptr[p + 1]
+ *               or a slot outside [0, n_ops] (then no per-op value is written).  The kernel decides
+ *               this from a counting pass over the ops before it follows any cell; what the
+ *               device arrays hold is compared and clipped, never followed unchecked, and nothing
+ *               outside the caller's buffers is read.  A refusal is not an error of the call.
+ *   No workspace.  One wave per path; max_waves = 0 leaves the number of waves to the library,
+ *   max_waves > 0 bounds it, and the waves take the paths in turn.
+ *   A NULL pointer (named in gfy_last_error), n, m, the record counts or P out of gfy_align_local's
+ *   ranges, a non-finite parameter, gap_extend outside [0, gap_open] and a negative n_ops or
+ *   max_waves are GFY_ERR_INVALID, before any launch and without a device.
+ *   Cost: DESIGN.md §4.                                                                        */
+int gfy_align_path_values(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                          const int32_t* pairs /* [P][2] device */, int64_t P,
+                          float match_scale, float match_shift, float gap_open, float gap_extend,
+                          const int32_t* starts /* [P][2] */, const int64_t* op_ptr /* [P + 1] */,
+                          const uint8_t* ops /* [n_ops] */, int64_t n_ops,
+                          float* out_cosine /* [n_ops] */, float* out_running /* [n_ops] */,
+                          float* out_score /* [P] */, int32_t* out_counts /* [P][4] */,
+                          double* out_cosine_sum /* [P] */, int64_t max_waves, void* stream);
+
 /* Seeds from radius-search hits: the MAXIMAL DIAGONAL RUNS of the hits of
  * gfy_pairwise_within_fill, the step between that search and the gfy_align_*_band calls.  A
  * stretch that two records share is one hit per row on one diagonal; this call collapses every

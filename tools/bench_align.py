@@ -57,7 +57,13 @@ pair), and (b) ``local_paths`` banded and boxed.  The document (default
 profiles/align_global_box_bench.json) holds the medians, the seconds per pair, the ratios and
 the strips of each by the kernel's loop bounds (arithmetic, counted on the host).
 
+``--values --box MARGIN`` times ``align.path_values`` next to the ``local_paths`` call, banded and
+boxed, that made its paths, on the pairs of ``--box``.  The document (default
+profiles/path_values_bench.json) holds the two medians, their ratio, the ops and how many of the
+scores are those of ``local_paths`` bit for bit (all of them should be).  No ratio is set.
+
     python tools/bench_align.py --pairs 20000
+    python tools/bench_align.py --pairs 2000 --records 64 --values --box 16
     python tools/bench_align.py --pairs 2000 --records 64 --box 16
     python tools/bench_align.py --pairs 2000 --records 64 --global --within --box 16
     python tools/bench_align.py --pairs 20000 --spans
@@ -93,6 +99,7 @@ BAND_SOURCES = ("align_local.inc", "align_band.hip")                      # --ba
 BOX_SOURCES = ("align_local.inc", "align_band.hip", "align_box.hip")      # --box
 GLOBAL_BOX_SOURCES = ("align_local.inc", "align_global.hip", "align_global_trace.hip",
                       "align_global_box.hip", "align_box.hip")           # --global / --within --box
+VALUE_SOURCES = ("align_values.hip", "pairwise_sweep.inc")               # --values
 BOX_RECORD_ROWS = 4096            # --box: rows of every record
 BOX_REGION_ROWS = 150             # --box: rows of the region a pair shares
 
@@ -267,6 +274,52 @@ def _global_box_bench(args) -> dict:
     return result
 
 
+def _values_bench(args) -> dict:
+    """``--values`` with ``--box``: ``path_values`` next to the ``local_paths`` call, banded and
+    boxed, that made the paths."""
+    a, b, counts, pairs, bands, boxes, first, last = _box_case(args)
+    parameters = dict(gap_open=1.0, gap_extend=0.25, match_scale=1.0, match_shift=-0.3)
+    pairs_dev = torch.from_numpy(pairs)
+    common = dict(counts_a=counts, counts_b=counts, pairs=pairs_dev, **parameters)
+    keeper = align.AlignWorkspace()
+
+    def make_paths():
+        return align.local_paths(a, b, band=torch.from_numpy(bands), box=torch.from_numpy(boxes),
+                                 workspace=keeper, **common)
+    source = ROOT / "ginfinity_amd" / "csrc"
+    made = _timed(make_paths, args.repeats, args.warmup)
+    paths = make_paths()
+    valued = _timed(lambda: align.path_values(paths, a, b, **common), args.repeats, args.warmup)
+    values = align.path_values(paths, a, b, **common)
+    made_mid, valued_mid = statistics.median(made), statistics.median(valued)
+    scores, mine = paths.scores.cpu().numpy(), values.scores.cpu().numpy()
+    same = (scores.view(np.uint32) == mine.view(np.uint32)) | ((scores == 0) & (mine == 0))
+    ops = int(paths.ops.shape[0])
+    print(f"local_paths (banded, boxed) {made_mid:.6f} s, path_values {valued_mid:.6f} s = "
+          f"{valued_mid / made_mid:.4f} x for {args.pairs} paths of {ops} ops", file=sys.stderr,
+          flush=True)
+    return {"metric": "path_values on the paths of local_paths (banded and boxed) of pairs of "
+                      "4,096-row records that share a 150-row region",
+            "pairs": args.pairs, "records": args.records, "record_rows": BOX_RECORD_ROWS,
+            "region_rows": BOX_REGION_ROWS, "margin": args.box, "band_diagonals": 9,
+            "parameters": parameters, "host": platform.node(),
+            "utc": datetime.datetime.now(datetime.timezone.utc).isoformat(timespec="seconds"),
+            "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
+            "torch": torch.__version__, "commit": args.commit or _commit(),
+            "source_sha256": {name: hashlib.sha256((source / name).read_bytes()).hexdigest()
+                              for name in VALUE_SOURCES},
+            "command": "python tools/bench_align.py " + " ".join(_measured_arguments()),
+            "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
+            "timed": "the whole call: host checks, the uploads, the launches (local_paths: its "
+                     "copy to the host and the compaction as well)",
+            "local_paths_seconds": _span(made), "path_values_seconds": _span(valued),
+            "path_values_over_local_paths": valued_mid / made_mid,
+            "ops": ops, "ops_per_path": ops / args.pairs,
+            "path_values_seconds_per_op": valued_mid / max(ops, 1),
+            "matches": int(values.matches.sum()), "refused": int((values.status != 0).sum()),
+            "scores_equal_to_local_paths": int(same.sum())}
+
+
 def _box_bench(args) -> dict:
     """``--box``: the same pairs banded, without and with the box of the planted region."""
     a, b, counts, pairs, bands, boxes, first, last = _box_case(args)
@@ -366,6 +419,10 @@ def main() -> None:
                         help="a measurement of its own: pairs of 4,096-row records that share a "
                              "150-row region, banded, without and with the region's box of MARGIN "
                              "rows around it (default output profiles/align_box_bench.json)")
+    parser.add_argument("--values", action="store_true",
+                        help="with --box: time align.path_values next to the local_paths call, "
+                             "banded and boxed, that made its paths (default output "
+                             "profiles/path_values_bench.json)")
     parser.add_argument("--whole-pairs", type=int, default=64,
                         help="with --global / --within and --box: the pairs on which global_paths "
                              "on the two whole records is timed")
@@ -382,13 +439,17 @@ def main() -> None:
         parser.error("--box: a margin of 0 rows or more")
     if args.whole_pairs < 1:
         parser.error("--whole-pairs: positive")
+    if args.values and (args.box is None or args.whole or args.within):
+        parser.error("--values: with --box MARGIN, and without --global and --within")
     fill = args.box is not None and (args.whole or args.within)
     if args.out is None:
         args.out = str(ROOT / "profiles" / ("align_bench.json" if args.box is None
+                                            else "path_values_bench.json" if args.values
                                             else "align_global_box_bench.json" if fill
                                             else "align_box_bench.json"))
     if args.box is not None:
-        result = _global_box_bench(args) if fill else _box_bench(args)
+        result = _values_bench(args) if args.values else _global_box_bench(args) if fill \
+            else _box_bench(args)
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
         print(json.dumps(result))
