@@ -173,6 +173,10 @@ SIGNATURES: dict[str, tuple] = {
                                     c_void_p, c_size_t, c_void_p]),
     "gfy_align_local_span_box": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_void_p, c_void_p,
                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    # null scores: bands and boxes (either may be NULL), shuffles, order (int32, device), order_ptr
+    # (int64 [P + 1], device), out_score [P][shuffles]; no out_end
+    "gfy_align_local_null": (c_int, [*_ALIGN_CALL, c_void_p, c_void_p, c_int64, c_void_p,
+                                     c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "gfy_align_global": (c_int, [*_ALIGN_CALL, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
                                  c_void_p]),
     "gfy_align_global_trace_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),

@@ -247,15 +247,44 @@ Limits: a record has at most ``GFY_ALIGN_ROWS_MAX`` = 4096 rows (``records.MAXIM
 global and ``within`` modes (borders that leave the band, pairs with no admissible path at all;
 a box has neither, and is built),
 band-only or box-only storage of the direction words, boxes that are not rectangles, a span-only kernel for the global and ``within`` modes,
-free ends on the a-side, a ``device="cpu"`` path, and any z-score or normalisation of the
-scores.  Measured cost: DESIGN.md §4.
+free ends on the a-side, a ``device="cpu"`` path, and, of what tells a score's meaning: nulls
+for the global and ``within`` modes, shuffling the a-side, and an E-value calibrated over a whole
+database search (``null_scores`` and ``significance`` below judge one pair against its own
+shuffled target).  Measured cost: DESIGN.md §4.
 
 Values along a path.  ``path_values`` takes the paths of any of the functions above (or a
 caller's own) and returns, per op, the cosine of its cell — the dense kernel's, bit for bit,
 from the same eight MFMA steps on the path's 32 row pairs at a time, not from a dense ``Lq x Lr``
 matrix — and the running score behind it, and per path the score (the aligner's, bit for bit),
-the matches, the gap runs and the float64 sum of the matched cosines.  No normalisation is
-built, but a normalisation of scores now has its inputs on the device.
+the matches, the gap runs and the float64 sum of the matched cosines.
+
+Null scores and significance.  A raw local score cannot rank hits across pairs: it grows with
+the two lengths, depends on ``match_scale / match_shift / gap_*`` and on how ordinary the two
+records' rows are, and this aligner has no scoring matrix to look a λ and a K up for.  The answer
+is empirical: align the pair against **the same target with its rows in random order**, K times,
+and state the real score against those K.  ``null_scores`` does that in one launch and without
+writing a shuffled row: in run k column j of pair p's matrix holds row ``order[j]`` of the pair's
+b-side (the b-record, or with a ``box`` the b-rows of the box, so entries are relative to the
+box: ``0 .. columns - 1``), 4 bytes per shuffled row in place of 256.  Nothing else changes — the
+a-side, the cosine (its ``1/|b|`` taken from the row the column holds), the recurrences, the band
+and the box — so ``null_scores(...)[p, k]`` equals, bit for bit, ``local_align`` of the pair with
+the b-side replaced by the rows ``order[...]`` copied out in that order.  Entries need not be a
+permutation: a reversal, or a bootstrap with repeats, is an order like any other.
+
+``shuffle_orders(columns, shuffles, seed)`` makes the orders, and they are a fixed function of
+``(seed, v, j)`` that anything with 64-bit integers reproduces (no ``torch.Generator``): with
+``v = p * shuffles + k`` the virtual pair, all arithmetic modulo 2^64 and ``>>`` logical,
+
+    mix(z):  z ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;
+             z ^= z >> 31
+    G = 0x9E3779B97F4A7C15
+    key(seed, v, j) = mix(mix(seed + (v + 1) * G) + (j + 1) * G) >> 32
+
+and the order of virtual pair v is ``0 .. columns - 1`` stably sorted by ``(key, j)``; the whole
+array is one stable sort by (virtual pair, key, j).  The same bytes come out on a CPU tensor and
+on the device.  ``significance(scores, null)`` turns ``[P, K]`` null scores into a z-score and an
+extreme-value p-value per pair; its docstring has the formulas.  They are estimates from K
+samples: K decides their resolution.
 """
 from __future__ import annotations
 
@@ -888,6 +917,226 @@ def path_values(paths, a, b=None, *, counts_a, counts_b=None, pairs, gap_open, g
                 name)
     return PathValues(cosines, running, scores, counts[:, 0], counts[:, 1:3], sums, counts[:, 3],
                       offsets)
+
+
+_WORD = 1 << 64
+_GOLDEN = 0x9E3779B97F4A7C15
+_MIX_1, _MIX_2 = 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+
+
+def _signed(word: int) -> int:
+    """The int64 with the bits of ``word`` modulo 2^64: torch has no uint64 arithmetic, and int64
+    products and sums wrap to the same bits."""
+    word %= _WORD
+    return word - _WORD if word >= 1 << 63 else word
+
+
+def _shifted(z: torch.Tensor, bits: int) -> torch.Tensor:
+    """``z >> bits`` of the 64-bit pattern, logical: int64's own shift copies the sign."""
+    return (z >> bits) & ((1 << (64 - bits)) - 1)
+
+
+def _mixed(z: torch.Tensor) -> torch.Tensor:
+    """``mix`` of the head of this module on int64 tensors, bit for bit what uint64 gives."""
+    z = (z ^ _shifted(z, 30)) * _signed(_MIX_1)
+    z = (z ^ _shifted(z, 27)) * _signed(_MIX_2)
+    return z ^ _shifted(z, 31)
+
+
+def _checked_columns(columns) -> np.ndarray:
+    columns = _host_array(columns)
+    if columns.size == 0 and columns.ndim == 1:
+        columns = np.zeros(0, dtype=np.int64)
+    if columns.ndim != 1 or columns.dtype.kind not in "iu" or (columns.size and columns.min() < 0):
+        raise ValueError("columns must be a one-dimensional array of non-negative integers, the "
+                         "rows of every pair's b-side")
+    return columns.astype(np.int64)
+
+
+def shuffle_orders(columns, shuffles, seed, device=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The orders of a null: for every pair p ``shuffles`` uniform-looking permutations of ``0 ..
+    columns[p] - 1``, as ``(order int32, order_ptr int64 [P + 1])`` the way ``null_scores`` and
+    ``gfy_align_local_null`` take them: pair p's orders lie back to back from ``order_ptr[p]``,
+    ``columns[p]`` entries each, ``order_ptr[p] = shuffles * sum(columns[:p])``.
+
+    The result is a fixed function of ``(seed, v, j)``, ``v = p * shuffles + k`` (the formula is
+    at the head of this module and in include/gfy.h): the entries of virtual pair v are ``0 ..
+    columns[p] - 1`` stably sorted by ``(key(seed, v, j), j)``, so a segment depends on its own
+    ``(seed, v)`` and length alone, not on what stands before or behind it, and numpy ``uint64``
+    reproduces it.  No ``torch.Generator`` is used.  ``seed`` is any integer, taken modulo 2^64.
+
+    ``device=None`` gives CPU tensors; on a device the scans and the one stable sort run there,
+    and the bytes are the same.  ``columns`` is a host array (a list, numpy, or a torch tensor,
+    which is copied to the host); ``P * shuffles`` must stay below 2^31."""
+    columns = _checked_columns(columns)
+    shuffles = _checked_integer(shuffles, "shuffles", 1)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError("seed must be an integer")
+    virtual = columns.size * shuffles
+    if virtual >= 2 ** 31:
+        raise ValueError(f"P * shuffles = {columns.size} * {shuffles} must stay below 2^31")
+    device = torch.device("cpu" if device is None else device)
+    total = int(columns.sum()) * shuffles
+    order_ptr = torch.from_numpy(np.concatenate(([0], np.cumsum(columns) * shuffles))).to(device)
+    if total == 0:
+        return torch.zeros(0, dtype=torch.int32, device=device), order_ptr
+    lengths = torch.from_numpy(np.repeat(columns, shuffles)).to(device)          # [P * shuffles]
+    first = torch.cumsum(lengths, 0) - lengths
+    v = torch.repeat_interleave(torch.arange(virtual, device=device), lengths, output_size=total)
+    j = torch.arange(total, device=device) - first[v]
+    keys = _mixed(_mixed((v + 1) * _signed(_GOLDEN) + _signed(int(seed)))
+                  + (j + 1) * _signed(_GOLDEN))
+    # one stable sort by (virtual pair, key, j): the elements stand in (virtual pair, j) order
+    where = torch.sort((v << 32) | _shifted(keys, 32), stable=True).indices
+    return j[where].to(torch.int32), order_ptr
+
+
+def _checked_orders(orders, columns: np.ndarray, shuffles: int) -> tuple:
+    """``orders`` as ``(order, order_ptr)`` tensors wherever they live, or the ``ValueError``.  Of
+    arrays only type and shape are looked at: what they hold is the kernel's to check."""
+    if not isinstance(orders, (tuple, list)) or len(orders) != 2:
+        raise ValueError("orders must be a pair (order, order_ptr), as shuffle_orders returns it")
+    tensors = []
+    for values, name in zip(orders, ("order", "order_ptr")):
+        if isinstance(values, np.ndarray):
+            values = torch.from_numpy(np.ascontiguousarray(values))
+        if not isinstance(values, torch.Tensor):
+            raise ValueError(f"orders: {name} must be a numpy array or a torch tensor")
+        tensors.append(values)
+    order, order_ptr = tensors
+    total = int(columns.sum()) * shuffles
+    if order.dtype != torch.int32 or order.shape != (total,):
+        raise ValueError(f"orders: order must be an int32 array of shape (shuffles * the columns "
+                         f"of all pairs,) = ({total},)")
+    if order_ptr.dtype != torch.int64 or order_ptr.shape != (columns.size + 1,):
+        raise ValueError(f"orders: order_ptr must be an int64 array of shape (P + 1,) = "
+                         f"({columns.size + 1},)")
+    return order, order_ptr
+
+
+def null_scores(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
+                match_scale=1.0, match_shift=0.0, band=None, box=None, shuffles=None, seed=0,
+                orders=None, workspace: AlignWorkspace | None = None) -> torch.Tensor:
+    """The null of ``local_align``: every pair aligned ``shuffles`` times against its own b-side
+    with the rows in another order each time, ``float32 [P, shuffles]`` on the device, in one
+    launch and without a shuffled row being written (the head of this module says why and how).
+
+    The arguments of ``local_align`` keep their meaning, ``band`` and ``box`` included: the
+    b-side of a pair is its b-record, or with a ``box`` rows ``j_lo .. j_hi`` of it (clipped), and
+    only those are shuffled, among themselves.  ``shuffles`` is required and has no default
+    worth having: it decides the resolution of everything ``significance`` makes of the result.
+    ``seed`` names the orders (``shuffle_orders(call's columns, shuffles, seed)``, made on the
+    device).  ``orders=(order, order_ptr)`` replaces them with the caller's own, in the layout
+    ``shuffle_orders`` documents: a reversal, a bootstrap with repeats, or the identity, under
+    which the result is ``local_align``'s score.  Result ``[p, k]`` equals, bit for bit,
+    ``local_align`` of pair p with its b-side replaced by the rows ``order[...]`` copied out in
+    the order of run k, and depends neither on the other pairs or runs of the call nor on the
+    workspace.
+
+    Every argument error is a ``ValueError`` before a device is touched: those of
+    ``local_align``, a ``shuffles`` that is missing or no positive integer, ``P * shuffles`` of
+    2^31 or more, a ``seed`` that is no integer, ``orders`` that is no pair of an int32 array of
+    ``shuffles * sum(columns)`` entries and an int64 array of ``P + 1``.  What ``orders`` HOLDS is
+    not read here, because that would wait for the device: a pair whose ``order_ptr`` does not
+    step by ``shuffles * columns`` gets NaN in all its runs, a run with an entry outside ``0 ..
+    columns - 1`` gets NaN, and nothing outside the arrays is read for either.  ``P == 0``
+    returns ``[0, shuffles]`` without a launch; an ``AlignWorkspace`` serves this function too."""
+    if shuffles is None:
+        raise ValueError("shuffles is required: it has no default")
+    shuffles = _checked_integer(shuffles, "shuffles", 1)
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):
+        raise ValueError("seed must be an integer")
+    call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
+                         match_shift, band, box)
+    count = call.pairs.shape[0]
+    if count * shuffles >= 2 ** 31:
+        raise ValueError(f"P * shuffles = {count} * {shuffles} must stay below 2^31")
+    columns = call.box_columns.astype(np.int64)
+    if orders is not None:
+        orders = _checked_orders(orders, columns, shuffles)
+    call = call.on_device()
+    device = call.a.device
+    with torch.cuda.device(device):
+        scores = torch.zeros((count, shuffles), dtype=torch.float32, device=device)
+        if call.empty:
+            return scores
+        order, order_ptr = orders if orders is not None else \
+            shuffle_orders(columns, shuffles, seed, device)
+        order, order_ptr = order.to(device).contiguous(), order_ptr.to(device).contiguous()
+        if order.numel() == 0:                   # no b-side has a row: NULL is no array
+            order = torch.zeros(1, dtype=torch.int32, device=device)
+        lib, name = native.library(), "gfy_align_local_null"
+        need = lib.gfy_align_workspace_bytes(count * shuffles, int(columns.max()))
+        scratch = (workspace or AlignWorkspace()).buffer(device, need)
+        native.check(getattr(lib, name)(
+            *call.arguments()[:14],
+            None if call.band is None else call.band_dev.data_ptr(),
+            None if call.box is None else call.box_dev.data_ptr(),
+            shuffles, order.data_ptr(), order_ptr.data_ptr(), scores.data_ptr(),
+            *_scratch_tail(scratch, device)), name)
+    return scores
+
+
+class Significance(NamedTuple):
+    """What ``significance`` returns: float64 ``[P]`` tensors on the device of ``null``."""
+    z: torch.Tensor          # (score - mean) / std
+    mean: torch.Tensor       # of the pair's null scores
+    std: torch.Tensor        # their K - 1 standard deviation
+    p_value: torch.Tensor    # P(a null score >= score) under the fitted Gumbel distribution
+    lam: torch.Tensor        # the Gumbel scale parameter lambda
+    mu: torch.Tensor         # the Gumbel location
+
+
+_EULER_GAMMA = 0.5772156649015329
+
+
+def significance(scores, null) -> Significance:
+    """The real ``scores`` (``[P]``) against their ``null`` scores (``[P, K]``, ``K >= 2``, what
+    ``null_scores`` returned): ``Significance(z, mean, std, p_value, lam, mu)``, float64 ``[P]``
+    tensors on the device of ``null``.  All in float64, per row of ``null``:
+
+        mean    = sum(null) / K
+        std     = sqrt(sum((null - mean)^2) / (K - 1))
+        z       = (score - mean) / std
+        lam     = pi / (std * sqrt(6))                   the Gumbel fit by moments
+        mu      = mean - gamma / lam                     gamma = 0.5772156649015329
+        p_value = -expm1(-exp(-lam * (score - mu)))      = 1 - exp(-exp(-lam (score - mu)))
+
+    The best local score of unrelated sequences follows an extreme-value (Gumbel) distribution,
+    which is why the p-value is read off a Gumbel fitted to the null and not off a normal one;
+    ``z`` is the plain distance in standard deviations.  These are ESTIMATES FROM K SAMPLES, and K
+    decides their resolution: the mean and the deviation carry a relative error of about
+    ``1 / sqrt(K)`` and ``1 / sqrt(2 K)``, and a p-value far below ``1 / K`` is an extrapolation
+    of the fitted tail that no sample has seen.
+
+    Nothing is raised for what the numbers hold.  Where ``std == 0`` (a constant row) the
+    results are the plain IEEE ones: ``z`` is ``+-inf`` or NaN, ``lam`` is ``inf``, ``mu == mean``,
+    ``p_value`` is 0 above the mean, 1 below it and NaN on it.  A NaN in a row of ``null`` (a
+    refused pair) makes all six NaN for that row; a NaN score makes its ``z`` and ``p_value`` NaN.
+    ``K < 2``, or shapes that do not match, are a ``ValueError``."""
+    if isinstance(null, np.ndarray):
+        null = torch.from_numpy(np.ascontiguousarray(null))
+    if not isinstance(null, torch.Tensor) or null.dim() != 2 or not null.dtype.is_floating_point:
+        raise ValueError("null must be a floating-point array of shape (P, K)")
+    if null.shape[1] < 2:
+        raise ValueError(f"null must hold at least 2 scores per pair, not K = {null.shape[1]}: "
+                         "one sample has no deviation")
+    if isinstance(scores, np.ndarray):
+        scores = torch.from_numpy(np.ascontiguousarray(scores))
+    if not isinstance(scores, torch.Tensor) or scores.shape != (null.shape[0],) \
+            or not scores.dtype.is_floating_point:
+        raise ValueError(f"scores must be a floating-point array of shape (P,) = "
+                         f"({null.shape[0]},), one score per row of null")
+    null = null.to(torch.float64)
+    scores = scores.to(device=null.device, dtype=torch.float64)
+    count = null.shape[1]
+    mean = null.sum(dim=1) / count
+    std = torch.sqrt(((null - mean[:, None]) ** 2).sum(dim=1) / (count - 1))
+    z = (scores - mean) / std
+    lam = math.pi / (std * math.sqrt(6.0))
+    mu = mean - _EULER_GAMMA / lam
+    p_value = -torch.expm1(-torch.exp(-lam * (scores - mu)))
+    return Significance(z, mean, std, p_value, lam, mu)
 
 
 def path_cells(ops, start) -> np.ndarray:

@@ -3,8 +3,9 @@
 // end) and k_align_trace (align_trace.hip, kTrace: the aligned path of a given box), their three
 // twins inside a band of diagonals (align_band.hip, | kBand), the score and span kernels inside
 // a box of rows the caller names (align_box.hip, | kBand | kBox), the two global kernels
-// (kGlobal) and their twins inside such a box (align_global_box.hip, | kBox), as
-// pairwise_topk.inc is shared by the top-k family.
+// (kGlobal) and their twins inside such a box (align_global_box.hip, | kBox), and the score
+// kernel of shuffled b-sides (align_null.hip, kBand | kBox | kOrder), as pairwise_topk.inc is
+// shared by the top-k family.
 //
 // One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
 // wave takes pairs wave, wave + waves of the grid, ... until the list ends.
@@ -48,7 +49,7 @@ static_assert(kRingBytes == kBuffers * (kSub * 256), "a quarter of the ring stag
 static_assert(kAlignLds <= 160 * 1024, "the LDS of a compute unit");
 static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an origin fit its word");
 
-// (AlignArgs and TraceArgs, the kernels' arguments: gfy_common.h)
+// (AlignArgs, TraceArgs and OrderArgs, the kernels' arguments: gfy_common.h)
 
 // The modes of align_pairs<kMode>, or-ed together.  A mode that is not set costs nothing: behind
 // `if constexpr` none of its code exists.
@@ -61,7 +62,10 @@ static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an or
 //            records' coordinates; with kBand (a call without a band has the covering one) or
 //            with kGlobal (no band: the box's edges are the charged or free borders), and with
 //            kTrace only next to kGlobal
-enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8, kBox = 16 };
+//   kOrder   column j of a pair's matrix holds row order[j] of the pair's b-side, and the call
+//            runs over virtual pairs v = p * shuffles + k, each under an order of its own;
+//            score only, with kBand and kBox, where a null `boxes` is the covering box
+enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8, kBox = 16, kOrder = 32 };
 
 // a carry entry: (H, F) of a column, and with kSpan their origins behind them
 template <bool kSpan>
@@ -97,6 +101,7 @@ struct AlignPair {
   int box_i, box_j;      // kBox: the box's first cell in the records' coordinates
   int64_t op_lo;         // kTrace: where the pair's slot starts
   int dir_pitch;         // kTrace: words of a row of the box
+  const int32_t* order;  // kOrder: the lr entries of the virtual pair, every one in 0 .. lr - 1
 };
 
 // The pair, wave-uniformly: its records compared and clipped, and what the modes add to it.
@@ -121,11 +126,25 @@ struct AlignPair {
 //     definition are the rows just outside it and the loop needs nothing more.
 //   kTrace, kGlobal and kBox: the caller's box is applied FIRST, and the checks of kTrace and
 //     kGlobal then run on the box's sizes, with the given end shifted by -(i_lo, j_lo).
+//   kOrder: `pair` is the virtual pair v = p * shuffles + k (p.P counts those); the records, the
+//     band and the box are pair p's, and a null `boxes` is the covering box.  The b-side has
+//     `side` columns: the b-rows of the box clipped into the record, whatever the a-side holds.
+//     The orders of pair p lie back to back from order_ptr[p], `side` entries each; an order_ptr
+//     that is negative or whose difference is not shuffles * side is refused, and so is a virtual
+//     pair with an entry outside 0 .. side - 1: the 64 lanes read its entries once, here, before
+//     any of them becomes an address.  (load_b compares again where it forms the address.)
 template <unsigned kMode>
 __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs* trace,
-                                             bool within, int64_t pair, AlignPair& pr) {
+                                             const OrderArgs* orders, bool within, int64_t pair,
+                                             AlignPair& pr) {
   constexpr bool kTrace = kMode & AlignMode::kTrace, kGlobal = kMode & AlignMode::kGlobal;
   constexpr bool kBand = kMode & AlignMode::kBand, kBox = kMode & AlignMode::kBox;
+  constexpr bool kOrder = kMode & AlignMode::kOrder;
+  int shuffle = 0;   // kOrder: k of the virtual pair
+  if constexpr (kOrder) {
+    shuffle = (int)(pair % orders->shuffles);
+    pair /= orders->shuffles;
+  }
   const int q = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair]);
   const int rec = __builtin_amdgcn_readfirstlane(p.pairs[2 * pair + 1]);
   bool ok = (uint32_t)q < (uint32_t)p.records_a && (uint32_t)rec < (uint32_t)p.records_b;
@@ -134,10 +153,14 @@ __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs
   int i_lo = 0, i_hi = 0, j_lo = 0, j_hi = 0;   // kBox: the box, from here on clipped
   if constexpr (kBox) {
     constexpr int most = GFY_ALIGN_ROWS_MAX;
-    i_lo = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair]);
-    i_hi = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 1]);
-    j_lo = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 2]);
-    j_hi = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 3]);
+    if (kOrder && p.boxes == nullptr) {   // a call without a box: the covering one
+      i_lo = -most, i_hi = most, j_lo = -most, j_hi = most;
+    } else {
+      i_lo = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair]);
+      i_hi = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 1]);
+      j_lo = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 2]);
+      j_hi = __builtin_amdgcn_readfirstlane(p.boxes[4 * pair + 3]);
+    }
     ok = ok && i_lo <= i_hi && j_lo <= j_hi;
     i_lo = i_lo < -most ? -most : i_lo > most ? most : i_lo;
     i_hi = i_hi < -most ? -most : i_hi > most ? most : i_hi;
@@ -163,6 +186,7 @@ __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs
        (kTrace || kBox || b_hi - b_lo <= p.cap);
   pr.op_lo = 0;
   pr.box_i = 0, pr.box_j = 0;
+  pr.order = nullptr;
   if constexpr (kBox) {
     // the box inside the records; a record of more than GFY_ALIGN_ROWS_MAX rows is refused above
     const int full_q = ok ? (int)(a_hi - a_lo) : 0, full_r = ok ? (int)(b_hi - b_lo) : 0;
@@ -173,6 +197,19 @@ __device__ __forceinline__ void resolve_pair(const AlignArgs& p, const TraceArgs
     const bool box = ok && i_lo <= i_hi && j_lo <= j_hi;   // it holds a cell
     const int box_rows = box ? i_hi - i_lo + 1 : 0, box_cols = box ? j_hi - j_lo + 1 : 0;
     ok = ok && box_cols <= p.cap;
+    if constexpr (kOrder) {
+      const int side = ok && j_lo <= j_hi ? j_hi - j_lo + 1 : 0;
+      int64_t first = 0, behind = 0;
+      if (ok) first = orders->order_ptr[pair], behind = orders->order_ptr[pair + 1];
+      ok = ok && first >= 0 && behind - first == (int64_t)orders->shuffles * side;
+      const int32_t* mine = orders->order + first + (int64_t)shuffle * side;
+      bool wrong = false;
+      if (ok)
+        for (int x = threadIdx.x & 63; x < side; x += 64)
+          wrong = wrong || (uint32_t)mine[x] >= (uint32_t)side;
+      ok = ok && __builtin_amdgcn_ballot_w64(wrong) == 0;
+      pr.order = mine;
+    }
     pr.box_i = box ? i_lo : 0, pr.box_j = box ? j_lo : 0;
     if constexpr (kBand) {   // the band in the box's coordinates
       lo -= pr.box_j - pr.box_i;
@@ -325,7 +362,7 @@ __device__ __forceinline__ void trace_walk(int lane, char* ring, const uint32_t*
   }
 }
 
-// The pair's result.  kGlobal: the last cell, or (within) the first best cell of the last row:
+// The pair's result (kOrder: the virtual pair's, the score alone).  kGlobal: the last cell, or (within) the first best cell of the last row:
 // one lane holds either.  Otherwise one butterfly orders the lanes' best cells by (score
 // descending, i ascending, j ascending), and with kSpan the origin goes along.  kBox: the cells
 // of a positive score (kGlobal: a real end) go back into the records' coordinates; (-1, -1) and
@@ -336,7 +373,7 @@ __device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const 
                                             float best, int best_i, int best_j,
                                             uint32_t best_o, int32_t* out_start) {
   constexpr bool kSpan = kMode & AlignMode::kSpan, kGlobal = kMode & AlignMode::kGlobal;
-  constexpr bool kBox = kMode & AlignMode::kBox;
+  constexpr bool kBox = kMode & AlignMode::kBox, kOrder = kMode & AlignMode::kOrder;
   const bool ok = pr.ok;
   if constexpr (kGlobal) {
     const int owner = (pr.lq - 1) & (kStrip - 1);
@@ -376,8 +413,10 @@ __device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const 
         start_i += pr.box_i, start_j += pr.box_j;
       }
       p.out_score[pair] = ok ? (none ? 0.f : best) : __builtin_nanf("");
-      p.out_end[2 * pair] = ok ? (none ? -1 : best_i) : -2;
-      p.out_end[2 * pair + 1] = ok ? (none ? -1 : best_j) : -2;
+      if constexpr (!kOrder) {   // kOrder: a cell of a shuffled matrix names no row of the record
+        p.out_end[2 * pair] = ok ? (none ? -1 : best_i) : -2;
+        p.out_end[2 * pair + 1] = ok ? (none ? -1 : best_j) : -2;
+      }
       if constexpr (kSpan) {
         out_start[2 * pair] = ok ? (none ? -1 : start_i) : -2;
         out_start[2 * pair + 1] = ok ? (none ? -1 : start_j) : -2;
@@ -388,13 +427,18 @@ __device__ __forceinline__ void finish_pair(const AlignArgs& p, int lane, const 
 
 // out_start ([P][2]) is written with kSpan, and with kTrace and kGlobal together; trace is read
 // with kTrace alone, within (wave-uniform) with kGlobal alone, p.bands with kBand alone, p.boxes
-// with kBox alone
+// with kBox alone, orders with kOrder alone (p.P then counts the virtual pairs and p.out_end is
+// not written)
 template <unsigned kMode>
 __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_start,
                                             const TraceArgs* trace = nullptr,
-                                            bool within = false) {
+                                            bool within = false,
+                                            const OrderArgs* orders = nullptr) {
   constexpr bool kSpan = kMode & AlignMode::kSpan, kTrace = kMode & AlignMode::kTrace;
   constexpr bool kGlobal = kMode & AlignMode::kGlobal, kBand = kMode & AlignMode::kBand;
+  constexpr bool kOrder = kMode & AlignMode::kOrder;
+  static_assert(!kOrder || kMode == (AlignMode::kBand | AlignMode::kBox | AlignMode::kOrder),
+                "orders come with the one score kernel that takes a band, a box, both or neither");
   static_assert(!(kSpan && kTrace), "the trace runs on the plain (H, F) carry");
   static_assert(!(kSpan && kGlobal), "a global alignment starts at the matrix's corner");
   static_assert(!(kBand && kGlobal), "a band on the global modes: borders that leave the band");
@@ -427,7 +471,7 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
 
   for (int64_t pair = slot; pair < p.P; pair += slots) {
     AlignPair pr;
-    resolve_pair<kMode>(p, trace, within, pair, pr);
+    resolve_pair<kMode>(p, trace, orders, within, pair, pr);
     const int lq = pr.lq, lr = pr.lr, lo = pr.lo, hi = pr.hi, dir_pitch = pr.dir_pitch;
     const f16* rows_a = pr.rows_a;
     const f16* rows_b = pr.rows_b;
@@ -439,14 +483,34 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
     float h_last = 0.f;                    // kTrace, kGlobal: a lane's H when its strip ended
     float left_run = 0.f;                  // kGlobal: H[i0 - 1][-1], down the left border
 
+    // kOrder: the rows that the columns of the NEXT load_b hold, order[col] for this lane's eight
+    // columns.  They are loaded one tile ahead of the rows, as the rows are one tile ahead of the
+    // multiply, so the dependent load stands in front of the prefetch and not in the step loop.
+    int rows_next[kOrder ? 8 : 1];
+    auto load_order = [&](int c0) __attribute__((always_inline)) {
+      if constexpr (kOrder) {
+#pragma unroll
+        for (int x = 0; x < 8; ++x) {
+          const int col = c0 + (lane >> 4) + 4 * x;
+          rows_next[x] = col < lr ? pr.order[col] : 0;
+        }
+      }
+    };
     // 32 b-rows from column c0 on as this lane's eight 16-byte pieces: piece lane + 64 x is
-    // chunk lane & 15 of row (lane >> 4) + 4 x — a row on 16 consecutive lanes (row_square_sum)
+    // chunk lane & 15 of row (lane >> 4) + 4 x — a row on 16 consecutive lanes (row_square_sum).
+    // kOrder: the row of column col is rows_next's, compared once more before it is an address.
     auto load_b = [&](f16x8 (&v)[8], int c0) __attribute__((always_inline)) {
 #pragma unroll
       for (int x = 0; x < 8; ++x) {
         const int col = c0 + (lane >> 4) + 4 * x;
         v[x] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        if (col < lr) v[x] = *reinterpret_cast<const f16x8*>(rows_b + (int64_t)col * 128 + (lane & 15) * 8);
+        if constexpr (kOrder) {
+          const int row = rows_next[x];
+          if (col < lr && (uint32_t)row < (uint32_t)lr)
+            v[x] = *reinterpret_cast<const f16x8*>(rows_b + (int64_t)row * 128 + (lane & 15) * 8);
+        } else {
+          if (col < lr) v[x] = *reinterpret_cast<const f16x8*>(rows_b + (int64_t)col * 128 + (lane & 15) * 8);
+        }
       }
     };
 
@@ -517,7 +581,9 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       uint32_t o_h = 0, o_e = 0, o_f = 0, o_diag = 0;   // kSpan: their origins
       uint32_t dir_word = 0;                            // kTrace: the row's 8 columns in the making
       f16x8 b_next[8];
+      load_order(t_first);
       load_b(b_next, t_first);
+      load_order(t_first + kSub);
       // the carry entries of the row above the strip for columns c0 + lane, lanes 0..31: the
       // strip's last row comes back to lane 0 of the next strip 32 columns at a time, one load
       // ahead, from the two buffers in turn
@@ -592,7 +658,10 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
           wave_sync();
           f32x16 acc[2];
           sweep_multiply<2, false>(acc, af, stage, 0, 0, r, hq);
-          if (kBand ? t0 + kSub <= c_hi : t0 + kSub < lr) load_b(b_next, t0 + kSub);
+          if (kBand ? t0 + kSub <= c_hi : t0 + kSub < lr) {
+            load_b(b_next, t0 + kSub);
+            load_order(t0 + 2 * kSub);
+          }
 #pragma unroll
           for (int g = 0; g < 4; ++g) {
             const int jl = 4 * hq + 8 * g;   // 4 consecutive b-rows

@@ -1189,6 +1189,36 @@ int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int
 }
 #undef GFY_REQUIRE_BOXES
 
+// Null scores (align_null.hip): the boxed score call's checks in its order with `bands` and
+// `boxes` both free to be NULL, the orders named like outputs, and then what the virtual pairs
+// add.
+int gfy_align_local_null(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs, int64_t P, float match_scale, float match_shift,
+                         float gap_open, float gap_extend, const int32_t* bands,
+                         const int32_t* boxes, int64_t shuffles, const int32_t* order,
+                         const int64_t* order_ptr, float* out_score, void* ws, size_t ws_bytes,
+                         void* stream) {
+  clear_error();
+  AlignArgs call;
+  if (const int rc = checked_align_call(
+          "gfy_align_local_null",
+          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
+           gap_open, gap_extend},
+          {{order, "order"}, {order_ptr, "order_ptr"}, {out_score, "out_score"}}, ws, &call))
+    return rc;
+  GFY_REQUIRE(shuffles >= 1, GFY_ERR_INVALID, "gfy_align_local_null: shuffles = %lld is below 1",
+              (long long)shuffles);
+  GFY_REQUIRE(shuffles <= INT32_MAX / P, GFY_ERR_INVALID,
+              "gfy_align_local_null: P * shuffles = %lld * %lld outside 1..2^31 - 1", (long long)P,
+              (long long)shuffles);
+  call.bands = bands;
+  call.boxes = boxes;
+  call.out_score = out_score;
+  OrderArgs orders{order, order_ptr, (int)shuffles};
+  return launch_align_local_null(call, orders, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                      const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                      const int32_t* pairs, int64_t P, float match_scale, float match_shift,

@@ -402,6 +402,15 @@ struct TraceArgs {
   int64_t region_words;    // direction words a wave's region holds
 };
 
+// what k_align_local_null takes next to AlignArgs (whose out_end it leaves alone): every pair is
+// aligned `shuffles` times, each time with the rows of its b-side in an order of its own
+struct OrderArgs {
+  const int32_t* order;       // entries 0 .. columns_p - 1: column j holds b-side row order[j]
+  const int64_t* order_ptr;   // [P + 1]: pair p's orders lie back to back from order_ptr[p],
+                              // shuffles of them, columns_p entries each
+  int shuffles;
+};
+
 // align_local.hip
 int launch_align_local(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
 size_t align_workspace_bytes(int64_t pairs, int64_t max_rows_b);
@@ -437,6 +446,12 @@ int launch_align_trace_band(const AlignArgs& call, const TraceArgs& trace, int64
 int launch_align_local_box(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
 int launch_align_local_span_box(const AlignArgs& call, int32_t* out_start, void* ws,
                                 size_t ws_bytes, hipStream_t s);
+// align_null.hip: the score call of align_box.hip on every pair `orders.shuffles` times, each
+// under an order of its b-side's rows; call.bands and call.boxes may each be null (the covering
+// one), call.out_score is [P][shuffles], call.out_end is not written; the workspace is
+// align_workspace_bytes of P * shuffles pairs
+int launch_align_local_null(const AlignArgs& call, const OrderArgs& orders, void* ws,
+                            size_t ws_bytes, hipStream_t s);
 // align_global_box.hip: the two global calls inside a box of rows per pair (call.boxes, no band);
 // the workspaces are align_workspace_bytes with the widest box's columns and
 // align_global_trace_workspace_bytes with the largest box's rows and columns

@@ -662,8 +662,8 @@ int gfy_pairwise_within_fill(const void* a, int64_t n, const void* b, int64_t m,
  *               four parameters finite; 1 <= P < 2^31.  Rows holding inf / NaN give unspecified
  *               values.  The start cell is gfy_align_local_span's and the aligned path
  *               gfy_align_trace's; global and query-in-target alignment are gfy_align_global's;
- *               alignment inside a band of diagonals is gfy_align_local_band's; no normalisation
- *               of scores.
+ *               alignment inside a band of diagonals is gfy_align_local_band's; what a raw score
+ *               means against shuffled targets is gfy_align_local_null's.
  *   Workspace   gfy_align_workspace_bytes(pairs, max_rows_b), max_rows_b the longest b-record any
  *               pair names: the last row of a 64-row strip of A, per wave in flight.
  *   ptr_a, ptr_b and pairs are device arrays, which the kernel only compares and clips.  A pair
@@ -714,7 +714,7 @@ int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
  *   Arguments, clipping of what the device arrays hold and error codes are those of
  *   gfy_align_local; a NULL out_start is GFY_ERR_INVALID and named.
  *   The aligned path itself is gfy_align_trace's; global alignment is gfy_align_global's; a band
- *   is gfy_align_local_span_band's; no normalisation of scores.                               */
+ *   is gfy_align_local_span_band's; null scores are gfy_align_local_null's.                   */
 size_t gfy_align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
 int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
@@ -931,6 +931,68 @@ int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int
                              int32_t* out_end /* [P][2] */,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* NULL SCORES of local alignment: every pair aligned `shuffles` times against its own b-side with
+ * the rows in another order each time, in one launch and without writing a shuffled row.  A raw
+ * local score grows with the two lengths and depends on the four parameters and on how ordinary
+ * the two records' rows are; there is no scoring matrix here to look a lambda and a K up for.
+ * The answer is empirical: the real score against the scores of the same pair with the target's
+ * rows in random order.  The arguments are gfy_align_local_box's with `shuffles`, `order` and
+ * `order_ptr` behind `boxes`, and without out_end.
+ *   B-side      of pair p: the rows of its b-record, or with a box rows j_lo .. j_hi of it after
+ *               clipping (gfy_align_local_box).  It has columns_p rows, whatever the a-side holds.
+ *   Orders      order is int32, order_ptr int64 [P + 1], both in device memory.  The `shuffles`
+ *               orders of pair p lie back to back from order[order_ptr[p]] on, columns_p entries
+ *               each.  In run k COLUMN j OF THE PAIR'S MATRIX HOLDS ROW order[order_ptr[p] + k *
+ *               columns_p + j] OF THE B-SIDE; entries are relative to the b-side, 0 .. columns_p -
+ *               1.  Nothing else changes: the a-side, s[i][j] (the cosine of row i with the row
+ *               that the column holds, its 1/|b| taken from that row), the recurrences, every
+ *               rounded operation, the band (diagonals of the matrix as it stands, in the records'
+ *               coordinates) and the box.  Entries need not be a permutation: repeats are legal
+ *               (a bootstrap of the target's rows).
+ *   Result      out_score[p][k], [P][shuffles] row-major, the local score of run k.  There is no
+ *               end: a cell of a shuffled matrix names no row of the record.
+ *   Identity    out_score[p][k] equals, bit for bit, gfy_align_local (or _band / _box) of the pair
+ *               with the b-side replaced by the rows order[...] copied out in that order.  A cell
+ *               is a fixed expression of its predecessors, and a cosine is a fixed function of
+ *               its two rows.  The order 0, 1, .. columns_p - 1 gives gfy_align_local_box's score.
+ *   bands, boxes  each may be NULL: the covering band, the covering box.  Band, box, both or
+ *               neither are one kernel.
+ *   Refusals    order and order_ptr are device arrays, which the kernel only compares and clips,
+ *               as it does pairs.  A pair with order_ptr[p] < 0 or order_ptr[p + 1] - order_ptr[p]
+ *               != shuffles * columns_p gets NaN in all its runs; a run with an entry outside 0 ..
+ *               columns_p - 1 gets NaN, and the other runs are not affected; a pair that
+ *               gfy_align_local_box refuses gets NaN in all its runs.  The range test comes before
+ *               an entry becomes an address: a refused run causes no access outside the caller's
+ *               buffers.  (order_ptr is trusted to lie inside order, as op_ptr is inside out_ops.)
+ *   Workspace   gfy_align_workspace_bytes(P * shuffles, max columns_p): the launch runs over the
+ *               virtual pairs v = p * shuffles + k, one wave each, by the grid and carry rules of
+ *               the score calls.
+ *   Orders for a null: ginfinity_amd.align.shuffle_orders makes them, a fixed function of (seed,
+ *               v, j) that anything with 64-bit integers reproduces.  With mix(z): z ^= z >> 30;
+ *               z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31 (all
+ *               modulo 2^64, >> logical) and G = 0x9E3779B97F4A7C15,
+ *                   key(seed, v, j) = mix(mix(seed + (v + 1) * G) + (j + 1) * G) >> 32,
+ *               and the order of virtual pair v is 0 .. columns - 1 sorted by (key, j).
+ *   What the scores become (z-score, Gumbel fit, p-value) is host arithmetic on [P][shuffles]
+ *   numbers: ginfinity_amd.align.significance states its formulas.
+ *   A NULL a, b, ptr_a, ptr_b, pairs, order, order_ptr, out_score or workspace (named in
+ *   gfy_last_error), shuffles < 1, P * shuffles outside 1..2^31 - 1 and what gfy_align_local
+ *   refuses are GFY_ERR_INVALID, a workspace shorter than gfy_align_workspace_bytes(P * shuffles,
+ *   0) is GFY_ERR_WORKSPACE; all of it before any launch and without a device.  Out of scope:
+ *   nulls for the global and query-in-target modes, orders of the a-side, start, end or path of a
+ *   run, an E-value calibrated over a whole database search.
+ *   Cost: DESIGN.md §4.                                                                        */
+int gfy_align_local_null(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
+                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
+                         const int32_t* pairs /* [P][2] device */, int64_t P,
+                         float match_scale, float match_shift, float gap_open, float gap_extend,
+                         const int32_t* bands /* [P][2] device, or NULL */,
+                         const int32_t* boxes /* [P][4] device, or NULL */,
+                         int64_t shuffles, const int32_t* order /* device */,
+                         const int64_t* order_ptr /* [P + 1] device */,
+                         float* out_score /* [P][shuffles] */,
+                         void* workspace, size_t workspace_bytes, void* stream);
+
 /* GLOBAL and QUERY-IN-TARGET alignment of record pairs: the recurrences of gfy_align_local with
  * charged borders and without the 0 candidate.  within = 0 aligns both records end to end
  * (Needleman-Wunsch with affine gaps): unrelated flanks are charged for, not ignored.  within = 1
@@ -964,7 +1026,8 @@ int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int
  *   Arguments and error codes are those of gfy_align_local; a within other than 0 or 1 is
  *   GFY_ERR_INVALID.  A box of rows on these modes is gfy_align_global_box's.  Out of scope: a
  *   band on these modes (the gfy_align_*_band calls are local only), free ends on the a-side, a
- *   span-only call for these modes, normalisation of scores.
+ *   span-only call for these modes, null scores for these modes (gfy_align_local_null is local
+ *   only).
  *   Cost: DESIGN.md §4.                                                                       */
 int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                      const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,

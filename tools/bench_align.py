@@ -62,7 +62,19 @@ boxed, that made its paths, on the pairs of ``--box``.  The document (default
 profiles/path_values_bench.json) holds the two medians, their ratio, the ops and how many of the
 scores are those of ``local_paths`` bit for bit (all of them should be).  No ratio is set.
 
+``--null K --box MARGIN`` times ``align.null_scores`` (K shuffles of every pair's b-side, one launch)
+on the pairs and boxes of ``--box``, with the making of its orders and with the orders given,
+next to two routes that need no such call: (a) K calls of ``local_align`` on the same boxed pairs
+(the same cells, nothing shuffled) and (b) a torch gather of the shuffled rows into ``pairs x K``
+records of their own plus one ``local_align`` on them, the gather timed with it and its bytes
+reported.  Without ``--band`` there is no band; ``--band W`` puts W diagonals around every
+region's diagonal, in all routes.  The document (default profiles/align_null_bench.json) holds
+the medians, their ratios to ``null_scores``, the bytes of the orders and of the gathered rows,
+and how many scores of the gathered route ``null_scores`` gives bit for bit (all of them should
+be).  No ratio is set.
+
     python tools/bench_align.py --pairs 20000
+    python tools/bench_align.py --pairs 2000 --records 64 --null 20 --box 16
     python tools/bench_align.py --pairs 2000 --records 64 --values --box 16
     python tools/bench_align.py --pairs 2000 --records 64 --box 16
     python tools/bench_align.py --pairs 2000 --records 64 --global --within --box 16
@@ -100,6 +112,7 @@ BOX_SOURCES = ("align_local.inc", "align_band.hip", "align_box.hip")      # --bo
 GLOBAL_BOX_SOURCES = ("align_local.inc", "align_global.hip", "align_global_trace.hip",
                       "align_global_box.hip", "align_box.hip")           # --global / --within --box
 VALUE_SOURCES = ("align_values.hip", "pairwise_sweep.inc")               # --values
+NULL_SOURCES = ("align_local.inc", "align_null.hip", "align_box.hip")    # --null
 BOX_RECORD_ROWS = 4096            # --box: rows of every record
 BOX_REGION_ROWS = 150             # --box: rows of the region a pair shares
 
@@ -320,6 +333,91 @@ def _values_bench(args) -> dict:
             "scores_equal_to_local_paths": int(same.sum())}
 
 
+def _null_bench(args) -> dict:
+    """``--null K`` with ``--box``: ``null_scores`` next to K calls of ``local_align`` and next to a
+    gather of the shuffled rows with one ``local_align`` on them."""
+    a, b, counts, pairs, bands, boxes, first, last = _box_case(args)
+    rows, shuffles = BOX_RECORD_ROWS, args.null
+    if args.band:       # W diagonals around the region's diagonal; without --band no band at all
+        centre = (bands[:, 0] + bands[:, 1]) // 2
+        bands = np.stack([centre - args.band // 2, centre + args.band - 1 - args.band // 2], axis=1)
+    parameters = dict(gap_open=1.0, gap_extend=0.25, match_scale=1.0, match_shift=-0.3)
+    keeper = align.AlignWorkspace()
+    pairs_dev, box_dev = torch.from_numpy(pairs), torch.from_numpy(boxes)
+    band_dev = torch.from_numpy(bands.astype(np.int32)) if args.band else None
+    common = dict(counts_a=counts, counts_b=counts, workspace=keeper, **parameters)
+    j_lo = np.maximum(boxes[:, 2], 0).astype(np.int64)
+    columns = np.minimum(boxes[:, 3], rows - 1) - j_lo + 1
+    box_rows = np.minimum(boxes[:, 1], rows - 1) - np.maximum(boxes[:, 0], 0) + 1
+    order, order_ptr = align.shuffle_orders(columns, shuffles, 0, "cuda")
+
+    def null():
+        return align.null_scores(a, b, pairs=pairs_dev, band=band_dev, box=box_dev,
+                                 shuffles=shuffles, seed=0, **common)
+
+    def null_given():
+        return align.null_scores(a, b, pairs=pairs_dev, band=band_dev, box=box_dev,
+                                 shuffles=shuffles, orders=(order, order_ptr), **common)
+
+    def repeated():                 # (a): the same cells, the rows not shuffled
+        for _ in range(shuffles):
+            align.local_align(a, b, pairs=pairs_dev, band=band_dev, box=box_dev, **common)
+
+    # (b): every shuffled b-side as a record of its own
+    virtual = args.pairs * shuffles
+    side_first = torch.from_numpy(np.repeat(pairs[:, 1].astype(np.int64) * rows + j_lo, shuffles))
+    lengths = torch.from_numpy(np.repeat(columns, shuffles))
+    many_pairs = torch.from_numpy(np.stack([np.repeat(pairs[:, 0], shuffles),
+                                            np.arange(virtual)], axis=1).astype(np.int32))
+    many_boxes = torch.from_numpy(np.repeat(np.stack(
+        [boxes[:, 0], boxes[:, 1], np.full(args.pairs, -rows), np.full(args.pairs, rows)],
+        axis=1), shuffles, axis=0).astype(np.int32))
+    many_bands = None if not args.band else torch.from_numpy(
+        np.repeat(bands - j_lo[:, None], shuffles, axis=0).astype(np.int32))
+    many_counts = np.repeat(columns, shuffles)
+    gathered_bytes = int(columns.sum()) * shuffles * 256
+
+    def gathered():
+        base = torch.repeat_interleave(side_first.cuda(), lengths.cuda(),
+                                       output_size=int(order.shape[0]))
+        shuffled = b[base + order]
+        return align.local_align(a, shuffled, counts_a=counts, counts_b=many_counts,
+                                 pairs=many_pairs, band=many_bands, box=many_boxes,
+                                 workspace=keeper, **parameters)[0]
+
+    timed = {name: _timed(call, args.repeats, args.warmup)
+             for name, call in (("null_scores", null), ("null_scores_given_orders", null_given),
+                                ("local_align_k_times", repeated),
+                                ("gather_and_local_align", gathered))}
+    mids = {name: statistics.median(seconds) for name, seconds in timed.items()}
+    same = (null().reshape(-1).view(torch.int32) == gathered().view(torch.int32))
+    source = ROOT / "ginfinity_amd" / "csrc"
+    for name, mid in mids.items():
+        print(f"{name}: {mid:.4f} s = {mid / mids['null_scores']:.3f} x null_scores",
+              file=sys.stderr, flush=True)
+    return {"metric": "null_scores of boxed pairs of 4,096-row records that share a 150-row region: "
+                      "K shuffles of every pair's b-side in one launch, next to K calls of "
+                      "local_align and next to a gather of the shuffled rows with one local_align",
+            "pairs": args.pairs, "records": args.records, "record_rows": rows,
+            "region_rows": BOX_REGION_ROWS, "margin": args.box, "shuffles": shuffles,
+            "band_diagonals": args.band or None, "parameters": parameters,
+            "host": platform.node(),
+            "utc": datetime.datetime.now(datetime.timezone.utc).isoformat(timespec="seconds"),
+            "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
+            "torch": torch.__version__, "commit": args.commit or _commit(),
+            "source_sha256": {name: hashlib.sha256((source / name).read_bytes()).hexdigest()
+                              for name in NULL_SOURCES},
+            "command": "python tools/bench_align.py " + " ".join(_measured_arguments()),
+            "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
+            "timed": "the whole call: host checks, the uploads, the launches; null_scores with the "
+                     "making of its orders, gather_and_local_align with the gather",
+            "virtual_pairs": virtual, "cells": int((box_rows * columns).sum()) * shuffles,
+            "order_bytes": int(order.shape[0]) * 4, "gathered_bytes": gathered_bytes,
+            "seconds": {name: _span(seconds) for name, seconds in timed.items()},
+            "over_null_scores": {name: mid / mids["null_scores"] for name, mid in mids.items()},
+            "scores_equal_to_the_gathered_route": int(same.sum())}
+
+
 def _box_bench(args) -> dict:
     """``--box``: the same pairs banded, without and with the box of the planted region."""
     a, b, counts, pairs, bands, boxes, first, last = _box_case(args)
@@ -423,6 +521,11 @@ def main() -> None:
                         help="with --box: time align.path_values next to the local_paths call, "
                              "banded and boxed, that made its paths (default output "
                              "profiles/path_values_bench.json)")
+    parser.add_argument("--null", type=int, default=0, metavar="K",
+                        help="with --box (and, if wanted, --band W): time align.null_scores with K "
+                             "shuffles next to K calls of local_align and next to a gather of the "
+                             "shuffled rows plus one local_align (default output "
+                             "profiles/align_null_bench.json)")
     parser.add_argument("--whole-pairs", type=int, default=64,
                         help="with --global / --within and --box: the pairs on which global_paths "
                              "on the two whole records is timed")
@@ -441,15 +544,20 @@ def main() -> None:
         parser.error("--whole-pairs: positive")
     if args.values and (args.box is None or args.whole or args.within):
         parser.error("--values: with --box MARGIN, and without --global and --within")
+    if args.null < 0 or (args.null and (args.box is None or args.values or args.whole
+                                        or args.within)):
+        parser.error("--null K: K positive, with --box MARGIN, and without --values, --global and "
+                     "--within")
     fill = args.box is not None and (args.whole or args.within)
     if args.out is None:
         args.out = str(ROOT / "profiles" / ("align_bench.json" if args.box is None
+                                            else "align_null_bench.json" if args.null
                                             else "path_values_bench.json" if args.values
                                             else "align_global_box_bench.json" if fill
                                             else "align_box_bench.json"))
     if args.box is not None:
-        result = _values_bench(args) if args.values else _global_box_bench(args) if fill \
-            else _box_bench(args)
+        result = _null_bench(args) if args.null else _values_bench(args) if args.values \
+            else _global_box_bench(args) if fill else _box_bench(args)
         Path(args.out).parent.mkdir(parents=True, exist_ok=True)
         Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
         print(json.dumps(result))
