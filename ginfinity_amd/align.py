@@ -456,20 +456,37 @@ class _Call(NamedTuple):
                              box_dev=None if self.box is None
                              else torch.from_numpy(self.box).to(a.device))
 
-    def arguments(self, within: bool | None = None) -> tuple:
-        """What every alignment call of the C ABI starts with, and behind it the band where the
-        call has one (the ``*_band`` symbols).  A call with a box (the ``*_box`` symbols) has
-        both behind it, the band or NULL and then the box.  The global calls (``within`` given)
-        have no band: ``within`` is behind the parameters, and behind it the box where the call
-        has one."""
-        band = () if self.band is None else (self.band_dev.data_ptr(),)
-        if self.box is not None:
-            band = (None if self.band is None else self.band_dev.data_ptr(), self.box_dev.data_ptr())
-        if within is not None:
-            band = (int(within),) + (() if self.box is None else (self.box_dev.data_ptr(),))
+    def values(self) -> tuple:
+        """The 14 values every alignment call of the C ABI starts with."""
         return (self.a.data_ptr(), self.a.shape[0], self.ptr_a_dev.data_ptr(), self.ptr_a.size - 1,
                 self.b.data_ptr(), self.b.shape[0], self.ptr_b_dev.data_ptr(), self.ptr_b.size - 1,
-                self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters, *band)
+                self.pairs_dev.data_ptr(), self.pairs.shape[0], *self.parameters)
+
+
+#: the kinds of call and the symbol of each without a band or a box
+_SYMBOLS = {"score": "gfy_align_local", "span": "gfy_align_local_span", "trace": "gfy_align_trace",
+            "global": "gfy_align_global", "global_trace": "gfy_align_global_trace",
+            "null": "gfy_align_local_null"}
+
+
+def _symbol(call: _Call, kind: str, within: bool | None = None) -> tuple:
+    """``(symbol, what it takes between gap_extend and its outputs)`` of a call of ``kind``, a key
+    of ``_SYMBOLS``.  The local symbols take the band where the call has one (``*_band``), and
+    with a box (``*_box``) the band or NULL and then the box; the trace of a local path takes no
+    box (``start..end`` lies inside it).  The global symbols have no band: they take ``within``
+    and behind it the box where the call has one.  The null scores have one symbol, which takes
+    the band or NULL and the box or NULL."""
+    name = _SYMBOLS[kind]
+    # an empty call is never launched and has no device arrays: its pointers are None
+    band, box = (None if x is None else x.data_ptr() for x in (call.band_dev, call.box_dev))
+    boxed = call.box is not None and kind != "trace"
+    if kind == "null":
+        return name, (band, box)
+    if kind in ("global", "global_trace"):
+        return (name + "_box", (int(within), box)) if boxed else (name, (int(within),))
+    if boxed:
+        return name + "_box", (band, box)
+    return (name, ()) if call.band is None else (name + "_band", (band,))
 
 
 def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
@@ -504,34 +521,27 @@ def _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_s
                  band=_checked_band(band, pairs.shape[0]), box=_checked_box(box, pairs.shape[0]))
 
 
-def _launch(call: _Call, name: str, sizer: str, within, span: bool, workspace) -> tuple:
-    """The one score launch of a call that is ``on_device``: the symbol ``name`` with the call's
-    arguments (``within`` among them for the global calls, None for the local ones) in front of
-    the outputs, its workspace sized by the symbol ``sizer`` for the widest matrix of the call.
-    ``span`` False gives ``(scores, ends)``, True ``(scores, starts, ends)``; an empty call gives
-    its results without a launch."""
-    device, count = call.a.device, call.pairs.shape[0]
+def _launch(call: _Call, kind: str, within, workspace) -> tuple:
+    """The one score launch of a call that is ``on_device``: the symbol of ``kind`` ("score",
+    "span" or "global", the last with ``within``) with the call's arguments in front of the
+    outputs, its workspace sized for the widest matrix of the call.  "span" gives ``(scores,
+    starts, ends)``, the others ``(scores, ends)``; an empty call gives its results without a
+    launch."""
+    device, count, span = call.a.device, call.pairs.shape[0], kind == "span"
+    sizer = "gfy_align_span_workspace_bytes" if span else "gfy_align_workspace_bytes"
     with torch.cuda.device(device):
         scores = torch.zeros(count, dtype=torch.float32, device=device)
         ends = torch.full((count, 2), -1, dtype=torch.int32, device=device)
         starts = torch.full((count, 2), -1, dtype=torch.int32, device=device) if span else None
         outputs = (scores, starts, ends) if span else (scores, ends)
         if not call.empty:
-            lib = native.library()
+            lib, (name, front) = native.library(), _symbol(call, kind, within)
             need = getattr(lib, sizer)(count, int(call.box_columns.max()))
             scratch = (workspace or AlignWorkspace()).buffer(device, need)
             native.check(getattr(lib, name)(
-                *call.arguments(within), *(out.data_ptr() for out in outputs),
+                *call.values(), *front, *(out.data_ptr() for out in outputs),
                 *_scratch_tail(scratch, device)), name)
     return outputs
-
-
-def _launch_local(call: _Call, span: bool, workspace) -> tuple:
-    """``_launch`` for ``local_align`` (``span`` False) and ``local_spans`` (True)."""
-    name = "gfy_align_local_span" if span else "gfy_align_local"
-    name += "_box" if call.box is not None else "_band" if call.band is not None else ""
-    sizer = "gfy_align_span_workspace_bytes" if span else "gfy_align_workspace_bytes"
-    return _launch(call, name, sizer, None, span, workspace)
 
 
 def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -571,9 +581,9 @@ def local_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     finite or out of order, a band that is not integer, of another shape, or with ``lo > hi``,
     a box that is not integer, of another shape, or with ``i_lo > i_hi`` or ``j_lo > j_hi``.
     ``P == 0`` returns empty tensors without a launch."""
-    return _launch_local(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                       match_scale, match_shift, band, box).on_device(), False,
-                         workspace)
+    return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                 match_scale, match_shift, band, box).on_device(), "score", None,
+                   workspace)
 
 
 def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -590,9 +600,9 @@ def local_spans(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     coordinates), their checks and the ``ValueError``s are those of
     ``local_align``; an ``AlignWorkspace`` serves both functions (this one needs twice the
     bytes)."""
-    return _launch_local(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                       match_scale, match_shift, band, box).on_device(), True,
-                         workspace)
+    return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                 match_scale, match_shift, band, box).on_device(), "span", None,
+                   workspace)
 
 
 class AlignedPaths(NamedTuple):
@@ -635,16 +645,15 @@ def local_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
     max_workspace_bytes = _checked_cap(max_workspace_bytes)
     call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
                          match_shift, band, box).on_device()
-    scores, starts, ends = _launch_local(call, True, workspace)
-    call = call._replace(box=None, box_dev=None)                    # the trace takes none
+    scores, starts, ends = _launch(call, "span", None, workspace)
     with torch.cuda.device(scores.device):
         box = (ends - starts + 1).cpu().numpy().astype(np.int64)    # waits for the span launch
         box[starts.cpu().numpy()[:, 0] < 0] = 0                     # nothing aligned: no box
         slots = np.maximum(box.sum(axis=1) - 1, 0)                  # rows + cols - 1 ops at most
-        name = "gfy_align_trace" if call.band is None else "gfy_align_trace_band"
+        name, front = _symbol(call, "trace")
 
         def trace(lib, slot_ptr, slot_ops, lengths, *rest):   # rest: box, workspace, stream
-            return getattr(lib, name)(*call.arguments(), starts.data_ptr(), ends.data_ptr(),
+            return getattr(lib, name)(*call.values(), *front, starts.data_ptr(), ends.data_ptr(),
                                       slot_ptr, slot_ops, lengths, *rest)
         return _traced(call, name, trace, "gfy_align_trace_workspace_bytes",
                        f"{name} refused a box of its span call", scores, starts, ends, slots, box,
@@ -700,12 +709,6 @@ def _checked_cap(max_workspace_bytes) -> int:
     return _checked_integer(max_workspace_bytes, "max_workspace_bytes", 1)
 
 
-def _launch_global(call: _Call, within: bool, workspace) -> tuple:
-    """``_launch`` for ``global_align``: ``(scores, ends)``."""
-    name = "gfy_align_global_box" if call.box is not None else "gfy_align_global"
-    return _launch(call, name, "gfy_align_workspace_bytes", within, False, workspace)
-
-
 def global_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
                  match_scale=1.0, match_shift=0.0, within: bool = False, box=None,
                  workspace: AlignWorkspace | None = None) -> tuple[torch.Tensor, torch.Tensor]:
@@ -732,9 +735,9 @@ def global_align(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_ext
     (``box`` and its texts included); ``within`` must be a bool.  An ``AlignWorkspace`` serves
     this function too."""
     within = _checked_within(within)
-    return _launch_global(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
-                                        match_scale, match_shift, None, box).on_device(), within,
-                          workspace)
+    return _launch(_checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend,
+                                 match_scale, match_shift, None, box).on_device(), "global", within,
+                   workspace)
 
 
 def global_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_extend,
@@ -767,20 +770,18 @@ def global_paths(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_ext
     cap = _checked_cap(max_workspace_bytes)
     call = _checked_call(a, b, counts_a, counts_b, pairs, gap_open, gap_extend, match_scale,
                          match_shift, None, box).on_device()
-    scores, ends = _launch_global(call, within, workspace)
+    scores, ends = _launch(call, "global", within, workspace)
     device, count = scores.device, scores.shape[0]
     with torch.cuda.device(device):
         starts = torch.full((count, 2), -1, dtype=torch.int32, device=device)
         rows_a, rows_b = call.box_rows.astype(np.int64), call.box_columns.astype(np.int64)
         both = (rows_a > 0) & (rows_b > 0)
         slots = np.where(both, rows_a + rows_b, 0)           # rows + columns ops at most
-        name = "gfy_align_global_trace" + ("_box" if call.box is not None else "")
+        name, front = _symbol(call, "global_trace", within)
 
         def trace(lib, slot_ptr, slot_ops, lengths, *rest):   # rest: box, workspace, stream
-            tail = (ends.data_ptr(), slot_ptr, slot_ops, lengths, starts.data_ptr(), *rest)
-            if call.box is not None:
-                return lib.gfy_align_global_trace_box(*call.arguments(within), *tail)
-            return lib.gfy_align_global_trace(*call.arguments(within), *tail)
+            return getattr(lib, name)(*call.values(), *front, ends.data_ptr(), slot_ptr, slot_ops,
+                                      lengths, starts.data_ptr(), *rest)
         return _traced(call, name, trace, "gfy_align_global_trace_workspace_bytes",
                        f"{name} refused an end of its score call", scores, starts, ends, slots,
                        np.stack([rows_a, rows_b], axis=1), cap, workspace)
@@ -911,7 +912,7 @@ def path_values(paths, a, b=None, *, counts_a, counts_b=None, pairs, gap_open, g
         elif total and count:
             name = "gfy_align_path_values"
             native.check(getattr(native.library(), name)(
-                *call.arguments(), starts.data_ptr(), offsets.data_ptr(), ops.data_ptr(), total,
+                *call.values(), starts.data_ptr(), offsets.data_ptr(), ops.data_ptr(), total,
                 cosines.data_ptr(), running.data_ptr(), scores.data_ptr(), counts.data_ptr(),
                 sums.data_ptr(), max_waves or 0, torch.cuda.current_stream(device).cuda_stream),
                 name)
@@ -1065,13 +1066,11 @@ def null_scores(a, b=None, *, counts_a, counts_b=None, pairs, gap_open, gap_exte
         order, order_ptr = order.to(device).contiguous(), order_ptr.to(device).contiguous()
         if order.numel() == 0:                   # no b-side has a row: NULL is no array
             order = torch.zeros(1, dtype=torch.int32, device=device)
-        lib, name = native.library(), "gfy_align_local_null"
+        lib, (name, front) = native.library(), _symbol(call, "null")
         need = lib.gfy_align_workspace_bytes(count * shuffles, int(columns.max()))
         scratch = (workspace or AlignWorkspace()).buffer(device, need)
         native.check(getattr(lib, name)(
-            *call.arguments()[:14],
-            None if call.band is None else call.band_dev.data_ptr(),
-            None if call.box is None else call.box_dev.data_ptr(),
+            *call.values(), *front,
             shuffles, order.data_ptr(), order_ptr.data_ptr(), scores.data_ptr(),
             *_scratch_tail(scratch, device)), name)
     return scores

@@ -19,9 +19,7 @@ LIBRARY = CSRC / "libgfy.so"
 SOURCES = ("gfy_api.hip", "graph_build.hip", "graph_windows.hip", "csr_build.hip", "gine_f16.hip",
            "gine_f32.hip", "pairwise.hip", "pairwise_topk.hip", "pairwise_topk_ranges.hip",
            "pairwise_topk_distinct.hip", "pairwise_records.hip", "pairwise_within.hip",
-           "align_local.hip", "align_span.hip", "align_trace.hip", "align_global.hip",
-           "align_global_trace.hip", "align_band.hip", "align_box.hip", "align_global_box.hip",
-           "align_values.hip", "align_null.hip",
+           "align_kernels.hip", "align_values.hip",
            "hit_runs.hip", "chain_runs.hip", "weight_image.cpp",
            "gine_host.cpp", "gfy_base.cpp")
 # device="cpu" (the reference's default device) without any ROCm runtime on the box: the host

@@ -1,10 +1,9 @@
-// The one alignment loop of the library (semantics: include/gfy.h), shared by k_align_local
-// (align_local.hip, mode 0: score and end), k_align_span (align_span.hip, kSpan: score, start and
-// end) and k_align_trace (align_trace.hip, kTrace: the aligned path of a given box), their three
-// twins inside a band of diagonals (align_band.hip, | kBand), the score and span kernels inside
-// a box of rows the caller names (align_box.hip, | kBand | kBox), the two global kernels
-// (kGlobal) and their twins inside such a box (align_global_box.hip, | kBox), and the score
-// kernel of shuffled b-sides (align_null.hip, kBand | kBox | kOrder), as pairwise_topk.inc is
+// The one alignment loop of the library (semantics: include/gfy.h), shared by the kernels of
+// align_kernels.hip: k_align_local (mode 0: score and end), k_align_span (kSpan: score, start and
+// end) and k_align_trace (kTrace: the aligned path of a given box), their three twins inside a
+// band of diagonals (| kBand), the score and span kernels inside a box of rows the caller names
+// (| kBand | kBox), the two global kernels (kGlobal) and their twins inside such a box (| kBox),
+// and the score kernel of shuffled b-sides (kBand | kBox | kOrder), as pairwise_topk.inc is
 // shared by the top-k family.
 //
 // One wave owns one pair; a workgroup is four waves that never meet (no barrier, no flag), and a
@@ -49,23 +48,8 @@ static_assert(kRingBytes == kBuffers * (kSub * 256), "a quarter of the ring stag
 static_assert(kAlignLds <= 160 * 1024, "the LDS of a compute unit");
 static_assert(GFY_ALIGN_ROWS_MAX == 1 << kOriginBits, "both coordinates of an origin fit its word");
 
-// (AlignArgs, TraceArgs and OrderArgs, the kernels' arguments: gfy_common.h)
-
-// The modes of align_pairs<kMode>, or-ed together.  A mode that is not set costs nothing: behind
-// `if constexpr` none of its code exists.
-//   kSpan    score, end and the start cell
-//   kTrace   the aligned path of a box the caller names; not with kSpan
-//   kGlobal  no 0 candidate and charged borders, with the wave-uniform flag `within` the
-//            query-in-target mode; not with kSpan
-//   kBand    only the cells of a band of diagonals exist; not with kGlobal
-//   kBox     only the cells of a box of rows the caller names exist, and the results are in the
-//            records' coordinates; with kBand (a call without a band has the covering one) or
-//            with kGlobal (no band: the box's edges are the charged or free borders), and with
-//            kTrace only next to kGlobal
-//   kOrder   column j of a pair's matrix holds row order[j] of the pair's b-side, and the call
-//            runs over virtual pairs v = p * shuffles + k, each under an order of its own;
-//            score only, with kBand and kBox, where a null `boxes` is the covering box
-enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8, kBox = 16, kOrder = 32 };
+// (AlignArgs, TraceArgs and OrderArgs, the kernels' arguments, and AlignMode, the modes of
+// align_pairs<kMode>: gfy_common.h)
 
 // a carry entry: (H, F) of a column, and with kSpan their origins behind them
 template <bool kSpan>
@@ -807,75 +791,6 @@ __device__ __forceinline__ void align_pairs(const AlignArgs& p, int32_t* out_sta
       finish_pair<kMode>(p, lane, pr, within, pair, strips, h_last, best, best_i, best_j, best_o,
                          out_start);
   }
-}
-
-int align_groups(int64_t pairs) {
-  const int64_t groups = (pairs + kAlignWaves - 1) / kAlignWaves;
-  return (int)(groups < 1 ? 1 : groups > kAlignGroupsMax ? kAlignGroupsMax : groups);
-}
-
-// two carry buffers of max_rows_b entries per wave of the grid
-template <bool kSpan>
-size_t align_carry_bytes(int64_t pairs, int64_t max_rows_b) {
-  const size_t waves = (size_t)align_groups(pairs) * kAlignWaves;
-  return align_up(waves * 2 * (size_t)max_rows_b * sizeof(AlignCarry<kSpan>) + 1, 256);
-}
-
-// the carry of a score or span call in the caller's workspace: the check, then `carry` and `cap`
-// of `p`, the launcher's copy of the call
-template <bool kSpan>
-int align_take_carry(const char* who, AlignArgs* p, void* ws, size_t ws_bytes) {
-  GFY_REQUIRE(ws_bytes >= align_carry_bytes<kSpan>(p->P, 0), GFY_ERR_WORKSPACE,
-              "%s: workspace %zu < required %zu", who, ws_bytes,
-              align_carry_bytes<kSpan>(p->P, 0));
-  const size_t columns =
-      ws_bytes / ((size_t)align_groups(p->P) * kAlignWaves * 2 * sizeof(AlignCarry<kSpan>));
-  p->carry = ws;
-  p->cap = (int)(columns < GFY_ALIGN_ROWS_MAX ? columns : GFY_ALIGN_ROWS_MAX);
-  return GFY_OK;
-}
-
-int64_t trace_region_words(int64_t max_box_rows, int64_t max_box_cols) {
-  return max_box_rows * ((max_box_cols + 7) / 8);
-}
-
-// a wave's part of a trace workspace: two carry buffers of max_box_cols (H, F) entries and the
-// direction words of the largest box
-size_t trace_wave_bytes(int64_t max_box_rows, int64_t max_box_cols) {
-  return align_up((size_t)2 * max_box_cols * sizeof(AlignCarry<false>) +
-                      (size_t)trace_region_words(max_box_rows, max_box_cols) * 4 + 1, 256);
-}
-
-// the caller's workspace cut into such parts: the check, then what the launcher's copies `p` and
-// `trace` of a trace call say about it
-int trace_take_workspace(const char* who, AlignArgs* p, TraceArgs* trace, int64_t max_box_rows,
-                         int64_t max_box_cols, void* ws, size_t ws_bytes) {
-  const size_t wave_bytes = trace_wave_bytes(max_box_rows, max_box_cols);
-  GFY_REQUIRE(ws_bytes >= wave_bytes, GFY_ERR_WORKSPACE,
-              "%s: workspace %zu < the %zu of one wave", who, ws_bytes, wave_bytes);
-  const size_t fit = ws_bytes / wave_bytes, waves = (size_t)align_groups(p->P) * kAlignWaves;
-  p->carry = ws;
-  p->cap = (int)max_box_cols;
-  trace->waves = (int64_t)(fit < waves ? fit : waves);
-  trace->wave_bytes = (int64_t)wave_bytes;
-  trace->region_words = trace_region_words(max_box_rows, max_box_cols);
-  return GFY_OK;
-}
-
-// kKernel<<<groups, kAlignThreads, kAlignLds>>>(p): the opt-in to that much dynamic LDS once per
-// device and kernel, as launch_sweep (pairwise_sweep.inc) does it
-template <auto kKernel, class Args>
-int align_launch(const Args& p, int groups, hipStream_t s) {
-  static PerDeviceOnce opt_in;
-  if (const int rc = opt_in.run([]() -> int {
-        GFY_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kKernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, kAlignLds));
-        return GFY_OK;
-      }))
-    return rc;
-  kKernel<<<groups, kAlignThreads, kAlignLds, s>>>(p);
-  GFY_CHECK_HIP(hipGetLastError());
-  return GFY_OK;
 }
 
 }  // namespace

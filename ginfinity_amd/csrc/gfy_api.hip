@@ -914,6 +914,7 @@ struct AlignAbi {
 struct NamedOutput {
   const void* pointer;
   const char* name;
+  bool has = true;   // the call has this pointer at all
 };
 
 // The argument rules every alignment call (gfy_align_local to gfy_align_global_trace_box) shares, in one
@@ -921,15 +922,15 @@ struct NamedOutput {
 // every field that comes from the 14 values; the outputs are the entry point's, carry and cap the
 // launcher's.
 static int checked_align_call(const char* who, const AlignAbi& v,
-                              std::initializer_list<NamedOutput> outputs, const void* ws,
+                              const NamedOutput* outputs, size_t count, const void* ws,
                               AlignArgs* call, bool has_workspace = true) {
   GFY_REQUIRE(v.a, GFY_ERR_INVALID, "%s: a is NULL", who);
   GFY_REQUIRE(v.b, GFY_ERR_INVALID, "%s: b is NULL", who);
   GFY_REQUIRE(v.ptr_a, GFY_ERR_INVALID, "%s: ptr_a is NULL", who);
   GFY_REQUIRE(v.ptr_b, GFY_ERR_INVALID, "%s: ptr_b is NULL", who);
   GFY_REQUIRE(v.pairs, GFY_ERR_INVALID, "%s: pairs is NULL", who);
-  for (const NamedOutput& out : outputs)
-    GFY_REQUIRE(out.pointer, GFY_ERR_INVALID, "%s: %s is NULL", who, out.name);
+  for (const NamedOutput* out = outputs; out != outputs + count; ++out)
+    GFY_REQUIRE(out->pointer || !out->has, GFY_ERR_INVALID, "%s: %s is NULL", who, out->name);
   GFY_REQUIRE(ws || !has_workspace, GFY_ERR_INVALID, "%s: workspace is NULL", who);
   GFY_REQUIRE(v.n > 0 && v.m > 0 && v.n < INT32_MAX && v.m < INT32_MAX, GFY_ERR_INVALID,
               "%s: bad arguments: n = %lld, m = %lld", who, (long long)v.n, (long long)v.m);
@@ -976,22 +977,106 @@ size_t gfy_align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b) {
   return align_span_workspace_bytes(pairs < 1 ? 1 : pairs, clipped_align_rows(max_rows_b));
 }
 
+size_t gfy_align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols) {
+  return align_trace_workspace_bytes(pairs < 1 ? 1 : pairs, clipped_align_rows(max_box_rows),
+                                     clipped_align_rows(max_box_cols));
+}
+
+size_t gfy_align_global_trace_workspace_bytes(int64_t pairs, int64_t max_rows_a,
+                                              int64_t max_rows_b) {
+  return gfy_align_trace_workspace_bytes(pairs, max_rows_a, max_rows_b);
+}
+
+// One of the twelve launch entry points (gfy_align_local to gfy_align_global_trace_box), described:
+// its name, its mode (the kernel, and which of the fields below the call has), the 14 values and
+// what follows them in the signature, as given.  A field that the mode does not have stays zero.
+struct AlignEntry {
+  const char* who;
+  unsigned mode;        // AlignMode bits
+  const char* plain;    // the call without the band (kBand) or box (kBox) that this one requires,
+                        // which a NULL one is told; kOrder requires neither
+  AlignAbi v;
+  const int32_t* bands;
+  const int32_t* boxes;
+  float* out_score;
+  int32_t* out_end;
+  AlignExtras extras;   // the trace's pointers, order and order_ptr, out_start, within, and the two
+                        // maxima of a trace as given
+  int64_t shuffles;
+};
+#define GFY_ALIGN_VALUES                                                                    \
+  {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift, gap_open, \
+   gap_extend}
+
+// Every check of such an entry point, in the one order all of them keep: the band or box that the
+// call requires, the pointers a trace call names first, the shared rules (a score call's outputs
+// between `pairs` and the workspace), `within`, the maxima or the shuffles; then the call record
+// and the launcher, which checks the workspace's size.
+static int align_entry(AlignEntry& e, void* ws, size_t ws_bytes, void* stream) {
+  const char* who = e.who;
+  const bool span = e.mode & kSpan, trace = e.mode & kTrace, global = e.mode & kGlobal;
+  const bool order = e.mode & kOrder;
+  clear_error();
+  if (!order && (e.mode & kBox)) {
+    GFY_REQUIRE(e.boxes, GFY_ERR_INVALID,
+                "%s: boxes is NULL (int32 [P][4] of (i_lo, i_hi, j_lo, j_hi) rows in device "
+                "memory; %s is the call without a box)", who, e.plain);
+  } else if (!order && (e.mode & kBand)) {
+    GFY_REQUIRE(e.bands, GFY_ERR_INVALID,
+                "%s: bands is NULL (int32 [P][2] of (lo, hi) diagonals in device memory; %s is "
+                "the call without a band)", who, e.plain);
+  }
+  // every pointer a call can name, in the order that all of them keep, and whether this one does
+  const TraceArgs& t = e.extras.trace;
+  const NamedOutput all[] = {{t.starts, "starts", trace && !global},
+                             {t.ends, "ends", trace},
+                             {t.op_ptr, "op_ptr", trace},
+                             {t.out_ops, "out_ops", trace},
+                             {t.out_len, "out_len", trace},
+                             {e.extras.orders.order, "order", order},
+                             {e.extras.orders.order_ptr, "order_ptr", order},
+                             {e.out_score, "out_score", !trace},
+                             {e.extras.out_start, "out_start", span || (trace && global)},
+                             {e.out_end, "out_end", !trace && !order}};
+  if (trace)
+    for (const NamedOutput& named : all)
+      GFY_REQUIRE(named.pointer || !named.has, GFY_ERR_INVALID, "%s: %s is NULL", who, named.name);
+  AlignArgs call;   // a trace's pointers are named above: none is left to the shared check
+  if (const int rc = checked_align_call(who, e.v, all, trace ? 0 : std::size(all), ws, &call))
+    return rc;
+  if (global)
+    GFY_REQUIRE(e.extras.within == 0 || e.extras.within == 1, GFY_ERR_INVALID,
+                "%s: within = %d is neither 0 nor 1", who, e.extras.within);
+  if (trace)
+    GFY_REQUIRE(e.extras.max_box_rows >= 0 && e.extras.max_box_cols >= 0, GFY_ERR_INVALID,
+                "%s: %s = %lld, %s = %lld are negative", who,
+                global ? "max_rows_a" : "max_box_rows", (long long)e.extras.max_box_rows,
+                global ? "max_rows_b" : "max_box_cols", (long long)e.extras.max_box_cols);
+  if (order) {
+    GFY_REQUIRE(e.shuffles >= 1, GFY_ERR_INVALID, "%s: shuffles = %lld is below 1", who,
+                (long long)e.shuffles);
+    GFY_REQUIRE(e.shuffles <= INT32_MAX / e.v.P, GFY_ERR_INVALID,
+                "%s: P * shuffles = %lld * %lld outside 1..2^31 - 1", who, (long long)e.v.P,
+                (long long)e.shuffles);
+    e.extras.orders.shuffles = (int)e.shuffles;
+  }
+  call.bands = e.bands;
+  call.boxes = e.boxes;
+  call.out_score = e.out_score;
+  call.out_end = e.out_end;
+  e.extras.max_box_rows = clipped_align_rows(e.extras.max_box_rows);
+  e.extras.max_box_cols = clipped_align_rows(e.extras.max_box_cols);
+  return launch_align(e.mode, call, e.extras, ws, ws_bytes, (hipStream_t)stream);
+}
+
 int gfy_align_local(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                     const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                     const int32_t* pairs, int64_t P, float match_scale, float match_shift,
                     float gap_open, float gap_extend, float* out_score, int32_t* out_end,
                     void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_local",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_local(call, ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_local", 0, nullptr, GFY_ALIGN_VALUES};
+  e.out_score = out_score, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -999,22 +1084,9 @@ int gfy_align_local_span(const void* a, int64_t n, const int32_t* ptr_a, int64_t
                          const int32_t* pairs, int64_t P, float match_scale, float match_shift,
                          float gap_open, float gap_extend, float* out_score, int32_t* out_start,
                          int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_local_span",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_start, "out_start"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_local_span(call, out_start, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t gfy_align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols) {
-  return align_trace_workspace_bytes(pairs < 1 ? 1 : pairs, clipped_align_rows(max_box_rows),
-                                     clipped_align_rows(max_box_cols));
+  AlignEntry e{"gfy_align_local_span", kSpan, nullptr, GFY_ALIGN_VALUES};
+  e.out_score = out_score, e.extras.out_start = out_start, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1024,57 +1096,22 @@ int gfy_align_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t reco
                     const int64_t* op_ptr, uint8_t* out_ops, int32_t* out_len,
                     int64_t max_box_rows, int64_t max_box_cols, void* ws, size_t ws_bytes,
                     void* stream) {
-  clear_error();
-  GFY_REQUIRE(starts, GFY_ERR_INVALID, "gfy_align_trace: starts is NULL");
-  GFY_REQUIRE(ends, GFY_ERR_INVALID, "gfy_align_trace: ends is NULL");
-  GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_trace: op_ptr is NULL");
-  GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_trace: out_ops is NULL");
-  GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_trace: out_len is NULL");
-  AlignArgs call;   // the five pointers are named above: no output is left to the shared check
-  if (const int rc = checked_align_call(
-          "gfy_align_trace",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {}, ws, &call))
-    return rc;
-  GFY_REQUIRE(max_box_rows >= 0 && max_box_cols >= 0, GFY_ERR_INVALID,
-              "gfy_align_trace: max_box_rows = %lld, max_box_cols = %lld are negative",
-              (long long)max_box_rows, (long long)max_box_cols);
-  TraceArgs trace{};
-  trace.starts = starts;
-  trace.ends = ends;
-  trace.op_ptr = op_ptr;
-  trace.out_ops = out_ops;
-  trace.out_len = out_len;
-  return launch_align_trace(call, trace, clipped_align_rows(max_box_rows),
-                            clipped_align_rows(max_box_cols), ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_trace", kTrace, nullptr, GFY_ALIGN_VALUES};
+  e.extras.trace = {starts, ends, op_ptr, out_ops, out_len};
+  e.extras.max_box_rows = max_box_rows, e.extras.max_box_cols = max_box_cols;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 // The three local calls inside a band per pair: their counterpart's checks in its order, with
-// `bands` named first, and the banded kernels (align_band.hip).
-#define GFY_REQUIRE_BANDS(who, plain)                                                         \
-  GFY_REQUIRE(bands, GFY_ERR_INVALID,                                                         \
-              who ": bands is NULL (int32 [P][2] of (lo, hi) diagonals in device memory; " plain \
-              " is the call without a band)")
-
+// `bands` named first.
 int gfy_align_local_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                          const int32_t* pairs, int64_t P, float match_scale, float match_shift,
                          float gap_open, float gap_extend, const int32_t* bands, float* out_score,
                          int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  GFY_REQUIRE_BANDS("gfy_align_local_band", "gfy_align_local");
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_local_band",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  call.bands = bands;
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_local_band(call, ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_local_band", kBand, "gfy_align_local", GFY_ALIGN_VALUES, bands};
+  e.out_score = out_score, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_local_span_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1083,19 +1120,10 @@ int gfy_align_local_span_band(const void* a, int64_t n, const int32_t* ptr_a, in
                               float match_shift, float gap_open, float gap_extend,
                               const int32_t* bands, float* out_score, int32_t* out_start,
                               int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  GFY_REQUIRE_BANDS("gfy_align_local_span_band", "gfy_align_local_span");
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_local_span_band",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_start, "out_start"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  call.bands = bands;
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_local_span_band(call, out_start, ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_local_span_band", kSpan | kBand, "gfy_align_local_span",
+               GFY_ALIGN_VALUES, bands};
+  e.out_score = out_score, e.extras.out_start = out_start, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_trace_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1105,64 +1133,24 @@ int gfy_align_trace_band(const void* a, int64_t n, const int32_t* ptr_a, int64_t
                          const int32_t* starts, const int32_t* ends, const int64_t* op_ptr,
                          uint8_t* out_ops, int32_t* out_len, int64_t max_box_rows,
                          int64_t max_box_cols, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  GFY_REQUIRE_BANDS("gfy_align_trace_band", "gfy_align_trace");
-  GFY_REQUIRE(starts, GFY_ERR_INVALID, "gfy_align_trace_band: starts is NULL");
-  GFY_REQUIRE(ends, GFY_ERR_INVALID, "gfy_align_trace_band: ends is NULL");
-  GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_trace_band: op_ptr is NULL");
-  GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_trace_band: out_ops is NULL");
-  GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_trace_band: out_len is NULL");
-  AlignArgs call;   // the pointers are named above: no output is left to the shared check
-  if (const int rc = checked_align_call(
-          "gfy_align_trace_band",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {}, ws, &call))
-    return rc;
-  GFY_REQUIRE(max_box_rows >= 0 && max_box_cols >= 0, GFY_ERR_INVALID,
-              "gfy_align_trace_band: max_box_rows = %lld, max_box_cols = %lld are negative",
-              (long long)max_box_rows, (long long)max_box_cols);
-  call.bands = bands;
-  TraceArgs trace{};
-  trace.starts = starts;
-  trace.ends = ends;
-  trace.op_ptr = op_ptr;
-  trace.out_ops = out_ops;
-  trace.out_len = out_len;
-  return launch_align_trace_band(call, trace, clipped_align_rows(max_box_rows),
-                                 clipped_align_rows(max_box_cols), ws, ws_bytes,
-                                 (hipStream_t)stream);
+  AlignEntry e{"gfy_align_trace_band", kTrace | kBand, "gfy_align_trace", GFY_ALIGN_VALUES, bands};
+  e.extras.trace = {starts, ends, op_ptr, out_ops, out_len};
+  e.extras.max_box_rows = max_box_rows, e.extras.max_box_cols = max_box_cols;
+  return align_entry(e, ws, ws_bytes, stream);
 }
-#undef GFY_REQUIRE_BANDS
 
 // The score and span calls inside a box of rows per pair: the banded call's checks in its order,
-// with `boxes` named first and `bands` free to be NULL (no band), and the boxed kernels
-// (align_box.hip).
-#define GFY_REQUIRE_BOXES(who, plain)                                                          \
-  GFY_REQUIRE(boxes, GFY_ERR_INVALID,                                                          \
-              who ": boxes is NULL (int32 [P][4] of (i_lo, i_hi, j_lo, j_hi) rows in device "  \
-                  "memory; " plain " is the call without a box)")
-
+// with `boxes` named first and `bands` free to be NULL (no band).
 int gfy_align_local_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                         const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                         const int32_t* pairs, int64_t P, float match_scale, float match_shift,
                         float gap_open, float gap_extend, const int32_t* bands,
                         const int32_t* boxes, float* out_score, int32_t* out_end, void* ws,
                         size_t ws_bytes, void* stream) {
-  clear_error();
-  GFY_REQUIRE_BOXES("gfy_align_local_box", "gfy_align_local_band");
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_local_box",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  call.bands = bands;
-  call.boxes = boxes;
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_local_box(call, ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_local_box", kBand | kBox, "gfy_align_local_band", GFY_ALIGN_VALUES,
+               bands, boxes};
+  e.out_score = out_score, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1172,26 +1160,14 @@ int gfy_align_local_span_box(const void* a, int64_t n, const int32_t* ptr_a, int
                              const int32_t* bands, const int32_t* boxes, float* out_score,
                              int32_t* out_start, int32_t* out_end, void* ws, size_t ws_bytes,
                              void* stream) {
-  clear_error();
-  GFY_REQUIRE_BOXES("gfy_align_local_span_box", "gfy_align_local_span_band");
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_local_span_box",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_start, "out_start"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  call.bands = bands;
-  call.boxes = boxes;
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_local_span_box(call, out_start, ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_local_span_box", kSpan | kBand | kBox, "gfy_align_local_span_band",
+               GFY_ALIGN_VALUES, bands, boxes};
+  e.out_score = out_score, e.extras.out_start = out_start, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
-#undef GFY_REQUIRE_BOXES
 
-// Null scores (align_null.hip): the boxed score call's checks in its order with `bands` and
-// `boxes` both free to be NULL, the orders named like outputs, and then what the virtual pairs
-// add.
+// Null scores: the boxed score call's checks in its order with `bands` and `boxes` both free to
+// be NULL, the orders named like outputs, and then what the virtual pairs add.
 int gfy_align_local_null(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                          const int32_t* pairs, int64_t P, float match_scale, float match_shift,
@@ -1199,24 +1175,11 @@ int gfy_align_local_null(const void* a, int64_t n, const int32_t* ptr_a, int64_t
                          const int32_t* boxes, int64_t shuffles, const int32_t* order,
                          const int64_t* order_ptr, float* out_score, void* ws, size_t ws_bytes,
                          void* stream) {
-  clear_error();
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_local_null",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{order, "order"}, {order_ptr, "order_ptr"}, {out_score, "out_score"}}, ws, &call))
-    return rc;
-  GFY_REQUIRE(shuffles >= 1, GFY_ERR_INVALID, "gfy_align_local_null: shuffles = %lld is below 1",
-              (long long)shuffles);
-  GFY_REQUIRE(shuffles <= INT32_MAX / P, GFY_ERR_INVALID,
-              "gfy_align_local_null: P * shuffles = %lld * %lld outside 1..2^31 - 1", (long long)P,
-              (long long)shuffles);
-  call.bands = bands;
-  call.boxes = boxes;
-  call.out_score = out_score;
-  OrderArgs orders{order, order_ptr, (int)shuffles};
-  return launch_align_local_null(call, orders, ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_local_null", kBand | kBox | kOrder, nullptr, GFY_ALIGN_VALUES, bands,
+               boxes};
+  e.shuffles = shuffles, e.extras.orders = {order, order_ptr};
+  e.out_score = out_score;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1224,25 +1187,9 @@ int gfy_align_global(const void* a, int64_t n, const int32_t* ptr_a, int64_t rec
                      const int32_t* pairs, int64_t P, float match_scale, float match_shift,
                      float gap_open, float gap_extend, int within, float* out_score,
                      int32_t* out_end, void* ws, size_t ws_bytes, void* stream) {
-  clear_error();
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_global",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  GFY_REQUIRE(within == 0 || within == 1, GFY_ERR_INVALID,
-              "gfy_align_global: within = %d is neither 0 nor 1", within);
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_global(call, within, ws, ws_bytes, (hipStream_t)stream);
-}
-
-size_t gfy_align_global_trace_workspace_bytes(int64_t pairs, int64_t max_rows_a,
-                                              int64_t max_rows_b) {
-  return align_global_trace_workspace_bytes(pairs < 1 ? 1 : pairs, clipped_align_rows(max_rows_a),
-                                            clipped_align_rows(max_rows_b));
+  AlignEntry e{"gfy_align_global", kGlobal, nullptr, GFY_ALIGN_VALUES};
+  e.extras.within = within, e.out_score = out_score, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_global_trace(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1252,62 +1199,25 @@ int gfy_align_global_trace(const void* a, int64_t n, const int32_t* ptr_a, int64
                            const int64_t* op_ptr, uint8_t* out_ops, int32_t* out_len,
                            int32_t* out_start, int64_t max_rows_a, int64_t max_rows_b, void* ws,
                            size_t ws_bytes, void* stream) {
-  clear_error();
-  GFY_REQUIRE(ends, GFY_ERR_INVALID, "gfy_align_global_trace: ends is NULL");
-  GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_global_trace: op_ptr is NULL");
-  GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_global_trace: out_ops is NULL");
-  GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_global_trace: out_len is NULL");
-  GFY_REQUIRE(out_start, GFY_ERR_INVALID, "gfy_align_global_trace: out_start is NULL");
-  AlignArgs call;   // the five pointers are named above: no output is left to the shared check
-  if (const int rc = checked_align_call(
-          "gfy_align_global_trace",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {}, ws, &call))
-    return rc;
-  GFY_REQUIRE(within == 0 || within == 1, GFY_ERR_INVALID,
-              "gfy_align_global_trace: within = %d is neither 0 nor 1", within);
-  GFY_REQUIRE(max_rows_a >= 0 && max_rows_b >= 0, GFY_ERR_INVALID,
-              "gfy_align_global_trace: max_rows_a = %lld, max_rows_b = %lld are negative",
-              (long long)max_rows_a, (long long)max_rows_b);
-  TraceArgs trace{};
-  trace.ends = ends;
-  trace.op_ptr = op_ptr;
-  trace.out_ops = out_ops;
-  trace.out_len = out_len;
-  return launch_align_global_trace(call, trace, out_start, within, clipped_align_rows(max_rows_a),
-                                   clipped_align_rows(max_rows_b), ws, ws_bytes,
-                                   (hipStream_t)stream);
+  AlignEntry e{"gfy_align_global_trace", kTrace | kGlobal, nullptr, GFY_ALIGN_VALUES};
+  e.extras.within = within, e.extras.out_start = out_start;
+  e.extras.trace = {nullptr, ends, op_ptr, out_ops, out_len};
+  e.extras.max_box_rows = max_rows_a, e.extras.max_box_cols = max_rows_b;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 // The two global calls inside a box of rows per pair: their counterpart's checks in its order,
-// with `boxes` named first, and the boxed kernels (align_global_box.hip).  There is no band.
-#define GFY_REQUIRE_BOXES(who, plain)                                                          \
-  GFY_REQUIRE(boxes, GFY_ERR_INVALID,                                                          \
-              who ": boxes is NULL (int32 [P][4] of (i_lo, i_hi, j_lo, j_hi) rows in device "  \
-                  "memory; " plain " is the call without a box)")
-
+// with `boxes` named first.  There is no band.
 int gfy_align_global_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
                          const void* b, int64_t m, const int32_t* ptr_b, int64_t records_b,
                          const int32_t* pairs, int64_t P, float match_scale, float match_shift,
                          float gap_open, float gap_extend, int within, const int32_t* boxes,
                          float* out_score, int32_t* out_end, void* ws, size_t ws_bytes,
                          void* stream) {
-  clear_error();
-  GFY_REQUIRE_BOXES("gfy_align_global_box", "gfy_align_global");
-  AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_global_box",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{out_score, "out_score"}, {out_end, "out_end"}}, ws, &call))
-    return rc;
-  GFY_REQUIRE(within == 0 || within == 1, GFY_ERR_INVALID,
-              "gfy_align_global_box: within = %d is neither 0 nor 1", within);
-  call.boxes = boxes;
-  call.out_score = out_score;
-  call.out_end = out_end;
-  return launch_align_global_box(call, within, ws, ws_bytes, (hipStream_t)stream);
+  AlignEntry e{"gfy_align_global_box", kGlobal | kBox, "gfy_align_global", GFY_ALIGN_VALUES,
+               nullptr, boxes};
+  e.extras.within = within, e.out_score = out_score, e.out_end = out_end;
+  return align_entry(e, ws, ws_bytes, stream);
 }
 
 int gfy_align_global_trace_box(const void* a, int64_t n, const int32_t* ptr_a, int64_t records_a,
@@ -1318,37 +1228,13 @@ int gfy_align_global_trace_box(const void* a, int64_t n, const int32_t* ptr_a, i
                                uint8_t* out_ops, int32_t* out_len, int32_t* out_start,
                                int64_t max_rows_a, int64_t max_rows_b, void* ws, size_t ws_bytes,
                                void* stream) {
-  clear_error();
-  GFY_REQUIRE_BOXES("gfy_align_global_trace_box", "gfy_align_global_trace");
-  GFY_REQUIRE(ends, GFY_ERR_INVALID, "gfy_align_global_trace_box: ends is NULL");
-  GFY_REQUIRE(op_ptr, GFY_ERR_INVALID, "gfy_align_global_trace_box: op_ptr is NULL");
-  GFY_REQUIRE(out_ops, GFY_ERR_INVALID, "gfy_align_global_trace_box: out_ops is NULL");
-  GFY_REQUIRE(out_len, GFY_ERR_INVALID, "gfy_align_global_trace_box: out_len is NULL");
-  GFY_REQUIRE(out_start, GFY_ERR_INVALID, "gfy_align_global_trace_box: out_start is NULL");
-  AlignArgs call;   // the pointers are named above: no output is left to the shared check
-  if (const int rc = checked_align_call(
-          "gfy_align_global_trace_box",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {}, ws, &call))
-    return rc;
-  GFY_REQUIRE(within == 0 || within == 1, GFY_ERR_INVALID,
-              "gfy_align_global_trace_box: within = %d is neither 0 nor 1", within);
-  GFY_REQUIRE(max_rows_a >= 0 && max_rows_b >= 0, GFY_ERR_INVALID,
-              "gfy_align_global_trace_box: max_rows_a = %lld, max_rows_b = %lld are negative",
-              (long long)max_rows_a, (long long)max_rows_b);
-  call.boxes = boxes;
-  TraceArgs trace{};
-  trace.ends = ends;
-  trace.op_ptr = op_ptr;
-  trace.out_ops = out_ops;
-  trace.out_len = out_len;
-  return launch_align_global_trace_box(call, trace, out_start, within,
-                                       clipped_align_rows(max_rows_a),
-                                       clipped_align_rows(max_rows_b), ws, ws_bytes,
-                                       (hipStream_t)stream);
+  AlignEntry e{"gfy_align_global_trace_box", kTrace | kGlobal | kBox, "gfy_align_global_trace",
+               GFY_ALIGN_VALUES, nullptr, boxes};
+  e.extras.within = within, e.extras.out_start = out_start;
+  e.extras.trace = {nullptr, ends, op_ptr, out_ops, out_len};
+  e.extras.max_box_rows = max_rows_a, e.extras.max_box_cols = max_rows_b;
+  return align_entry(e, ws, ws_bytes, stream);
 }
-#undef GFY_REQUIRE_BOXES
 
 // The values of given paths (align_values.hip): the shared checks of the alignment calls, the
 // pointers of its own named in its own order, and no workspace.
@@ -1362,14 +1248,12 @@ int gfy_align_path_values(const void* a, int64_t n, const int32_t* ptr_a, int64_
                           void* stream) {
   clear_error();
   AlignArgs call;
-  if (const int rc = checked_align_call(
-          "gfy_align_path_values",
-          {a, n, ptr_a, records_a, b, m, ptr_b, records_b, pairs, P, match_scale, match_shift,
-           gap_open, gap_extend},
-          {{starts, "starts"}, {op_ptr, "op_ptr"}, {ops, "ops"}, {out_cosine, "out_cosine"},
-           {out_running, "out_running"}, {out_score, "out_score"}, {out_counts, "out_counts"},
-           {out_cosine_sum, "out_cosine_sum"}},
-          nullptr, &call, false))
+  const NamedOutput named[] = {
+      {starts, "starts"}, {op_ptr, "op_ptr"}, {ops, "ops"}, {out_cosine, "out_cosine"},
+      {out_running, "out_running"}, {out_score, "out_score"}, {out_counts, "out_counts"},
+      {out_cosine_sum, "out_cosine_sum"}};
+  if (const int rc = checked_align_call("gfy_align_path_values", GFY_ALIGN_VALUES, named,
+                                        std::size(named), nullptr, &call, false))
     return rc;
   GFY_REQUIRE(n_ops >= 0, GFY_ERR_INVALID, "gfy_align_path_values: n_ops = %lld is negative",
               (long long)n_ops);

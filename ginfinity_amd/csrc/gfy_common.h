@@ -369,7 +369,7 @@ int launch_pairwise_within(const void* a, int64_t n, const void* b, int64_t m, i
 size_t pairwise_within_workspace_bytes(int64_t n, int64_t m);
 int pairwise_within_chunks(int64_t n, int64_t m);
 // One alignment call (align_local.inc): what the alignment entry points of gfy_api.hip check and
-// fill, the launchers complete (carry, cap) and the kernels read as their argument.
+// fill, the launcher completes (carry, cap) and the kernels read as their argument.
 struct AlignArgs {
   const f16* a;
   const f16* b;
@@ -411,55 +411,41 @@ struct OrderArgs {
   int shuffles;
 };
 
-// align_local.hip
-int launch_align_local(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
+// The modes of align_pairs<kMode> (align_local.inc), or-ed together: a mode names a kernel of
+// align_kernels.hip.  A mode that is not set costs nothing: behind `if constexpr` none of its code
+// exists.
+//   kSpan    score, end and the start cell
+//   kTrace   the aligned path of a box the caller names; not with kSpan
+//   kGlobal  no 0 candidate and charged borders, with the wave-uniform flag `within` the
+//            query-in-target mode; not with kSpan
+//   kBand    only the cells of a band of diagonals exist; not with kGlobal
+//   kBox     only the cells of a box of rows the caller names exist, and the results are in the
+//            records' coordinates; with kBand (a call without a band has the covering one) or
+//            with kGlobal (no band: the box's edges are the charged or free borders), and with
+//            kTrace only next to kGlobal
+//   kOrder   column j of a pair's matrix holds row order[j] of the pair's b-side, and the call
+//            runs over virtual pairs v = p * shuffles + k, each under an order of its own;
+//            score only, with kBand and kBox, where a null `boxes` is the covering box
+enum AlignMode : unsigned { kSpan = 1, kTrace = 2, kGlobal = 4, kBand = 8, kBox = 16, kOrder = 32 };
+
+// what the modes take next to AlignArgs; a field is read by the modes named and by no other
+struct AlignExtras {
+  TraceArgs trace;         // kTrace: the caller's five pointers (kGlobal: no starts)
+  OrderArgs orders;        // kOrder
+  int32_t* out_start;      // [P][2]: kSpan, and kTrace with kGlobal
+  int within;              // kGlobal
+  int64_t max_box_rows, max_box_cols;   // kTrace, the launcher alone: the largest box, clipped
+};
+
+// align_kernels.hip: the kernel of `mode` on the caller's workspace.  A score or span call needs
+// align_workspace_bytes / align_span_workspace_bytes for the widest matrix's columns (kOrder: of
+// P * shuffles pairs) and a trace call one wave's part of align_trace_workspace_bytes at least;
+// call.carry and call.cap, and of extras.trace what is not the caller's, are set here.
+int launch_align(unsigned mode, const AlignArgs& call, const AlignExtras& extras, void* ws,
+                 size_t ws_bytes, hipStream_t s);
 size_t align_workspace_bytes(int64_t pairs, int64_t max_rows_b);
-// align_span.hip: the same with the start cell of every alignment
-int launch_align_local_span(const AlignArgs& call, int32_t* out_start, void* ws, size_t ws_bytes,
-                            hipStream_t s);
 size_t align_span_workspace_bytes(int64_t pairs, int64_t max_rows_b);
-// align_trace.hip: the aligned path of the box start..end of every pair; `trace` carries the
-// caller's five pointers, the rest of it is set here
-int launch_align_trace(const AlignArgs& call, const TraceArgs& trace, int64_t max_box_rows,
-                       int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
 size_t align_trace_workspace_bytes(int64_t pairs, int64_t max_box_rows, int64_t max_box_cols);
-// align_global.hip: global alignment, with `within` query-in-target (a free top border); the
-// workspace is align_workspace_bytes
-int launch_align_global(const AlignArgs& call, int within, void* ws, size_t ws_bytes,
-                        hipStream_t s);
-// align_global_trace.hip: the aligned path of rows 0 .. L_q - 1 x columns 0 .. end_j; of `trace`
-// the caller sets ends, op_ptr, out_ops and out_len (starts is not read)
-int launch_align_global_trace(const AlignArgs& call, const TraceArgs& trace, int32_t* out_start,
-                              int within, int64_t max_rows_a, int64_t max_rows_b, void* ws,
-                              size_t ws_bytes, hipStream_t s);
-size_t align_global_trace_workspace_bytes(int64_t pairs, int64_t max_rows_a, int64_t max_rows_b);
-// align_band.hip: the three local calls inside a band of diagonals per pair (call.bands); the
-// workspaces are those of the unbanded calls
-int launch_align_local_band(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_align_local_span_band(const AlignArgs& call, int32_t* out_start, void* ws,
-                                 size_t ws_bytes, hipStream_t s);
-int launch_align_trace_band(const AlignArgs& call, const TraceArgs& trace, int64_t max_box_rows,
-                            int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
-// align_box.hip: the score and span calls inside a box of rows per pair (call.boxes) and, where
-// call.bands is not null, a band; the workspaces are those of the unbanded calls with the widest
-// box's columns for max_rows_b
-int launch_align_local_box(const AlignArgs& call, void* ws, size_t ws_bytes, hipStream_t s);
-int launch_align_local_span_box(const AlignArgs& call, int32_t* out_start, void* ws,
-                                size_t ws_bytes, hipStream_t s);
-// align_null.hip: the score call of align_box.hip on every pair `orders.shuffles` times, each
-// under an order of its b-side's rows; call.bands and call.boxes may each be null (the covering
-// one), call.out_score is [P][shuffles], call.out_end is not written; the workspace is
-// align_workspace_bytes of P * shuffles pairs
-int launch_align_local_null(const AlignArgs& call, const OrderArgs& orders, void* ws,
-                            size_t ws_bytes, hipStream_t s);
-// align_global_box.hip: the two global calls inside a box of rows per pair (call.boxes, no band);
-// the workspaces are align_workspace_bytes with the widest box's columns and
-// align_global_trace_workspace_bytes with the largest box's rows and columns
-int launch_align_global_box(const AlignArgs& call, int within, void* ws, size_t ws_bytes,
-                            hipStream_t s);
-int launch_align_global_trace_box(const AlignArgs& call, const TraceArgs& trace,
-                                  int32_t* out_start, int within, int64_t max_box_rows,
-                                  int64_t max_box_cols, void* ws, size_t ws_bytes, hipStream_t s);
 
 // what k_align_path_values takes next to AlignArgs (of which it reads the rows, the records, the
 // pairs and the four parameters, and no output, carry, band or box)

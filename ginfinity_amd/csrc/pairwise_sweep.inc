@@ -52,7 +52,7 @@ __device__ __forceinline__ float max16(const f32x16& g) {
 }
 
 // |row|^2 the way every key's terms take it (k_row_terms, pairwise.hip; the local aligner's
-// rows, align_local.hip): 16 consecutive lanes hold the 16 pieces of a row, each adds its eight
+// rows, align_local.inc): 16 consecutive lanes hold the 16 pieces of a row, each adds its eight
 // squares in order and a butterfly adds the 16 partial sums, so that all 16 lanes hold the sum.
 __device__ __forceinline__ float row_square_sum(const f16x8& v) {
   float ss = 0.f;

@@ -6,7 +6,7 @@
 namespace gfy {
 
 // Clears the call's status word (p.status), then kKernel<<<grid, threads, 0, stream>>>(p); as
-// align_launch (align_local.inc) it reports a launch that the runtime refused.
+// launch_align (align_kernels.hip) it reports a launch that the runtime refused.
 template <auto kKernel, class Args>
 int seed_launch(const Args& p, unsigned grid, int threads, void* stream) {
   hipStream_t s = (hipStream_t)stream;

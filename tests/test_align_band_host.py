@@ -197,7 +197,7 @@ def test_none_and_a_band_pass_the_checks_with_no_device_touched():
 
 
 def test_the_call_record_appends_the_band_to_the_arguments():
-    """``arguments()`` is what every symbol starts with; with a band its device pointer follows
+    """``values()`` is what every symbol starts with; with a band its device pointer follows
     gap_extend, where the ``*_band`` symbols take it."""
 
     class Pointer:
@@ -211,8 +211,11 @@ def test_the_call_record_appends_the_band_to_the_arguments():
                         np.zeros((3, 2), dtype=np.int32), np.array([4, 4, 2]), (1.0, 0.0, 1.0, 0.5),
                         Pointer(3), Pointer(4), Pointer(5))
     banded = plain._replace(band=np.zeros((3, 2), dtype=np.int32), band_dev=Pointer(6))
-    assert plain.arguments() == (1, 6, 3, 2, 2, 6, 4, 2, 5, 3, 1.0, 0.0, 1.0, 0.5)
-    assert banded.arguments() == plain.arguments() + (6,)
+    assert plain.values() == banded.values() == (1, 6, 3, 2, 2, 6, 4, 2, 5, 3, 1.0, 0.0, 1.0, 0.5)
+    for kind, name in (("score", "gfy_align_local"), ("span", "gfy_align_local_span"),
+                       ("trace", "gfy_align_trace")):
+        assert align._symbol(plain, kind) == (name, ())
+        assert align._symbol(banded, kind) == (name + "_band", (6,))
 
 
 def test_c_abi_declares_the_three_symbols_and_names_what_they_refuse():

@@ -199,9 +199,14 @@ def test_the_call_record_appends_the_band_and_the_box_to_the_arguments():
     banded = plain._replace(band=np.zeros((3, 2), dtype=np.int32), band_dev=Pointer(6))
     boxed = plain._replace(box=np.zeros((3, 4), dtype=np.int32), box_dev=Pointer(7))
     both = banded._replace(box=np.zeros((3, 4), dtype=np.int32), box_dev=Pointer(7))
-    assert boxed.arguments() == plain.arguments() + (None, 7)
-    assert both.arguments() == plain.arguments() + (6, 7)
-    assert banded.arguments() == plain.arguments() + (6,)
+    assert boxed.values() == both.values() == banded.values() == plain.values()
+    for kind, name in (("score", "gfy_align_local"), ("span", "gfy_align_local_span")):
+        assert align._symbol(boxed, kind) == (name + "_box", (None, 7))
+        assert align._symbol(both, kind) == (name + "_box", (6, 7))
+        assert align._symbol(banded, kind) == (name + "_band", (6,))
+    # the trace of a local path takes the band and never the box
+    assert align._symbol(boxed, "trace") == ("gfy_align_trace", ())
+    assert align._symbol(both, "trace") == ("gfy_align_trace_band", (6,))
 
 
 def _runs(cells, lengths):

@@ -252,10 +252,12 @@ def test_the_call_record_sizes_slots_by_the_clipped_box_and_puts_the_box_behind_
                         np.zeros((3, 2), dtype=np.int32), np.array([4, 4, 2]), (1.0, 0.0, 1.0, 0.5),
                         Pointer(3), Pointer(4), Pointer(5))
     boxed = plain._replace(box=np.zeros((3, 4), dtype=np.int32), box_dev=Pointer(7))
-    assert plain.arguments(False) == plain.arguments() + (0,)
-    assert plain.arguments(True) == plain.arguments() + (1,)
-    assert boxed.arguments(True) == plain.arguments() + (1, 7)
-    assert boxed.arguments() == plain.arguments() + (None, 7)       # the local symbols' order
+    assert boxed.values() == plain.values() and len(plain.values()) == 14
+    for kind, name in (("global", "gfy_align_global"), ("global_trace", "gfy_align_global_trace")):
+        assert align._symbol(plain, kind, False) == (name, (0,))
+        assert align._symbol(plain, kind, True) == (name, (1,))
+        assert align._symbol(boxed, kind, True) == (name + "_box", (1, 7))
+    assert align._symbol(boxed, "span") == ("gfy_align_local_span_box", (None, 7))   # the local order
 
 
 def test_c_abi_declares_the_two_symbols_and_names_what_they_refuse():

@@ -291,12 +291,12 @@ def test_global_paths_copies_nothing_to_the_host_between_its_launches():
     way to the host, and the slots and boxes come from the counts."""
     import inspect
     source = inspect.getsource(align.global_paths)
-    before, after = source.split("lib.gfy_align_global_trace(", 1)
+    before, after = source.split("return _traced(", 1)
     body = before.split('"""', 2)[2]
     for word in (".cpu(", ".numpy(", ".item(", ".tolist(", "bool(", "synchronize"):
         assert word not in body, word
-    assert "_launch_global(" in body and "rows_a + rows_b" in body
-    launch = inspect.getsource(align._launch_global)
+    assert '_launch(call, "global", within' in body and "rows_a + rows_b" in body
+    launch = inspect.getsource(align._launch) + inspect.getsource(align._symbol)
     for word in (".cpu(", ".numpy(", ".item(", ".tolist(", "bool(", "synchronize"):
         assert word not in launch, word
 
@@ -367,28 +367,28 @@ def test_c_abi_binds_and_names_what_it_refuses_without_a_gpu():
 
 # ---- registers ----------------------------------------------------------------------------------
 
-def _resource_line(tmp_path, source):
+def _resource_line(tmp_path, source, kernel):
     env = dict(os.environ, TMPDIR=str(tmp_path), GFY_SOURCE=source,
                GFY_ASM_OUT=str(tmp_path / (source + ".s")))
     done = subprocess.run(["bash", str(ROOT / "tools" / "pairwise_resources.sh")],
                           capture_output=True, text=True, timeout=900, env=env)
     assert done.returncode == 0, done.stderr[-2000:]
     print(done.stdout)
-    lines = [line for line in done.stdout.splitlines() if line.strip()]
-    assert len(lines) == 1, done.stdout          # one kernel per file
+    lines = [line for line in done.stdout.splitlines() if kernel + "E" in line]   # E: the name's end
+    assert len(lines) == 1, done.stdout          # one kernel of that name
     fields = lines[0].split()
     return lines[0], {word: int(fields[fields.index(word) + 1])
                       for word in ("vgpr", "spilled", "scratch", "barrier", "mfma", "ds128")}
 
 
 @pytest.mark.parametrize("source, kernel, twin, twin_kernel", (
-    ("align_global.hip", "k_align_global", "align_local.hip", "k_align_local"),
-    ("align_global_trace.hip", "k_align_global_trace", "align_trace.hip", "k_align_trace")))
+    ("align_kernels.hip", "k_align_global", "align_kernels.hip", "k_align_local"),
+    ("align_kernels.hip", "k_align_global_trace", "align_kernels.hip", "k_align_trace")))
 def test_the_global_kernels_keep_out_of_scratch(tmp_path, source, kernel, twin, twin_kernel):
     """No spill, no scratch, no workgroup barrier, at most the 512 registers of a SIMD's one
     wave, and the multiply of the local twin: the same MFMA and 16-byte LDS read counts."""
-    line, mine = _resource_line(tmp_path, source)
-    twin_line, theirs = _resource_line(tmp_path, twin)
+    line, mine = _resource_line(tmp_path, source, kernel)
+    twin_line, theirs = _resource_line(tmp_path, twin, twin_kernel)
     assert kernel in line and twin_kernel in twin_line
     assert mine["vgpr"] <= 512 and mine["spilled"] == 0 and mine["scratch"] == 0, line
     assert mine["barrier"] == 0, line

@@ -293,10 +293,9 @@ def _resources(source: str) -> dict:
 
 
 def test_the_null_kernel_does_not_spill_and_keeps_the_box_kernels_occupancy():
-    null = {name: values for name, values in _resources("align_null.hip").items()
-            if "k_align_local_null" in name}
-    box = {name: values for name, values in _resources("align_box.hip").items()
-           if "k_align_local_box" in name}
+    kernels = _resources("align_kernels.hip")
+    null = {name: values for name, values in kernels.items() if "k_align_local_null" in name}
+    box = {name: values for name, values in kernels.items() if "k_align_local_box" in name}
     assert len(null) == 1 and len(box) == 1
     (null,), (box,) = null.values(), box.values()
     assert null["SGPRs Spill"] == 0 and null["VGPRs Spill"] == 0 and null["ScratchSize"] == 0

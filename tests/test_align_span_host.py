@@ -290,16 +290,16 @@ def test_python_refuses_what_local_align_refuses(monkeypatch):
 # ---- registers ----------------------------------------------------------------------------------
 
 def test_the_span_kernel_keeps_out_of_scratch(tmp_path):
-    """align_span.hip holds one kernel, k_align_span: no spill, no scratch, no workgroup barrier,
+    """k_align_span of align_kernels.hip: no spill, no scratch, no workgroup barrier,
     and a wave within the 512 registers of its SIMD."""
-    env = dict(os.environ, TMPDIR=str(tmp_path), GFY_SOURCE="align_span.hip",
+    env = dict(os.environ, TMPDIR=str(tmp_path), GFY_SOURCE="align_kernels.hip",
                GFY_ASM_OUT=str(tmp_path / "align_span.s"))
     done = subprocess.run(["bash", str(ROOT / "tools" / "pairwise_resources.sh")],
                           capture_output=True, text=True, timeout=900, env=env)
     assert done.returncode == 0, done.stderr[-2000:]
     print(done.stdout)
-    lines = [line for line in done.stdout.splitlines() if line.strip()]
-    assert len(lines) == 1 and "k_align_span" in lines[0], done.stdout
+    lines = [line for line in done.stdout.splitlines() if "k_align_spanE" in line]   # E: the name's end
+    assert len(lines) == 1, done.stdout
     fields = lines[0].split()
     vgprs, spilled, scratch, barriers = (int(fields[fields.index(word) + 1])
                                          for word in ("vgpr", "spilled", "scratch", "barrier"))

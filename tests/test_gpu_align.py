@@ -34,7 +34,7 @@ pytestmark = pytest.mark.gpu
 COSINE_TOL = 2e-6        # tests/test_gpu_distance_ranges.py
 ROWS_A = (1, 63, 64, 65, 129, 200)      # strip edge 64
 ROWS_B = (1, 127, 128, 129, 257, 330)   # b-tile edges 32 and 128
-WAVES = 4                               # pairs per workgroup (align_local.hip)
+WAVES = 4                               # pairs per workgroup (align_local.inc)
 #: (match_scale, match_shift, gap_open, gap_extend)
 PARAMETERS = ((1.0, -0.3, 1.0, 0.25), (2.0, -0.5, 0.75, 0.0), (1.5, -0.4, 0.5, 0.5),
               (1.0, 0.0, 1.0, 0.5))

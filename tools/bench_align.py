@@ -8,7 +8,7 @@ this before the first run.  For scale only, a host numpy float32 dynamic program
 recurrences (anti-diagonal by anti-diagonal, from cosines the device computed) is timed on
 ``--host-pairs`` of the pairs.  Nothing else may run on the device.  The document names the run:
 host, UTC time, device, ROCm / torch versions, the commit (``--commit``, or ``git rev-parse
-HEAD`` where the tree is a checkout) and a SHA-256 of align_local.hip.  Writes one JSON document
+HEAD`` where the tree is a checkout) and a SHA-256 of align_kernels.hip.  Writes one JSON document
 (default profiles/align_bench.json) and prints it.
 
 ``--spans`` times ``align.local_spans`` (score, start and end) after ``local_align`` in the same
@@ -103,16 +103,9 @@ ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 from ginfinity_amd import align, distance, synthetic  # noqa: E402
 
-KERNEL_SOURCE = "align_local.hip"
-SPAN_SOURCES = ("align_local.inc", "align_span.hip")     # --spans: the shared body and its kernel
-PATH_SOURCES = ("align_local.inc", "align_span.hip", "align_trace.hip")   # --paths
-GLOBAL_SOURCES = ("align_local.inc", "align_global.hip")                  # --global, --within
-BAND_SOURCES = ("align_local.inc", "align_band.hip")                      # --band
-BOX_SOURCES = ("align_local.inc", "align_band.hip", "align_box.hip")      # --box
-GLOBAL_BOX_SOURCES = ("align_local.inc", "align_global.hip", "align_global_trace.hip",
-                      "align_global_box.hip", "align_box.hip")           # --global / --within --box
-VALUE_SOURCES = ("align_values.hip", "pairwise_sweep.inc")               # --values
-NULL_SOURCES = ("align_local.inc", "align_null.hip", "align_box.hip")    # --null
+KERNEL_SOURCE = "align_kernels.hip"
+ALIGN_SOURCES = ("align_local.inc", "align_kernels.hip")     # every alignment kernel: the shared body and its modes
+VALUE_SOURCES = ("align_values.hip", "pairwise_sweep.inc")   # --values
 BOX_RECORD_ROWS = 4096            # --box: rows of every record
 BOX_REGION_ROWS = 150             # --box: rows of the region a pair shares
 
@@ -249,7 +242,7 @@ def _global_box_bench(args) -> dict:
               "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
               "torch": torch.__version__, "commit": args.commit or _commit(),
               "source_sha256": {name: hashlib.sha256((source / name).read_bytes()).hexdigest()
-                                for name in GLOBAL_BOX_SOURCES},
+                                for name in ALIGN_SOURCES},
               "command": "python tools/bench_align.py " + " ".join(_measured_arguments()),
               "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
               "timed": "the whole call: host checks, the uploads, both launches, the compaction",
@@ -406,7 +399,7 @@ def _null_bench(args) -> dict:
             "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
             "torch": torch.__version__, "commit": args.commit or _commit(),
             "source_sha256": {name: hashlib.sha256((source / name).read_bytes()).hexdigest()
-                              for name in NULL_SOURCES},
+                              for name in ALIGN_SOURCES},
             "command": "python tools/bench_align.py " + " ".join(_measured_arguments()),
             "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
             "timed": "the whole call: host checks, the uploads, the launches; null_scores with the "
@@ -445,7 +438,7 @@ def _box_bench(args) -> dict:
               "device": torch.cuda.get_device_name(0), "hip": torch.version.hip,
               "torch": torch.__version__, "commit": args.commit or _commit(),
               "source_sha256": {name: hashlib.sha256((source / name).read_bytes()).hexdigest()
-                                for name in BOX_SOURCES},
+                                for name in ALIGN_SOURCES},
               "command": "python tools/bench_align.py " + " ".join(_measured_arguments()),
               "repeats": args.repeats, "warmup": args.warmup, "rates_use": "median",
               "timed": "the whole call: host checks, the upload of pairs, bands and boxes, the "
@@ -601,7 +594,7 @@ def main() -> None:
         result["spans_over_local_align"] = span_mid / mid
         result["spans_source_sha256"] = {
             name: hashlib.sha256((source.parent / name).read_bytes()).hexdigest()
-            for name in SPAN_SOURCES}
+            for name in ALIGN_SOURCES}
         print(f"local_spans: {span_mid:.4f} s = {cells / span_mid:.3e} cell updates/s, "
               f"{span_mid / mid:.3f} x local_align", file=sys.stderr, flush=True)
     for name, wanted, within in (("global", args.whole, False), ("within", args.within, True)):
@@ -617,7 +610,7 @@ def main() -> None:
                         "over_local_align": mode_mid / mid}
         result["global_source_sha256"] = {
             source_name: hashlib.sha256((source.parent / source_name).read_bytes()).hexdigest()
-            for source_name in GLOBAL_SOURCES}
+            for source_name in ALIGN_SOURCES}
         print(f"global_align(within={within}): {mode_mid:.4f} s = {args.pairs / mode_mid:.3e} "
               f"pairs/s, {cells / mode_mid:.3e} cell updates/s, {mode_mid / mid:.3f} x local_align",
               file=sys.stderr, flush=True)
@@ -629,7 +622,7 @@ def main() -> None:
                                                     args.repeats, args.warmup)
         result["paths_source_sha256"] = {
             name: hashlib.sha256((source.parent / name).read_bytes()).hexdigest()
-            for name in PATH_SOURCES}
+            for name in ALIGN_SOURCES}
         for name in ("paths", "paths_self"):
             part = result[name]
             print(f"{name}: local_spans {part['spans_seconds']['median']:.4f} s, local_paths "
@@ -660,7 +653,7 @@ def main() -> None:
                     args.warmup)
         part["source_sha256"] = {
             name: hashlib.sha256((source.parent / name).read_bytes()).hexdigest()
-            for name in BAND_SOURCES}
+            for name in ALIGN_SOURCES}
         result["band"] = part
         for name, timed in part.items():
             if isinstance(timed, dict) and "over_unbanded" in timed:

@@ -4,8 +4,7 @@
 #   GFY_SOURCE=pairwise_topk.hip bash tools/pairwise_resources.sh     # the top-k kernels
 #   GFY_SOURCE=pairwise_topk_ranges.hip bash tools/pairwise_resources.sh   # ... with per-row ranges
 #   GFY_SOURCE=pairwise_within.hip bash tools/pairwise_resources.sh   # the radius search (count, fill, order)
-#   GFY_SOURCE=align_local.hip bash tools/pairwise_resources.sh       # the local aligner (no scratch, no barrier)
-#   GFY_SOURCE=align_span.hip bash tools/pairwise_resources.sh        # ... with start cells
+#   GFY_SOURCE=align_kernels.hip bash tools/pairwise_resources.sh     # the aligners (no scratch, no barrier)
 # Per kernel: registers, spills, scratch, and how many MFMA, LDS-DMA, 16-byte LDS read and barrier
 # instructions its code holds (the figures a refactor of the sweep must leave alone).
 # The assembly is left in $GFY_ASM_OUT (default /tmp/<source stem>.s, i.e. /tmp/pairwise.s).
